@@ -17,9 +17,14 @@ total work is fixed ("scaling": "strong").
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel K2 (k_reproject): algorithmic bytes per launch
 (12*P + 48*N + 4*N*P + 4*N per frame) over the average launch duration measured with HIP events on the engine's
-stream inside the timed region (every launch when steps <= 64).  `single_frame` repeats the measurement with ONE frame per step (the
-literal configs[1]); `rates` separates the kernel-only (K2) rate from the per-image (K1+K2+K3) rate.  `cpu_baseline` is the CPU oracle
-(a port of the reference path, g++ -Ofast -fopenmp) timed on this box's host cores on a bounded sample, plus a 1-thread number.
+stream inside the timed region (every launch when steps <= 64).  `rates` separates the kernel-only (K2) rate from the per-image
+(K1+K2+K3) rate.
+
+A plain run sets up, warms up, times --steps steps and prints that line.  --full adds the side measurements after the timed steps:
+`repeats`, `roofline.store_schedule_only_us`, `k2_forms`, `soft_only`, `single_frame` (ONE frame per step, the literal configs[1]),
+`reference_size`, `process_image`, `strong` with more than one rank, `cpu_baseline` (the CPU oracle, a port of the reference path,
+g++ -Ofast -fopenmp, timed on the host's cores on a bounded sample, plus a 1-thread number) and `host_driver`.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs); the step's inputs depend on the arguments only.
 """
 import argparse
 import json
@@ -117,6 +122,28 @@ def event_stride_for(steps, requested):
     return 1 if steps <= 64 else max(1, steps // 64)
 
 
+ERR_SAMPLE = 1 << 22  # error-image cells written by --dump-outputs (16 MB); a step's whole error images are 4 B x hypotheses x pixels (5 GB by default)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: arrays (name -> tensor on the GPU) as path/<name>.npy.  Integer and byte outputs are written as float64 / float32 (exact); an
+    "err" entry larger than ERR_SAMPLE cells is replaced by its cells at a fixed, seeded sample of flat indices (the same for every run of one shape)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        if name == "err" and t.numel() > ERR_SAMPLE:
+            idx = np.sort(np.random.default_rng(1305).choice(t.numel(), size=ERR_SAMPLE, replace=False, shuffle=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype.itemsize >= 4 else np.float32) if a.dtype.kind in "iub" else a
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        total += a.nbytes
+        assert total <= DUMP_LIMIT_BYTES, "--dump-outputs: more than %d MB" % (DUMP_LIMIT_BYTES >> 20)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -162,6 +189,13 @@ def parse_args(argv=None):
                          "fast (fp32 matrix-core transform, rounds 2-5), precise (fp64 on the vector ALU)")
     ap.add_argument("--no-k2-forms", action="store_true", help="skip the measurement of K2's other arithmetic forms (`k2_forms`)")
     ap.add_argument("--dry-run", action="store_true", help="exercise launch / shard / gather / reporting without touching a GPU (CPU tests, gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the side measurements: re-runs of the timed region, the store-only and other K2 forms, soft-inlier-only "
+                         "launches, one frame per step, the reference size, processImage, the strong-scaling leg with more than one rank, the CPU baseline and "
+                         "the C++ host programs.  Without it the run times the steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64); the error images as a fixed, seeded sample of "
+                         "%d cells" % ERR_SAMPLE)
     return ap.parse_args(argv)
 
 
@@ -619,7 +653,7 @@ def run_dry(args, rank, world, dist):
         total = N * args.frames_per_step * K * world
         scaling, per_step = "weak", args.frames_per_step * world
     strong = None
-    if args.workload == "frames" and (world > 1 or args.emulate_world > 1):
+    if args.workload == "frames" and ((args.full and world > 1) or args.emulate_world > 1):
         strong = dry_strong(args, rank, world, dist)
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64)
@@ -767,6 +801,8 @@ def run_config5(args, rank, local_rank, world, backend, dist):
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.dump_outputs and (args.dry_run or args.workload == "config5"):
+        raise SystemExit("--dump-outputs: the frames and config3 workloads only (no outputs in a dry run or a training step)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no torchrun environment: this process becomes the launcher of the N ranks
         sys.exit(launch_ranks(args.gpus, sys.argv[1:] if argv is None else argv))
@@ -931,11 +967,18 @@ def main(argv=None):
         nb = bufs[1 - k]
         set_frames_of(eng, xyz_batches[(i + 1) & 1])  # borrowed frames: the slot remembers the frame it was sampled from
         eng.sampleAhead(1 - k, NB, seed_of(i + 1), nb["poses"], nb["sets"], nb["ok"], thr=10.0, max_tries=1 << 16)
+        score_slot(k)
+
+    def score_slot(k):
         b = bufs[k]
-        eng.scoreSampled(k, b["poses"], b["soft"], b["w"], ent=b["ent"], avg=b["avg"], err=err_shared, clamp=100.0, tau=10.0, beta=0.5, scale=0.1)
+        engines[0][0].scoreSampled(k, b["poses"], b["soft"], b["w"], ent=b["ent"], avg=b["avg"], err=err_shared, clamp=100.0, tau=10.0, beta=0.5, scale=0.1)
 
     def step_config3(i):
         runner.step(i)  # enqueues only; results are collected by runner.drain() (inside the timed region, once)
+
+    def buf_of(i):
+        """the result arrays step i writes"""
+        return bufs[(i & 1) if (pipelined or staged or defer_on[0]) else (i % n_ctx)]
 
     def step(i):
         if config3:
@@ -945,7 +988,7 @@ def main(argv=None):
         if staged:
             return step_staged(i)
         eng, _ = engines[i % n_ctx]
-        b = bufs[(i & 1) if defer_on[0] else (i % n_ctx)]
+        b = buf_of(i)
         if batched:
             # three launches for B frames: K1 over B*N waves, K2 over B*N error images, K3 with one workgroup per frame
             eng.scoreHypothesesFrames(N, seed=seed_of(i), thr=10.0, max_tries=1 << 16, clamp=100.0, tau=10.0, beta=0.5, scale=0.1,
@@ -1020,19 +1063,33 @@ def main(argv=None):
             em_early = run_emulation()
         runner = make_runner()
 
+    def prime_pipeline():
+        # the pipelined mode scores at step i what step i - 1 sampled ahead: step 0's poses are sampled here
+        set_frames_of(engines[0][0], xyz_batches[0])
+        engines[0][0].sampleAhead(0, NB, seed_of(0), bufs[0]["poses"], bufs[0]["sets"], bufs[0]["ok"], thr=10.0, max_tries=1 << 16)
+
     if pipelined:
         err_shared = bufs[0]["err"]  # the scoring stage is serial: one error-image buffer
-        engines[0][0].sampleAhead(0, NB, seed_of(0), bufs[0]["poses"], bufs[0]["sets"], bufs[0]["ok"], thr=10.0, max_tries=1 << 16)
+        prime_pipeline()
     # untimed settling phase (not steps): the same work until --prewarm-ms have passed, so that clocks, TLBs and the power governor are in
     # their sustained state when the warm-up steps start
-    ctr = 0  # steps are numbered consecutively across pre-warm, warm-up and timed region (the pipelined mode's slots alternate strictly)
+    ctr = 0  # steps are numbered consecutively (result arrays, pipeline slots and frame batches alternate with the step's parity)
     t_pre = time.perf_counter()
-    while (time.perf_counter() - t_pre) * 1e3 < args.prewarm_ms:
+    while (time.perf_counter() - t_pre) * 1e3 < args.prewarm_ms or ctr % 2:
         step(ctr)
         ctr += 1
         if ctr % 8 == 0:
             sync_all()
     n_pre = ctr
+    if n_pre:
+        # the settling phase ran for a time, not a number of steps: the warm-up and timed steps start again at step 0 (an even number of
+        # steps later), so that the same arguments time the same inputs in every run (--dump-outputs)
+        ctr = 0
+        if pipelined:
+            score_slot(0)  # what the last settling step sampled ahead under its own step number
+            sync_all()
+            prime_pipeline()
+        sync_all()
     for i in range(Wm):
         step(ctr)
         ctr += 1
@@ -1062,9 +1119,20 @@ def main(argv=None):
         ms, n = eng.profile_read(0, reset=True)
         k2_ms += ms
         k2_n += n
+    if args.dump_outputs and rank == 0:
+        if config3:
+            dump_outputs(args.dump_outputs, {"results": last})  # per image: refined pose (6), loss / errors (4), softmax weights (N)
+        else:
+            b = buf_of(ctr - 1)
+            outs = {} if args.kernel_only else {k_: b[k_] for k_ in ("poses", "sets", "ok", "w", "ent", "avg")}
+            if args.k2_mode != "err":
+                outs["soft"] = b["soft"]
+            if args.k2_mode != "soft":
+                outs["err"] = err_shared if pipelined else b["err"]
+            dump_outputs(args.dump_outputs, outs)
     # the same K steps again, a few times: the spread of the step time on this box (the timed region above is ONE sample of K steps)
     repeats = None
-    if rank == 0 and not config3 and not distributed:
+    if args.full and rank == 0 and not config3 and not distributed:
         reps = []
         for _ in range(5):
             sync_all()
@@ -1090,7 +1158,7 @@ def main(argv=None):
     # The ceiling of K2's own write pattern ON THIS BOX: the same launches with k2_flags bit 1 (the kernel issues its store schedule only, no
     # arithmetic; include/dsac_hip.h).  The pool's boxes differ by several per cent for the same binary; this number moves with them.
     store_only_us = None
-    if rank == 0 and not config3 and args.k2_mode != "soft" and not args.separate_calls:
+    if args.full and rank == 0 and not config3 and args.k2_mode != "soft" and not args.separate_calls:
         try:
             for eng, _ in engines:
                 eng.set_option("k2_flags", K2_FORMS[args.k2_form][0] | 2)
@@ -1116,7 +1184,7 @@ def main(argv=None):
     # the OTHER arithmetic forms of K2 at the same launch shape, inside the driver's own line -- the form `value` is measured on and the forms that
     # restate more of the reference's double-precision projection (core/cnn_softam.h:319-362), each with the tolerance it is tested at (`tolerance` below)
     k2_forms = None
-    if rank == 0 and not config3 and args.k2_mode != "soft" and not args.separate_calls and not args.kernel_only and not args.no_k2_forms:
+    if args.full and rank == 0 and not config3 and args.k2_mode != "soft" and not args.separate_calls and not args.kernel_only and not args.no_k2_forms:
         k2_forms = {}
         for name, (flags, auto) in K2_FORMS.items():
             if name == args.k2_form:
@@ -1159,7 +1227,7 @@ def main(argv=None):
             eng.profile_read(0, reset=True)
     # SURVEY.md 8(d) secondary line: the same launches WITHOUT the error-image output (fused soft-inlier mode): K2 is then VALU-bound
     soft_only = None
-    if rank == 0 and batched and not config3 and not pipelined and args.k2_mode == "both":
+    if args.full and rank == 0 and batched and not config3 and not pipelined and args.k2_mode == "both":
         eng, _ = engines[0]
         b = bufs[0]
         eng.profile_read(0, reset=True)
@@ -1193,7 +1261,7 @@ def main(argv=None):
 
     # literal configs[1]: ONE frame per step on the same context (fused call), its own K2 timing
     single = None
-    if not args.no_single_frame and not args.kernel_only and not config3 and args.k2_mode == "both" and rank == 0:
+    if args.full and not args.no_single_frame and not args.kernel_only and not config3 and args.k2_mode == "both" and rank == 0:
         eng, _ = engines[0]
         b = bufs[0]
         x1 = xyz_batches[0][0] if batched else xyz_batches[0]
@@ -1254,7 +1322,7 @@ def main(argv=None):
     # BASELINE.json configs[0] / SURVEY.md 8(d) config 1 in the reference-exact mode: P = 40 x 40 sub-sampled map, int16-quantised
     # coordinates, 256 hypotheses, one frame per step (K1 -> K2 -> K3); 32 such frames per step as well (what a GPU is fed with)
     refsize = None
-    if not args.no_single_frame and not args.kernel_only and not config3 and args.k2_mode == "both" and rank == 0:
+    if args.full and not args.no_single_frame and not args.kernel_only and not config3 and args.k2_mode == "both" and rank == 0:
         eng, _ = engines[0]
         f40 = synth.chess_like_frame(40, 40, seed=1305, quantise_int16=True)
         x40 = torch.from_numpy(f40["xyz"]).to(dev)
@@ -1297,7 +1365,7 @@ def main(argv=None):
     # the reference's test-time unit of work (test_ransac_softam.cpp:97-157): processImage of ONE image -- K1 -> K2 -> K3, then the 8-step
     # inlier refinement of the soft-argmax pose (K6) and the pose loss (K7) -- device-resident, at full and at reference size
     procimg = None
-    if not args.no_single_frame and not args.kernel_only and not config3 and args.k2_mode == "both" and rank == 0:
+    if args.full and not args.no_single_frame and not args.kernel_only and not config3 and args.k2_mode == "both" and rank == 0:
         from dsac_amd.capi import lib as _lib, ptr as _ptr, check as _check
         eng, _ = engines[0]
         b = bufs[0]
@@ -1416,7 +1484,7 @@ def main(argv=None):
     # over the N ranks, the result rows exchanged over RCCL inside the timed region -- next to the weak-scaling `value`; on one GPU --emulate-world W fills
     # the same fields from the emulation of one rank's share
     strong = None
-    if not config3 and not args.kernel_only and args.k2_mode == "both" and (world > 1 or args.emulate_world > 1):
+    if not config3 and not args.kernel_only and args.k2_mode == "both" and ((args.full and world > 1) or args.emulate_world > 1):
         for b_ in bufs[1:]:
             b_["err"] = None  # the leg's runners write into the first context's error-image buffer; drop the others
         strong = strong_scaling_leg(args, rank, local_rank, world, backend, dist if distributed else None, emulate_world=args.emulate_world,
@@ -1509,9 +1577,9 @@ def main(argv=None):
             out["emulation"] = emulation
         if strong is not None:
             out["strong"] = strong
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, fr, N, H, W)
-        if (not args.no_host_driver and world == 1 and not config3 and not args.kernel_only and args.k2_mode == "both" and not args.no_single_frame
+        if (args.full and not args.no_host_driver and world == 1 and not config3 and not args.kernel_only and args.k2_mode == "both" and not args.no_single_frame
                 and N % 128 == 0):
             hd = host_driver_leg(N, H, W, device=local_rank)
             ref = (procimg or {}).get("%dx%d_batch_of_%d_refinement_under_the_next_batch" % (W, H, B)) if batched else None

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 nproc > $O/nproc.txt
 echo "== bench 2 contexts, frames round-robin (K2 launches may overlap)"; timeout 600 python bench.py --frames-per-step 1 --streams 2 --overlap frames --no-cpu-baseline 2>/dev/null | tail -1 | tee $O/bench_frames2.json | cut -c1-200
 echo "== bench in-context pipeline"; timeout 600 python bench.py --frames-per-step 1 --streams 1 --overlap pipeline --no-cpu-baseline 2>/dev/null | tail -1 | tee $O/bench_pipeline.json | cut -c1-200
-echo "== bench (default)"; timeout 600 python bench.py 2>/dev/null | tail -1 | tee $O/bench_default.json | cut -c1-400
+echo "== bench (default)"; timeout 600 python bench.py --full 2>/dev/null | tail -1 | tee $O/bench_default.json | cut -c1-400
 echo "== bench single frame per step, 2 contexts gated"; timeout 600 python bench.py --frames-per-step 1 --streams 2 --overlap gated --no-cpu-baseline 2>/dev/null | tail -1 | tee $O/bench_single_gated2.json | cut -c1-200
 echo "== bench 8 frames per step, 2 contexts gated"; timeout 600 python bench.py --frames-per-step 8 --streams 2 --overlap gated --no-cpu-baseline 2>/dev/null | tail -1 | tee $O/bench_batch8_gated2.json | cut -c1-200
 echo "== bench single frame per step, no overlap"; timeout 600 python bench.py --frames-per-step 1 --streams 1 --overlap frames --event-stride 1 --no-cpu-baseline 2>/dev/null | tail -1 | tee $O/bench_streams1.json | cut -c1-200

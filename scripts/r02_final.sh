@@ -3,7 +3,7 @@
 REPO="${GRAFT_REPO_ROOT:-/root/repo}"; cd "$REPO"; O=gpurun_out/r02f; mkdir -p $O; export TMPDIR=/tmp
 timeout 1800 python -m pytest tests -m gpu -q --timeout 900 2>&1 | tail -6 | tee $O/pytest_gpu.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $O/smoke.log
-timeout 600 python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_driver_flags.json
+timeout 600 python bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_driver_flags.json
 cd /tmp; rm -rf /tmp/kt; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -o k -- python $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-single-frame > /tmp/kt.log 2>&1
 cp /tmp/kt/k_kernel_stats.csv $REPO/$O/bench_driver_flags_kernel_stats.csv
 python - /tmp/kt/k_kernel_trace.csv $REPO/$O/bench_driver_flags.json <<'PY' | tee $REPO/$O/bench_vs_rocprof.txt

@@ -5,6 +5,6 @@ fmt='import sys,json; d=json.loads(sys.stdin.read()); print("%.1f us/step  %.3f 
 {
 for wide in 0 2 4; do
   echo "== k1_wide $wide"; DSAC_K1_WIDE=$wide python scripts/k1_bench.py 2>/dev/null | head -3 | tail -2
-  DSAC_K1_WIDE=$wide timeout 300 python bench.py --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "$fmt"
+  DSAC_K1_WIDE=$wide timeout 300 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "$fmt"
 done
 } | tee $O/k1_wide.txt

@@ -4,7 +4,7 @@ timeout 900 python -m pytest tests/test_gpu_forward.py tests/test_gpu_edge.py te
 fmt='import sys,json; d=json.loads(sys.stdin.read()); print("%.1f us/step  %.3f Mhyp/s  frac %.3f  K2 %.1f us | single frame %.1f us/frame %.3f Mhyp/s" % (d["ms_per_step"]*1e3, d["value"]/1e6, d["roofline"]["frac"], d["roofline"]["avg_launch_us"], d["single_frame"]["us_per_frame"], d["single_frame"]["value"]/1e6))'
 {
 for sh in 0 4 8; do
-  r=$(DSAC_K1_SHARE=$sh timeout 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "$fmt")
+  r=$(DSAC_K1_SHARE=$sh timeout 300 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "$fmt")
   echo "default mode, K1 share $sh: $r"
   DSAC_K1_SHARE=$sh python scripts/k1_bench.py 2>/dev/null | tail -5
 done

@@ -6,8 +6,8 @@ REPO="${GRAFT_REPO_ROOT:-/root/repo}"
 cd "$REPO"; O=gpurun_out/r02p; mkdir -p $O
 export TMPDIR=/tmp
 nproc > $O/nproc.txt
-echo "== bench, driver flags"; timeout 600 python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 | tee $O/bench_driver_flags.json | cut -c1-300
-echo "== bench (default)"; timeout 600 python bench.py 2>/dev/null | tail -1 | tee $O/bench_default.json | cut -c1-300
+echo "== bench, driver flags"; timeout 600 python bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 | tee $O/bench_driver_flags.json | cut -c1-300
+echo "== bench (default)"; timeout 600 python bench.py --full 2>/dev/null | tail -1 | tee $O/bench_default.json | cut -c1-300
 echo "== bench K2 only, N=4096 (configs[2])"; for m in err both; do timeout 600 python bench.py --steps 30 --warmup 5 --hyps 4096 --kernel-only --no-cpu-baseline --streams 1 --k2-mode $m 2>/dev/null | tail -1 | tee $O/bench_k2only_4096_$m.json | cut -c1-120; done
 echo "== bench K2 only, N=256"; for m in err both; do timeout 600 python bench.py --steps 200 --warmup 20 --kernel-only --no-cpu-baseline --streams 1 --k2-mode $m 2>/dev/null | tail -1 | tee $O/bench_k2only_256_$m.json | cut -c1-120; done
 echo "== bench configs[3] on one GPU"; timeout 600 python bench.py --workload config3 --steps 10 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 | tee $O/bench_config3_1gpu.json | cut -c1-300

@@ -2,7 +2,7 @@
 # does GPU_MAX_HW_QUEUES (HIP's number of hardware queues per device, default 4) matter for the bench process, which holds more streams than that?
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; O=gpurun_out/r04hq; mkdir -p $O
 for q in 4 8 4 8; do
-  GPU_MAX_HW_QUEUES=$q timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-host-driver 2>>$O/err.log | tail -1 > $O/b_$q.json
+  GPU_MAX_HW_QUEUES=$q timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-host-driver 2>>$O/err.log | tail -1 > $O/b_$q.json
   GPU_MAX_HW_QUEUES=$q timeout 600 python bench.py --workload config3 --steps 20 --warmup 5 --emulate-world 8 --no-cpu-baseline 2>>$O/err.log | tail -1 > $O/c_$q.json
   python - <<PY
 import json

@@ -6,7 +6,7 @@ nproc > $O/nproc.txt; cat /sys/fs/cgroup/cpu.max >> $O/nproc.txt 2>/dev/null
 echo "== pytest -m gpu -q -s (margins -> $O/parity_margins.txt)"
 DSAC_MARGINS_FILE=$REPO/$O/parity_margins.txt timeout 2400 python -m pytest tests -m gpu -q -s -p no:cacheprovider > $O/pytest_gpu_full.log 2>&1; tail -3 $O/pytest_gpu_full.log | tee $O/pytest_gpu.log
 echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee $O/smoke.log
-echo "== bench, driver flags"; timeout 900 python bench.py --steps 20 --warmup 5 2>$O/bench.err | tail -1 | tee $O/bench_driver_flags.json | cut -c1-300
+echo "== bench, driver flags"; timeout 900 python bench.py --full --steps 20 --warmup 5 2>$O/bench.err | tail -1 | tee $O/bench_driver_flags.json | cut -c1-300
 echo "== bench, driver flags, on the fp32 form (for the record)"; timeout 900 python bench.py --steps 20 --warmup 5 --k2-form fast --no-cpu-baseline --no-host-driver --no-k2-forms 2>>$O/bench.err | tail -1 | tee $O/bench_driver_flags_fast_form.json | cut -c1-200
 echo "== the strong object: one GPU emulating rank 0 / 7 of 8"
 for r in 0 7; do timeout 600 python bench.py --steps 20 --warmup 5 --emulate-world 8 --emulate-rank $r --no-cpu-baseline --no-host-driver --no-single-frame --no-k2-forms 2>>$O/bench.err | tail -1 > $O/bench_em8_rank$r.json; python -c "

@@ -143,21 +143,51 @@ def _json_line(stdout):
 def test_gpus_flag_launches_the_ranks_itself():
     """`python bench.py --gpus 2` without a torchrun environment spawns 2 ranks (gloo here, RCCL on the GPUs), and the line reports the
     number of ranks that joined.  --dry-run replaces the engine; launch, rendezvous, MAX-over-ranks timing and the line are the real code."""
-    r = _run_bench("--gpus", "2", "--steps", "3", "--dry-run")
+    r = _run_bench("--gpus", "2", "--steps", "3", "--dry-run", "--full")
     assert r.returncode == 0, r.stderr
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["steps"] == 3
     assert d["config"]["frames_per_step_all_ranks"] == 32  # 16 frames per rank
     # round 5: with more than one rank the SAME line carries north_star's strong-scaling claim -- configs[3], 64 images fixed, sharded, the result rows
-    # exchanged by the backend inside the timed region -- next to the weak-scaling value
+    # exchanged by the backend inside the timed region -- next to the weak-scaling value (with --full: a plain run measures the headline only)
     _check_strong(d["strong"], ranks=2, shards=2)
+    r = _run_bench("--gpus", "2", "--steps", "3", "--dry-run")
+    assert r.returncode == 0, r.stderr
+    assert "strong" not in _json_line(r.stdout)
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_same_inputs_and_dumps_them(tmp_path):
+    """A plain run prints the headline line without the side measurements of --full; --dump-outputs writes what the last timed step computed, and two runs
+    with the same arguments time the same inputs (the settling phase runs for a time, not a number of steps)."""
+    import numpy as np
+    flags = ("--gpus", "1", "--steps", "3", "--warmup", "1", "--hyps", "128", "--height", "96", "--width", "128", "--frames-per-step", "4", "--prewarm-ms", "50")
+    names = ("poses", "sets", "ok", "soft", "w", "ent", "avg", "err")
+    outs = []
+    for k in range(2):
+        r = _run_bench(*flags, "--dump-outputs", str(tmp_path / str(k)))
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        d = _json_line(r.stdout)
+        assert d["steps"] == 3 and d["warmup"] == 1 and abs(d["value"] - 4 * 128 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        for key in ("repeats", "k2_forms", "soft_only", "single_frame", "reference_size", "process_image", "strong", "cpu_baseline", "host_driver"):
+            assert key not in d, key
+        outs.append({n: np.load(str(tmp_path / str(k) / (n + ".npy"))) for n in names})
+    a, b = outs
+    for n in names:
+        assert a[n].dtype in (np.float32, np.float64) and a[n].shape == b[n].shape, n
+    assert a["poses"].shape == (4 * 128, 6) and a["ent"].shape == (4,)
+    assert a["err"].shape == (1 << 22,)  # of 4 x 128 x 96 x 128 cells: the seeded sample
+    assert np.array_equal(a["sets"], b["sets"]) and np.array_equal(a["ok"], b["ok"])
+    for n in ("poses", "err", "soft", "w", "ent", "avg"):
+        assert np.abs(a[n] - b[n]).max() <= 1e-9 * max(1.0, np.abs(a[n]).max()), n
+    assert np.abs(a["w"].reshape(4, 128).sum(1) - 1).max() < 1e-9
 
 
 def test_the_command_the_driver_runs_at_eight_ranks():
-    """`bench.py --gpus 8` as the driver launches it on an 8-GPU node -- 8 processes, one rendezvous, the weak line plus the `strong` object
+    """`bench.py --gpus 8 --full` as the driver launches it on an 8-GPU node -- 8 processes, one rendezvous, the weak line plus the `strong` object
     (configs[3]: 64 images, 8 per rank and step, one gather of 8 x 8 x (10 + N) doubles) -- exercised here with 8 CPU ranks over gloo (--dry-run: the stand-in
     engine; launch, sharding, exchange, max-over-ranks timing and reporting are the real code)."""
-    r = _run_bench("--gpus", "8", "--steps", "2", "--dry-run")
+    r = _run_bench("--gpus", "8", "--steps", "2", "--dry-run", "--full")
     assert r.returncode == 0, r.stderr
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 8 and d["scaling"] == "weak" and d["steps"] == 2
@@ -256,7 +286,8 @@ def test_timing_collectives_fall_back_to_gloo_when_rccl_cannot_start(tmp_path):
     script = tmp_path / "rank.py"
     script.write_text(_FALLBACK_RANK)
     port = str(29600 + os.getpid() % 300)
-    env = dict(os.environ)
+    # no device visible to the ranks, also where the suite runs beside a GPU: the two pretended GPUs must not be backed by a real one
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
     env.pop("DSAC_BENCH_BACKEND", None)
     procs = [subprocess.Popen([sys.executable, str(script), str(r), port, os.path.join(ROOT, "bench.py")], env=env, stdout=subprocess.PIPE,
                               stderr=subprocess.PIPE, text=True) for r in range(2)]
