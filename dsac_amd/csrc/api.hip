@@ -59,6 +59,9 @@ struct dsac_ctx {
     // scratch, one buffer per role so that calls can be chained without aliasing
     DevBuf rs_states, rs_scratch, rs_small, k6_scratch;  // the reference's random streams (dsac_refstream_init) and the scratch of a sampling window
     int rs_threads = 0, rs_mode = DSAC_RS_DEFAULT_MODE;
+    // "pi_refstream": dsac_process_images / _begin draw their sets with the enqueue-only chain of dsac_sample_refstream_frames instead of K1's counter stream;
+    // "pi_refstream_discard0": outputs generator 0 skips before every image; "pi_refstream_attempts": budget per stream and image (0 = rs::default_budget)
+    int pi_refstream = 0, pi_refstream_discard0 = 0, pi_refstream_attempts = 0;
     int k6_walk_exact = 0;  // "k6_walk_exact": 1 = the split walk decides every cell by the fp64 residual (no fp32 filter; A/B)
     int k6_waves = 0;  // "k6_waves": waves per refinement problem of K6's walk (0 = by the problem count)
     DevBuf staged, staged_lo, staged_split, soft_part, bwd_staged, dRdH, grad_part, g12_part, g6;
@@ -267,6 +270,38 @@ static hipError_t k2_records_lo(dsac_ctx* c, hipStream_t st, int N, const double
         int rc__ = (expr);           \
         if (rc__ != DSAC_OK) return rc__; \
     } while (0)
+
+// The enqueue-only chain of dsac_sample_refstream_frames for the frames of c->F on the context's stream (also K1 of dsac_process_images with
+// "pi_refstream").  The generators, the window scratch and the counters are touched on that stream only, so calls order themselves; the scratch is sized
+// BEFORE the first launch of a call and a regrowth goes through hipFree, which waits for the device: never freed under a chain in flight.
+constexpr unsigned long long RS_MAX_DISCARD0 = 1ull << 24;
+// the checks of a chain and its window ladder; nothing is enqueued or allocated here
+int refstream_plan(dsac_ctx* c, const char* who, int N, long long max_attempts, unsigned long long discard0, int* windows, int* n_windows) {
+    if (c->rs_threads <= 0) return fail(c, DSAC_ERR_INVALID, "%s: call dsac_refstream_init first", who);
+    if (max_attempts <= 0) return fail(c, DSAC_ERR_INVALID, "%s: max_attempts (per stream and image) must be > 0", who);
+    if (discard0 > RS_MAX_DISCARD0) return fail(c, DSAC_ERR_INVALID, "%s: at most 2^24 outputs are skipped per image (dsac_refstream_discard takes more)", who);
+    if (c->F.P < 4) return fail(c, DSAC_ERR_INVALID, "%s: frame has fewer than 4 cells", who);
+    const int want = (N + c->rs_threads - 1) / c->rs_threads;  // the largest static chunk
+    const int K = rs::window_ladder(want, max_attempts, windows, rs::MAX_WINDOWS);
+    if (K > rs::MAX_WINDOWS)
+        return fail(c, DSAC_ERR_INVALID, "%s: a budget of %lld attempts for %d hypotheses per stream needs %d windows, the limit is %d", who, max_attempts, want, K,
+                    rs::MAX_WINDOWS);
+    *n_windows = K;
+    return DSAC_OK;
+}
+int refstream_chain_call(dsac_ctx* c, const char* who, int N, float thr, long long max_attempts, unsigned long long discard0, double* d_poses, int32_t* d_sets,
+                         uint8_t* d_ok, float* d_staged, unsigned long long* d_consumed, long long* d_attempts) {
+    int windows[rs::MAX_WINDOWS], K = 0;
+    ARG_TRY(refstream_plan(c, who, N, max_attempts, discard0, windows, &K));
+    const int T = c->rs_threads, frames = c->F.frames > 1 ? c->F.frames : 1;
+    int stride = 0;
+    for (int k = 0; k < K; k++) stride = std::max(stride, windows[k]);
+    HIP_TRY(c, c->rs_scratch.reserve(dk::refstream_window_bytes(T, stride)));
+    HIP_TRY(c, c->rs_small.reserve((size_t)T * 32));
+    HIP_TRY(c, dk::refstream_chain(c->stream, c->rs_states.as<dk::RefStreamState>(), T, N, frames, windows, K, c->rs_mode, c->rs_scratch.p, c->rs_small.p, c->F, (int)thr,
+                                   discard0, d_poses, d_sets, d_ok, d_staged, d_consumed, d_attempts));
+    return DSAC_OK;
+}
 
 // dsac_gather_rows: row i of dst = row idx.r[i] of src, rows of `words` 32-bit words; blockIdx.y = destination row.  The indices travel as a kernel
 // argument (no device buffer, no upload): up to 256 rows per launch.
@@ -683,6 +718,39 @@ int dsac_sample_refstream(dsac_ctx* c, int N, float thr, long long max_attempts,
     return end_call(c);
 }
 
+int dsac_sample_refstream_frames(dsac_ctx* c, int hyps_per_frame, float thr, long long max_attempts, unsigned long long discard0_per_image, double* poses,
+                                 int32_t* sets_out, uint8_t* ok, unsigned long long* consumed32_or_null, long long* attempts_or_null) {
+    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_sample_refstream_frames: ctx is NULL");
+    if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "dsac_sample_refstream_frames: no frame set");
+    if (hyps_per_frame < 0 || !poses || !sets_out || !ok)
+        return fail(c, DSAC_ERR_INVALID, "dsac_sample_refstream_frames: hyps_per_frame >= 0 and poses/sets_out/ok must be non-NULL");
+    const int frames = c->F.frames > 1 ? c->F.frames : 1;
+    if ((long long)hyps_per_frame * frames > (1ll << 24)) return fail(c, DSAC_ERR_INVALID, "dsac_sample_refstream_frames: too many hypotheses");
+    if (c->rs_threads <= 0) return fail(c, DSAC_ERR_INVALID, "dsac_sample_refstream_frames: call dsac_refstream_init first");
+    if (max_attempts == 0) max_attempts = rs::default_budget((hyps_per_frame + c->rs_threads - 1) / c->rs_threads);
+    {
+        int windows[rs::MAX_WINDOWS], K = 0;  // every check before anything is staged or enqueued
+        ARG_TRY(refstream_plan(c, "dsac_sample_refstream_frames", hyps_per_frame, max_attempts, discard0_per_image, windows, &K));
+    }
+    if (hyps_per_frame == 0) return DSAC_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    begin_call(c);
+    const size_t N = (size_t)hyps_per_frame * frames, FT = (size_t)frames * c->rs_threads;
+    double* d_poses;
+    int32_t* d_sets;
+    uint8_t* d_ok;
+    unsigned long long* d_consumed;
+    long long* d_attempts;
+    ARG_TRY(out_arg(c, poses, N * 6, &d_poses));
+    ARG_TRY(out_arg(c, sets_out, N * 4, &d_sets));
+    ARG_TRY(out_arg(c, ok, N, &d_ok));
+    ARG_TRY(out_arg(c, consumed32_or_null, FT, &d_consumed));
+    ARG_TRY(out_arg(c, attempts_or_null, FT, &d_attempts));
+    ARG_TRY(refstream_chain_call(c, "dsac_sample_refstream_frames", hyps_per_frame, thr, max_attempts, discard0_per_image, d_poses, d_sets, d_ok, nullptr, d_consumed,
+                                 d_attempts));
+    return end_call(c);
+}
+
 int dsac_reproject(dsac_ctx* c, int N, const double* poses, float clampv, float* err_or_null, float tau, float beta, double* soft_or_null) {
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_reproject: ctx is NULL");
     if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "dsac_reproject: no frame set");
@@ -1016,6 +1084,15 @@ int dsac_set_option(dsac_ctx* c, const char* key, int value) {
     else if (k == "refstream_mode") {
         if (value < -1 || value > 1) return fail(c, DSAC_ERR_INVALID, "dsac_set_option: refstream_mode is 0 (libstdc++ >= 11), 1 (libstdc++ <= 10) or -1 (this build's)");
         c->rs_mode = value < 0 ? DSAC_RS_DEFAULT_MODE : value;
+    }
+    else if (k == "pi_refstream") c->pi_refstream = value != 0;
+    else if (k == "pi_refstream_discard0") {
+        if (value < 0 || (unsigned long long)value > RS_MAX_DISCARD0) return fail(c, DSAC_ERR_INVALID, "dsac_set_option: pi_refstream_discard0 is 0 .. 2^24 outputs");
+        c->pi_refstream_discard0 = value;
+    }
+    else if (k == "pi_refstream_attempts") {
+        if (value < 0) return fail(c, DSAC_ERR_INVALID, "dsac_set_option: pi_refstream_attempts is > 0, or 0 for the default budget");
+        c->pi_refstream_attempts = value;
     }
     else if (k == "k1_wpb") c->k1.wpb = value;
     else if (k == "k1_prio") c->k1.prio = value;
@@ -1746,6 +1823,18 @@ int dsac_soft_score_derr(dsac_ctx* c, int N, const double* g, const float* err, 
 }
 
 // ---- shared by dsac_process_images and the begin / finish pair -------------------------------------------------------------------------------
+// K1 of the batched calls in the reference's own random stream ("pi_refstream"): the chain of dsac_sample_refstream_frames, with the K2 records staged
+static long long pi_refstream_budget(const dsac_ctx* c, int hyps_per_frame) {
+    return c->pi_refstream_attempts > 0 ? c->pi_refstream_attempts : rs::default_budget((hyps_per_frame + std::max(1, c->rs_threads) - 1) / std::max(1, c->rs_threads));
+}
+static int pi_refstream_check(dsac_ctx* c, const char* who, int hyps_per_frame) {
+    int windows[rs::MAX_WINDOWS], K = 0;
+    return refstream_plan(c, who, hyps_per_frame, pi_refstream_budget(c, hyps_per_frame), (unsigned long long)c->pi_refstream_discard0, windows, &K);
+}
+static int pi_refstream_k1(dsac_ctx* c, const char* who, int hyps_per_frame, float thr, double* d_poses, int32_t* d_sets, uint8_t* d_ok) {
+    return refstream_chain_call(c, who, hyps_per_frame, thr, pi_refstream_budget(c, hyps_per_frame), (unsigned long long)c->pi_refstream_discard0, d_poses, d_sets, d_ok,
+                                c->staged.as<float>(), nullptr, nullptr);
+}
 // Which deferral mode a call runs in: the context's "pi_defer_tail", but only with device-resident arguments -- a host destination is copied back at
 // the end of the call, and a host `perm` / `gt` lives in a staging slot that the next call reuses.
 static int pi_mode(dsac_ctx* c, const void* perm, const void* gt_or_null) {
@@ -1808,6 +1897,7 @@ int dsac_process_images(dsac_ctx* c, int hyps_per_frame, uint64_t seed, float th
     if ((out4_or_null != nullptr) != (gt_jp6_or_null != nullptr)) return fail(c, DSAC_ERR_INVALID, "dsac_process_images: out4 and gt_jp6 go together");
     if (max_inl < 1 || max_inl > 256 || min_inl < 0) return fail(c, DSAC_ERR_INVALID, "dsac_process_images: need 1 <= max_inl <= 256 (got %d), min_inl >= 0", max_inl);
     if (max_tries <= 0 || c->F.P < 4) return fail(c, DSAC_ERR_INVALID, "dsac_process_images: max_tries > 0 and a frame of at least 4 cells needed");
+    if (c->pi_refstream) ARG_TRY(pi_refstream_check(c, "dsac_process_images (pi_refstream)", hyps_per_frame));  // before anything is enqueued
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c, /*keep_tail=*/c->pi_defer_tail != 0);
     const size_t P = (size_t)c->F.P;
@@ -1864,7 +1954,8 @@ int dsac_process_images(dsac_ctx* c, int hyps_per_frame, uint64_t seed, float th
     // processImage (core/cnn_softam.h:960-1179) for every frame of the batch, one launch per stage:
     //   K1 sample + P3P (:1010-1060)  ->  K2 error images + soft-inlier sums (:1067-1072)  ->  scores  ->  K3 softmax / entropy / soft-argmax
     //   (:1078-1094)  ->  K6 the refinement loop, one wave per frame (:1099-1154)  ->  K7 maxLoss against each frame's ground truth (:1160-1179)
-    HIP_TRY(c, dk::sample(c->stream, N, seed, nullptr, c->F, (int)thr, max_tries, d_poses, d_sets, d_ok, c->staged.as<float>(), Nf, c->k1));
+    if (c->pi_refstream) ARG_TRY(pi_refstream_k1(c, "dsac_process_images", hyps_per_frame, thr, d_poses, d_sets, d_ok));
+    else HIP_TRY(c, dk::sample(c->stream, N, seed, nullptr, c->F, (int)thr, max_tries, d_poses, d_sets, d_ok, c->staged.as<float>(), Nf, c->k1));
     int used = 0;
     if (c->k2_wait) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->k2_wait, 0));
     // mode 2: the tail starts behind K2.  The event it waits for rides on K2's own dispatch packet (hipExtLaunchKernelGGL's stop event) -- an event
@@ -1926,6 +2017,7 @@ int dsac_process_images_begin(dsac_ctx* c, int hyps_per_frame, uint64_t seed, fl
     if (!poses || !sets_out || !ok || (!err && !soft_or_null))
         return fail(c, DSAC_ERR_INVALID, "dsac_process_images_begin: poses / sets_out / ok and at least one of err / soft must be non-NULL");
     if (max_tries <= 0 || c->F.P < 4) return fail(c, DSAC_ERR_INVALID, "dsac_process_images_begin: max_tries > 0 and a frame of at least 4 cells needed");
+    if (c->pi_refstream) ARG_TRY(pi_refstream_check(c, "dsac_process_images_begin (pi_refstream)", hyps_per_frame));  // before anything is enqueued
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c, /*keep_tail=*/c->pi_defer_tail != 0);
     const size_t P = (size_t)c->F.P;
@@ -1954,7 +2046,8 @@ int dsac_process_images_begin(dsac_ctx* c, int hyps_per_frame, uint64_t seed, fl
         d_part = c->soft_part.as<float>();
     }
     if (fused_for_err && !(beta > 0.f)) { tau = 10.f; beta = 0.5f; }
-    HIP_TRY(c, dk::sample(c->stream, N, seed, nullptr, c->F, (int)thr, max_tries, d_poses, d_sets, d_ok, c->staged.as<float>(), Nf, c->k1));
+    if (c->pi_refstream) ARG_TRY(pi_refstream_k1(c, "dsac_process_images_begin", hyps_per_frame, thr, d_poses, d_sets, d_ok));
+    else HIP_TRY(c, dk::sample(c->stream, N, seed, nullptr, c->F, (int)thr, max_tries, d_poses, d_sets, d_ok, c->staged.as<float>(), Nf, c->k1));
     int used = 0;
     if (c->k2_wait) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->k2_wait, 0));
     {

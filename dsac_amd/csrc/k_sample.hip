@@ -544,6 +544,7 @@ hipError_t sample(hipStream_t st, int N, uint64_t seed, const int32_t* sets_in, 
 // the generator advances to the output behind the last attempt used.  A window that does not serve every hypothesis is followed by another (host loop).
 // --------------------------------------------------------------------------------------------------
 constexpr int RS_THREADS = 256;
+constexpr int RS_STAGE = 8 * RS_THREADS + 128;  // outputs of the stream a parsing round of the step kernel keeps in LDS
 
 __global__ __launch_bounds__(64) void k_refstream_init(RefStreamState* st, uint32_t seed, int T) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -639,11 +640,12 @@ __global__ __launch_bounds__(RS_THREADS) void k_refstream_parse(const RefStreamS
 }
 
 // (2) one lane per attempt
-__global__ __launch_bounds__(64) void k_refstream_eval(int A, const int32_t* __restrict__ parsed, const int32_t* __restrict__ sets_all, FrameDev F, int thr_int,
+// (stride: attempts per stream the scratch is laid out for -- the window's own size, or the largest window of an enqueue-only chain)
+__global__ __launch_bounds__(64) void k_refstream_eval(int stride, const int32_t* __restrict__ parsed, const int32_t* __restrict__ sets_all, FrameDev F, int thr_int,
                                                        double* __restrict__ poses_tmp, uint8_t* __restrict__ ok_tmp) {
     const int t = blockIdx.y, a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= parsed[t]) return;
-    const size_t i = (size_t)t * A + a;
+    const size_t i = (size_t)t * stride + a;
     int32_t set4[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) set4[k] = sets_all[i * 4 + k];
@@ -723,6 +725,201 @@ __global__ __launch_bounds__(64) void k_refstream_unserved(int T, const int32_t*
     }
 }
 
+// --------------------------------------------------------------------------------------------------
+// The same loop as a chain the host enqueues blind (dsac_sample_refstream_frames): per image and window one step launch and one evaluation launch,
+// sizes fixed beforehand (rs::window_ladder), nothing read back.  The step kernel, one workgroup per stream, fuses what is sequential per stream:
+//   (a) select: the accepted attempts of the window just evaluated go to the stream's next hypotheses of image `sel` (as k_refstream_select), the
+//       generator is put behind the last attempt used -- from the window's own outputs, untempered, where they hold that block (rs::mt_untemper);
+//   (b) at the end of an image (close): hypotheses still open report ok = 0 and a zero pose, the image's counters go to cons_out / att_out;
+//   (c) at the start of an image (open): need = the stream's static chunk, counters = 0, generator 0 skips discard0 outputs (stochasticSubSample drew
+//       them before the sampling loop, core/cnn_softam.h:283-309);
+//   (d) generate + parse the next window (A_gen attempts) from the generator still in LDS, if the stream has hypotheses open: k_refstream_parse's
+//       speculation with the whole workgroup, RS_THREADS attempts per round from a stretch of the stream staged in LDS (13 KB of LDS per workgroup).
+// The generator makes one round trip through global memory per step.  Every workgroup owns its stream's slice of the scratch (laid out for the largest
+// window of the chain, `stride`), waits on no other workgroup, and finds need[t] == 0 in the windows behind the one that served it: those return at once.
+// --------------------------------------------------------------------------------------------------
+struct RefStepOut {  // rows of the image being selected into
+    double* poses;
+    int32_t* sets;
+    uint8_t* ok;
+    float* staged;
+    unsigned long long* cons;  // [T] or nullptr
+    long long* att;            // [T] or nullptr
+};
+
+__global__ __launch_bounds__(RS_THREADS) void k_refstream_step(RefStreamState* __restrict__ st, int T, int N, int W, int H, int mode, int stride, int A_sel, int A_gen,
+                                                               int close_image, int open_image, unsigned long long discard0, uint32_t* __restrict__ raw_all,
+                                                               int32_t* __restrict__ sets_all, uint32_t* __restrict__ offs_all, const double* __restrict__ poses_tmp,
+                                                               const uint8_t* __restrict__ ok_tmp, int32_t* __restrict__ served_g, int32_t* __restrict__ need_g,
+                                                               int32_t* __restrict__ parsed_g, unsigned long long* __restrict__ consumed_g,
+                                                               long long* __restrict__ attempts_g, FrameDev F, RefStepOut out) {
+    const int t = blockIdx.x, tid = threadIdx.x;
+    __shared__ int s_cnt[RS_THREADS];
+    __shared__ int s_last;
+    __shared__ uint32_t mt[rs::MT_N];
+    const int D = refstream_window_outputs(stride);
+    const size_t base = (size_t)t * stride;
+    int32_t* sets = sets_all + base * 4;
+    uint32_t* offs = offs_all + (size_t)t * (stride + 1);
+    int first, chunk;
+    rs::static_chunk(N, T, t, first, chunk);  // #pragma omp parallel for, static schedule (core/cnn_softam.h:1010)
+    // the stream's counters of the image in progress: every lane holds them (uniform), lane 0 writes them back
+    int want = 0, served = 0;
+    unsigned long long consumed = 0;
+    long long attempts = 0;
+    if (A_sel > 0) { want = need_g[t]; served = served_g[t]; consumed = consumed_g[t]; attempts = attempts_g[t]; }
+    const int n = A_sel > 0 ? parsed_g[t] : 0;
+    bool have_mt = false;
+    uint32_t idx = 0;
+    auto load_mt = [&]() {
+        if (have_mt) return;
+        for (int i = tid; i < rs::MT_N; i += RS_THREADS) mt[i] = st[t].mt[i];
+        idx = st[t].idx;
+        have_mt = true;
+        __syncthreads();
+    };
+    // (a)
+    if (want > 0 && n > 0) {
+        const int per = (n + RS_THREADS - 1) / RS_THREADS, a0 = tid * per, a1 = min(n, a0 + per);
+        int cnt = 0;
+        for (int a = a0; a < a1; a++) cnt += ok_tmp[base + a];
+        s_cnt[tid] = cnt;
+        if (tid == 0) s_last = -1;
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int i = 0; i < RS_THREADS; i++) { const int v = s_cnt[i]; if (i < tid) before += v; total += v; }
+        const int row0 = first + served;
+        int r = before;
+        for (int a = a0; a < a1 && r < want; a++) {
+            if (!ok_tmp[base + a]) continue;
+            const int h = row0 + r;
+            double cv6[6];
+#pragma unroll
+            for (int k = 0; k < 6; k++) { cv6[k] = poses_tmp[(base + a) * 6 + k]; out.poses[(size_t)h * 6 + k] = cv6[k]; }
+#pragma unroll
+            for (int k = 0; k < 4; k++) out.sets[(size_t)h * 4 + k] = sets[(size_t)a * 4 + k];
+            out.ok[h] = 1;
+            if (out.staged) write_staged(F, cv6, out.staged + (size_t)h * POSE_STRIDE);
+            if (r == want - 1) s_last = a;
+            r++;
+        }
+        __syncthreads();
+        const int got = min(total, want);
+        const int used = rs::window_used(total, want, s_last, n);
+        const unsigned long long took = offs[used];
+        // the generator behind the last attempt used.  The window's outputs are still in `raw` (output o = position idx + o of the stream as the previous
+        // step stored it): where the block that holds the new position lies inside them, its 624 state words are the untempered outputs -- no twisting up
+        // to it; otherwise (the position is still in the stored block, or past the blocks the window generated whole) the generator is advanced as ever
+        const uint32_t idx_old = st[t].idx;
+        const unsigned long long pos = (unsigned long long)idx_old + took;
+        const unsigned long long blk = pos > (unsigned long long)rs::MT_N ? (pos - 1) / rs::MT_N : 0;
+        const long long o0 = (long long)(blk * rs::MT_N) - (long long)idx_old;
+        if (blk > 0 && o0 + rs::MT_N <= (long long)refstream_window_outputs(A_sel)) {
+            const uint32_t* raw_sel = raw_all + (size_t)t * D;
+            for (int i = tid; i < rs::MT_N; i += RS_THREADS) mt[i] = rs::mt_untemper(raw_sel[o0 + i]);
+            idx = (uint32_t)(pos - blk * rs::MT_N);
+            have_mt = true;
+            __syncthreads();
+        } else {
+            load_mt();
+            rs_advance_lds(mt, idx, took, tid);
+        }
+        served += got;
+        want -= got;
+        consumed += took;
+        attempts += used;
+    }
+    // (b)
+    if (close_image) {
+        for (int j = tid; j < want; j += RS_THREADS) {
+            const int h = first + served + j;
+#pragma unroll
+            for (int k = 0; k < 6; k++) out.poses[(size_t)h * 6 + k] = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) out.sets[(size_t)h * 4 + k] = 0;
+            out.ok[h] = 0;
+            if (out.staged) { const double z6[6] = {0, 0, 0, 0, 0, 0}; write_staged(F, z6, out.staged + (size_t)h * POSE_STRIDE); }
+        }
+        if (tid == 0) {
+            if (out.cons) out.cons[t] = consumed;
+            if (out.att) out.att[t] = attempts;
+        }
+    }
+    // (c)
+    if (open_image) {
+        want = chunk; served = 0; consumed = 0; attempts = 0;
+        if (t == 0 && discard0 > 0) {
+            load_mt();
+            rs_advance_lds(mt, idx, discard0, tid);
+        }
+    }
+    const bool gen = A_gen > 0 && want > 0;
+    if (gen) load_mt();
+    if (have_mt) {  // the generator where the next window starts (whoever reads it next: a later step, dsac_sample_refstream, dsac_refstream_discard)
+        __syncthreads();
+        for (int i = tid; i < rs::MT_N; i += RS_THREADS) st[t].mt[i] = mt[i];
+        if (tid == 0) st[t].idx = idx;
+    }
+    if (tid == 0) {
+        served_g[t] = served; need_g[t] = want; consumed_g[t] = consumed; attempts_g[t] = attempts;
+        if (!gen) parsed_g[t] = 0;
+    }
+    if (!gen) return;
+    // (d): raw[0 .. Dg) from the copy in LDS, then the attempts, a wave at a time (see k_refstream_parse)
+    const int Dg = refstream_window_outputs(A_gen);  // <= D: A_gen <= stride
+    uint32_t* raw = raw_all + (size_t)t * D;
+    const int idx0 = (int)idx;
+    __syncthreads();
+    int o = 0;
+    for (int i = idx0 + tid; i < rs::MT_N && o + (i - idx0) < Dg; i += RS_THREADS) raw[o + (i - idx0)] = rs::mt_temper(mt[i]);
+    o += rs::MT_N - idx0;
+    while (o < Dg) {
+        rs_twist_lds(mt, tid);
+        for (int i = tid; i < rs::MT_N && o + i < Dg; i += RS_THREADS) raw[o + i] = rs::mt_temper(mt[i]);
+        o += rs::MT_N;
+    }
+    __threadfence_block();
+    __syncthreads();
+    // the whole workgroup speculates: attempt cur-th ... at 8 outputs each, RS_THREADS at a time, from a copy of that stretch of the stream in LDS (an attempt
+    // that needs more than the stretch holds reads on in global memory).  The valid prefix ends at the first attempt that took more than 8 (a duplicate
+    // cell, a rejected draw); the next round starts behind it.  The same attempts as k_refstream_parse's one wave finds, four times as many per round.
+    __shared__ uint32_t s_raw[RS_STAGE];
+    __shared__ int s_len[RS_THREADS];
+    long long cur = 0;
+    int a = 0;
+    while (a < A_gen) {
+        for (int i = tid; i < RS_STAGE && cur + i < (long long)Dg; i += RS_THREADS) s_raw[i] = raw[cur + i];
+        __syncthreads();
+        const long long start = cur + 8 * tid;
+        int32_t set4[4];
+        const int len = rs::parse_attempt([&](long long i) { return i - cur < (long long)RS_STAGE ? s_raw[i - cur] : raw[i]; }, start, (long long)Dg, (uint32_t)W,
+                                          (uint32_t)H, mode, set4);
+        s_len[tid] = len;
+        __syncthreads();
+        int k0 = RS_THREADS;
+        for (int w = 0; w < RS_THREADS / 64; w++) {
+            const int l = s_len[w * 64 + (tid & 63)];
+            const unsigned long long odd_w = __ballot(l != 8);
+            if (odd_w && k0 == RS_THREADS) k0 = w * 64 + __ffsll((long long)odd_w) - 1;
+        }
+        const bool odd = k0 < RS_THREADS;
+        const int len_k0 = odd ? s_len[k0] : 8;
+        int nv = odd ? (len_k0 > 0 ? k0 + 1 : k0) : RS_THREADS;  // a starved / degenerate attempt is not an attempt
+        nv = min(nv, A_gen - a);
+        if (tid < nv) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) sets[(size_t)(a + tid) * 4 + k] = set4[k];
+            offs[a + tid] = (uint32_t)start;
+        }
+        if (nv == 0) break;
+        cur = cur + 8 * (nv - 1) + s_len[nv - 1];
+        a += nv;
+        if (odd && len_k0 <= 0) break;
+        __syncthreads();  // s_raw / s_len are rewritten by the next round
+    }
+    if (tid == 0) { offs[a] = (uint32_t)cur; parsed_g[t] = a; }
+}
+
 hipError_t refstream_init(hipStream_t st, RefStreamState* states, uint32_t seed, int T) {
     hipLaunchKernelGGL(k_refstream_init, dim3((T + 63) / 64), dim3(64), 0, st, states, seed, T);
     return hipGetLastError();
@@ -749,6 +946,58 @@ hipError_t refstream_window(hipStream_t st, RefStreamState* states, int T, int A
     hipLaunchKernelGGL(k_refstream_eval, dim3((A + 63) / 64, T), dim3(64), 0, st, A, parsed, sets, F, thr_int, poses_tmp, ok_tmp);
     hipLaunchKernelGGL(k_refstream_select, dim3(T), dim3(RS_THREADS), 0, st, states, A, parsed, sets, offs, poses_tmp, ok_tmp, first, served, need, consumed, attempts, F, poses,
                        sets_out, ok, staged);
+    return hipGetLastError();
+}
+// The chain for `frames` images of F (frame f at xyz + f * xyz_stride), N hypotheses each, rows [f N, (f + 1) N) of the outputs.  small: 3 T int32
+// (served | need | parsed) + T uint64 + T int64; scratch: refstream_window_bytes(T, largest window).  Launches only; nothing is read back.
+hipError_t refstream_chain(hipStream_t st, RefStreamState* states, int T, int N, int frames, const int* windows, int n_windows, int mode, void* scratch, void* small,
+                           const FrameDev& F, int thr_int, unsigned long long discard0, double* poses, int32_t* sets_out, uint8_t* ok, float* staged,
+                           unsigned long long* consumed_or_null, long long* attempts_or_null) {
+    if (frames <= 0 || N <= 0 || n_windows <= 0) return hipSuccess;
+    int stride = 0;
+    for (int k = 0; k < n_windows; k++) stride = windows[k] > stride ? windows[k] : stride;
+    const int D = refstream_window_outputs(stride);
+    char* p = reinterpret_cast<char*>(scratch);
+    double* poses_tmp = reinterpret_cast<double*>(p); p += (size_t)T * stride * 48;
+    uint32_t* raw = reinterpret_cast<uint32_t*>(p); p += (size_t)T * D * 4;
+    int32_t* sets = reinterpret_cast<int32_t*>(p); p += (size_t)T * stride * 16;
+    uint32_t* offs = reinterpret_cast<uint32_t*>(p); p += (size_t)T * (stride + 1) * 4;
+    uint8_t* ok_tmp = reinterpret_cast<uint8_t*>(p);
+    int32_t *served = reinterpret_cast<int32_t*>(small), *need = served + T, *parsed = served + 2 * T;
+    unsigned long long* consumed = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(small) + (size_t)T * 16);
+    long long* attempts = reinterpret_cast<long long*>(reinterpret_cast<char*>(small) + (size_t)T * 24);
+    auto frame = [&](int f) {
+        FrameDev G = F;
+        G.xyz = F.xyz + (long long)f * F.xyz_stride;
+        G.uv = F.uv ? F.uv + (long long)f * F.uv_stride : nullptr;
+        G.frames = 1;
+        return G;
+    };
+    auto rows = [&](int f) {
+        RefStepOut o;
+        o.poses = poses + (size_t)f * N * 6;
+        o.sets = sets_out + (size_t)f * N * 4;
+        o.ok = ok + (size_t)f * N;
+        o.staged = staged ? staged + (size_t)f * N * POSE_STRIDE : nullptr;
+        o.cons = consumed_or_null ? consumed_or_null + (size_t)f * T : nullptr;
+        o.att = attempts_or_null ? attempts_or_null + (size_t)f * T : nullptr;
+        return o;
+    };
+    // step (f, k): selects window k - 1 of image f (k == 0: closes image f - 1 with its last window) and generates window k of image f
+    for (int f = 0; f <= frames; f++) {
+        for (int k = 0; k < (f < frames ? n_windows : 1); k++) {
+            const bool open = k == 0 && f < frames, close = k == 0 && f > 0;
+            const int fs = k == 0 ? f - 1 : f;  // the image the step selects into
+            const int A_sel = k > 0 ? windows[k - 1] : (f > 0 ? windows[n_windows - 1] : 0);
+            const int A_gen = f < frames ? windows[k] : 0;
+            hipLaunchKernelGGL(k_refstream_step, dim3(T), dim3(RS_THREADS), 0, st, states, T, N, F.W, F.H, mode, stride, A_sel, A_gen, close ? 1 : 0, open ? 1 : 0, discard0, raw,
+                               sets, offs, poses_tmp, ok_tmp, served, need, parsed, consumed, attempts, frame(fs < 0 ? 0 : fs), rows(fs < 0 ? 0 : fs));
+            if (A_gen > 0) {
+                const FrameDev G = frame(f);
+                hipLaunchKernelGGL(k_refstream_eval, dim3((A_gen + 63) / 64, T), dim3(64), 0, st, stride, parsed, sets, G, thr_int, poses_tmp, ok_tmp);
+            }
+        }
+    }
     return hipGetLastError();
 }
 hipError_t refstream_unserved(hipStream_t st, int T, const int32_t* first, const int32_t* served, const int32_t* need, const FrameDev& F, double* poses, int32_t* sets_out,

@@ -90,7 +90,7 @@ hipError_t sample(hipStream_t st, int N, uint64_t seed, const int32_t* sets_in, 
 // K1 in the reference's own random stream (round 6; core/thread_rand.cpp:40-69, core/cnn_softam.h:1010-1060; refstream.h): T generators std::mt19937(seed + t)
 // on the device; a window = A attempts per stream parsed, evaluated and handed to the stream's next hypotheses in order.
 struct RefStreamState { uint32_t mt[624]; uint32_t idx; uint32_t pad[3]; };
-inline int refstream_window_outputs(int A) { return 9 * A + 128; }  // raw outputs generated per window (an attempt takes 8, rarely more)
+constexpr int refstream_window_outputs(int A) { return 9 * A + 128; }  // raw outputs generated per window (an attempt takes 8, rarely more)
 size_t refstream_window_bytes(int T, int A);
 hipError_t refstream_init(hipStream_t st, RefStreamState* states, uint32_t seed, int T);
 hipError_t refstream_discard(hipStream_t st, RefStreamState* states, int t, unsigned long long n);
@@ -98,6 +98,11 @@ hipError_t refstream_discard(hipStream_t st, RefStreamState* states, int t, unsi
 hipError_t refstream_window(hipStream_t st, RefStreamState* states, int T, int A, int mode, void* scratch, const FrameDev& F, int thr_int, const int32_t* first,
                             int32_t* served, int32_t* need, int32_t* parsed, unsigned long long* consumed, long long* attempts, double* poses, int32_t* sets_out,
                             uint8_t* ok, float* staged);
+// the same loop as an enqueue-only chain over the images of a frame batch, window sizes fixed beforehand (rs::window_ladder); scratch holds
+// refstream_window_bytes(T, largest window), small 3 T int32 + T uint64 + T int64
+hipError_t refstream_chain(hipStream_t st, RefStreamState* states, int T, int N, int frames, const int* windows, int n_windows, int mode, void* scratch, void* small,
+                           const FrameDev& F, int thr_int, unsigned long long discard0, double* poses, int32_t* sets_out, uint8_t* ok, float* staged,
+                           unsigned long long* consumed_or_null, long long* attempts_or_null);
 hipError_t refstream_unserved(hipStream_t st, int T, const int32_t* first, const int32_t* served, const int32_t* need, const FrameDev& F, double* poses, int32_t* sets_out,
                               uint8_t* ok, float* staged);
 // Nf (frame batch): hypotheses per frame, hypothesis h reads frame h / Nf

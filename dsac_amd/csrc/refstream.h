@@ -4,7 +4,7 @@
 // seed + t, and irand(lo, hi) = std::uniform_int_distribution<int>(lo, hi - 1) on it (:59-69, :95-98).  The sampling loop (core/cnn_softam.h:1010-1060)
 // draws x = irand(0, cols) BEFORE y = irand(0, rows), re-draws a cell that is already in the set, and starts a new attempt after a failed P3P or
 // re-projection check.  Everything in this header is a pure function of the 32-bit output stream of the generator, so it runs the same on the host
-// and in a kernel; the kernels are in k_refstream.hip.
+// and in a kernel; the kernels are in k_sample.hip.
 //
 //   mt_seed / mt_twist_word / mt_temper : MT19937 (Matsumoto & Nishimura 1998) as std::mt19937 parameterises it (w 32, n 624, m 397, r 31, a 0x9908b0df,
 //                                         u 11, s 7, b 0x9d2c5680, t 15, c 0xefc60000, l 18, f 1812433253)
@@ -34,6 +34,18 @@ RS_FN uint32_t mt_temper(uint32_t y) {
     y ^= (y << 7) & 0x9d2c5680u;
     y ^= (y << 15) & 0xefc60000u;
     y ^= y >> 18;
+    return y;
+}
+// the state word behind an output: tempering is a bijection of 32-bit words.  624 consecutive outputs of one block are that block's state, so a generator
+// whose outputs are at hand is put at a position without twisting up to it (the step kernel of the enqueue-only chain)
+RS_FN uint32_t mt_untemper(uint32_t y) {
+    y ^= y >> 18;
+    y ^= (y << 15) & 0xefc60000u;
+    uint32_t z = y;  // y = z ^ ((z << 7) & b): seven more bits of z are known after every pass
+    for (int i = 0; i < 4; i++) z = y ^ ((z << 7) & 0x9d2c5680u);
+    y = z;
+    y ^= y >> 11;
+    y ^= y >> 22;
     return y;
 }
 // x[k + n] from x[k], x[k + 1], x[k + m]
@@ -107,5 +119,37 @@ RS_FN void static_chunk(int N, int T, int t, int& first, int& count) {
     first = t * q + (t < r ? t : r);
     count = q + (t < r ? 1 : 0);
 }
+
+// ---- the window ladder of the enqueue-only chain (dsac_sample_refstream_frames; host side, no device code) ------------------------------------------
+// The chain is enqueued without reading anything back, so the sizes of its windows are fixed before the first launch: a pure function of the
+// hypotheses wanted per stream (the largest static_chunk) and the attempt budget per stream and image.  The first window holds WINDOW_PER_HYP attempts
+// per wanted hypothesis, rounded up to a power of two in [WINDOW_MIN, WINDOW_MAX]; every further one doubles up to WINDOW_MAX; the last is trimmed so
+// that the sizes sum to the budget exactly.  A window behind the one that served a stream's last hypothesis finds need[t] == 0 on the device and returns.
+constexpr int WINDOW_MIN = 256, WINDOW_MAX = 16384, WINDOW_PER_HYP = 16;
+constexpr int MAX_WINDOWS = 64;  // a budget whose ladder is longer is refused by the API (DSAC_ERR_INVALID), never truncated
+
+inline int window_first(int want) {
+    int A = WINDOW_MIN;
+    while (A < WINDOW_MAX && (long long)A < (long long)WINDOW_PER_HYP * want) A *= 2;
+    return A;
+}
+// Fills sizes[0 .. min(count, cap)) and returns count, the number of windows the budget needs (which may exceed cap and MAX_WINDOWS: the caller decides).
+inline int window_ladder(int want, long long budget, int* sizes, int cap) {
+    int count = 0, A = window_first(want);
+    for (long long left = budget; left > 0; count++) {
+        const int a = (long long)A <= left ? A : (int)left;
+        if (count < cap) sizes[count] = a;
+        left -= a;
+        if (A < WINDOW_MAX) A *= 2;
+    }
+    return count;
+}
+// The budget the callers use when they are given none: 256 attempts per wanted hypothesis, at least 4096.  (The reference's loop has no cap; on its
+// golden frames the worst stream makes up to 148 attempts per hypothesis, on 640 x 480 synthetic frames 15-18.)
+inline long long default_budget(int want) { return want * 256ll > 4096ll ? want * 256ll : 4096ll; }
+
+// What a window charges a stream: with `accepted` good attempts among its `parsed` ones and `want` hypotheses still open, the stream stops behind the
+// attempt that served its last hypothesis (index last_needed), or spends the whole window.  Attempts charged = attempts used, whatever the window held.
+RS_FN int window_used(int accepted, int want, int last_needed, int parsed) { return accepted >= want ? last_needed + 1 : parsed; }
 
 }  // namespace rs

@@ -144,10 +144,11 @@ class Engine:
         return out
 
     def processImages(self, hyps_per_frame, perm, gt_jp6=None, seed=1305, thr=10.0, max_tries=1 << 20, clamp=CNN_OBJ_MAXINPUT, tau=10.0, beta=0.5,
-                      scale=0.1, max_inl=100, min_inl=50, err=None, want_inlier_maps=False, out=None):
+                      scale=0.1, max_inl=100, min_inl=50, err=None, want_inlier_maps=False, out=None, refstream=None):
         """processImage (cnn_softam.h:960-1179) for every frame set with set_frame / set_frames in one call (dsac_process_images): K1, K2, K3, the
         refinement loop (one wave per frame) and the loss against each frame's ground truth, one launch per stage.  perm: refSteps x H*W pixel
-        permutations (shared by the frames); gt_jp6: F x 6 or None.  Frame f uses the random stream of seed + f.
+        permutations (shared by the frames); gt_jp6: F x 6 or None.  Frame f uses the random stream of seed + f.  refstream (True or
+        dict(discard0=, attempts=); after refstreamInit): the sets come from the reference's own generators instead ("pi_refstream"), seed is unused.
         out = dict of preallocated buffers (numpy or torch) with the keys of the returned dict; returns dict(hyps, sampledPoints, ok, scores,
         sfScores, sfEntropy F, avgHyp F x 6, refAvgHyp F x 6, refSteps F[, inlierMaps F x P][, out4 F x 4 = loss, rotErr, tErr, correct])."""
         F, N = getattr(self, "frames", 1), int(hyps_per_frame)
@@ -164,6 +165,7 @@ class Engine:
         maps = buf("inlierMaps", (F, self.P), np.int32) if (want_inlier_maps or o.get("inlierMaps") is not None) else None
         gt = _np(np.asarray(gt_jp6, dtype=np.float64).reshape(F, 6), np.float64) if isinstance(gt_jp6, (np.ndarray, list, tuple)) else gt_jp6
         out4 = buf("out4", (F, 4)) if gt is not None else None
+        self._pi_refstream(refstream)
         check(self._ctx, lib.dsac_process_images(self._ctx, N, int(seed) & 0xFFFFFFFFFFFFFFFF, float(thr), int(max_tries), float(clamp), float(tau), float(beta),
                                                  float(scale), ptr(perm), steps, int(max_inl), int(min_inl), ptr(gt), ptr(hyps), ptr(sets), ptr(ok), ptr(err),
                                                  ptr(scores), ptr(w), ptr(ent), ptr(avg), ptr(ref), ptr(sd), ptr(maps), ptr(out4)))
@@ -192,14 +194,16 @@ class Engine:
         return call
 
     # ---- the score-CNN seam of the batched fast path (dsac_process_images_begin / _finish) ---------------------------------------------
-    def processImagesBegin(self, hyps_per_frame, err, seed=1305, thr=10.0, max_tries=1 << 20, clamp=CNN_OBJ_MAXINPUT, tau=10.0, beta=0.5, soft=None, out=None):
+    def processImagesBegin(self, hyps_per_frame, err, seed=1305, thr=10.0, max_tries=1 << 20, clamp=CNN_OBJ_MAXINPUT, tau=10.0, beta=0.5, soft=None, out=None,
+                           refstream=None):
         """First half of processImage for every frame set with set_frame / set_frames (cnn_softam.h:1010-1069): K1 sample + P3P, K2 -> the F*N error
         images in `err` (F*N x H*W float32, where the reference's score CNN reads them: lua_calls.h:98-104); soft (F*N float64, optional) receives the
-        soft-inlier sums as well.  out = (poses F*N x 6, sets F*N x 4, ok F*N) preallocated or None; returns it."""
+        soft-inlier sums as well.  out = (poses F*N x 6, sets F*N x 4, ok F*N) preallocated or None; returns it.  refstream: as processImages."""
         F, N = getattr(self, "frames", 1), int(hyps_per_frame)
         if out is None:
             out = (np.zeros((F * N, 6)), np.zeros((F * N, 4), np.int32), np.zeros(F * N, np.uint8))
         poses, sets_out, ok = out
+        self._pi_refstream(refstream)
         check(self._ctx, lib.dsac_process_images_begin(self._ctx, N, int(seed) & 0xFFFFFFFFFFFFFFFF, float(thr), int(max_tries), float(clamp), float(tau), float(beta),
                                                        ptr(poses), ptr(sets_out), ptr(ok), ptr(err), ptr(soft)))
         return out
@@ -236,12 +240,12 @@ class Engine:
         return w, ent, avg
 
     def processImagesScored(self, hyps_per_frame, perm, score_fn, gt_jp6=None, seed=1305, thr=10.0, max_tries=1 << 20, clamp=CNN_OBJ_MAXINPUT, max_inl=100,
-                            min_inl=50, scale=1.0, err=None, want_inlier_maps=False, out=None):
+                            min_inl=50, scale=1.0, err=None, want_inlier_maps=False, out=None, refstream=None):
         """processImage of every frame with the reference's own kind of score: score_fn(err) -> F*N scores, err the F*N x H x W float32 error images
         as a torch DEVICE tensor that K2 has just written (nothing crosses PCIe: the reference pushes the same maps to Lua number by number,
         lua_calls.h:89-105).  score_fn runs on the engine's stream when the engine was made on torch's current stream (Engine(stream=...)); its result
         may be any floating torch tensor on the device.  perm / gt_jp6: device tensors or host arrays (host arrays are uploaded).  Returns the dict of
-        processImages with torch device tensors (plus "diffMaps")."""
+        processImages with torch device tensors (plus "diffMaps").  refstream: as processImages."""
         import torch
         F, N = getattr(self, "frames", 1), int(hyps_per_frame)
         dev = torch.device("cuda", self.device)
@@ -266,7 +270,7 @@ class Engine:
                 buf("inlierMaps", (F, self.P), torch.int32)
             if gt_d is not None:
                 buf("out4", (F, 4))
-            self.processImagesBegin(N, err, seed=seed, thr=thr, max_tries=max_tries, clamp=clamp, out=(hyps, sets, ok))
+            self.processImagesBegin(N, err, seed=seed, thr=thr, max_tries=max_tries, clamp=clamp, out=(hyps, sets, ok), refstream=refstream)
             scores = score_fn(err.view(F * N, self.H, self.W))
             if not hasattr(scores, "data_ptr"):
                 scores = torch.as_tensor(np.ascontiguousarray(scores, dtype=np.float64))
@@ -329,6 +333,32 @@ class Engine:
         consumed, attempts = np.zeros(max(T, 1), np.uint64), np.zeros(max(T, 1), np.int64)
         check(self._ctx, lib.dsac_sample_refstream(self._ctx, int(N), float(thr), int(max_attempts), ptr(poses), ptr(sets_out), ptr(ok), ptr(consumed), ptr(attempts)))
         return poses, sets_out, ok, consumed, attempts
+
+    def sampleRefstreamFrames(self, hyps_per_frame, thr=10.0, max_attempts=0, discard0=0, out=None, counters=True):
+        """The sampling loop for every frame set with set_frame / set_frames, image after image on the running generators, with no host round trip
+        (dsac_sample_refstream_frames).  discard0: outputs generator 0 skips before every image (6 400 where the reference sub-samples a 40 x 40 grid);
+        max_attempts: per stream and image, 0 = 256 per hypothesis wanted of a stream (at least 4 096).  out = (poses F*N x 6, sets F*N x 4, ok F*N[,
+        consumed32 F x T uint64, attempts F x T int64]) preallocated numpy or torch buffers; with device buffers the call only enqueues.
+        Returns (poses, sets, ok, consumed32, attempts); the counters are None with counters=False."""
+        F, N, T = getattr(self, "frames", 1), int(hyps_per_frame), max(getattr(self, "_rs_threads", 0), 1)
+        if out is None:
+            out = (np.zeros((F * N, 6)), np.zeros((F * N, 4), np.int32), np.zeros(F * N, np.uint8))
+        poses, sets_out, ok = out[:3]
+        consumed, attempts = (out[3], out[4]) if len(out) >= 5 else ((np.zeros((F, T), np.uint64), np.zeros((F, T), np.int64)) if counters else (None, None))
+        check(self._ctx, lib.dsac_sample_refstream_frames(self._ctx, N, float(thr), int(max_attempts), int(discard0), ptr(poses), ptr(sets_out), ptr(ok), ptr(consumed),
+                                                          ptr(attempts)))
+        return poses, sets_out, ok, consumed, attempts
+
+    def _pi_refstream(self, refstream):
+        """refstream= of the process-images calls: None leaves the context as it is; False / True switch "pi_refstream"; a dict(discard0=, attempts=)
+        switches it on with those options.  The options stay set on the context."""
+        if refstream is None:
+            return
+        if isinstance(refstream, dict):
+            self.set_option("pi_refstream_discard0", refstream.get("discard0", 0))
+            self.set_option("pi_refstream_attempts", refstream.get("attempts", 0))
+            refstream = refstream.get("on", True)
+        self.set_option("pi_refstream", 1 if refstream else 0)
 
     # ---- K2 ---------------------------------------------------------------------------------------
     def reproject(self, poses, N=None, clamp=CNN_OBJ_MAXINPUT, err=None, soft=None, tau=10.0, beta=0.5):

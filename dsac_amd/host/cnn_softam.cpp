@@ -294,6 +294,16 @@ struct DeviceArgsScope {
 };
 }  // namespace
 
+// "pi_refstream" is a knob of the (possibly shared) context: a batch switches it on for its own calls only, so that a Frame or another batch on the same
+// context keeps drawing from the counter stream
+namespace {
+struct RefstreamScope {
+    Context& C;
+    bool on;
+    ~RefstreamScope() { if (on) try { C.setOption("pi_refstream", 0); } catch (...) {} }
+};
+}  // namespace
+
 FrameBatch::FrameBatch(Context& ctx, int frames, int H, int W, const Camera& cam, int objHyps, int refSteps, const std::vector<int32_t>& pixelIdxs,
                        int maxFramesPerCall, const FrameBatchOptions& opt)
     : C_(ctx), F_(frames), H_(H), W_(W), N_(objHyps), refSteps_(refSteps), maxCall_(maxFramesPerCall), cam_(cam), opt_(opt) {
@@ -341,7 +351,8 @@ void FrameBatch::processImages(int first, int count, uint64_t seedOfFrame0, int 
     if (first < 0 || count <= 0 || first + count > F_ || count > maxCall_) throw Error(DSAC_ERR_INVALID, "FrameBatch::processImages: bad frame range");
     const size_t P = (size_t)H_ * W_, N = (size_t)N_, f0 = (size_t)first;
     dsac_ctx* c = C_.get();
-    C_.setOption("pi_defer_tail", opt_.deferTail ? (opt_.deferScoreTail ? 2 : 1) : 0);
+    setSamplingOptions();
+    const RefstreamScope rsScope{C_, opt_.refstream > 0};
     // with the score tail deferred every result row of the previous call is still being written: the same frames again (one call per pass) go in order
     if (opt_.deferTail && opt_.deferScoreTail && first < lastFirst_ + lastCount_ && lastFirst_ < first + count) C_.check(dsac_join_tail(c), "dsac_join_tail");
     lastFirst_ = first; lastCount_ = count;
@@ -389,6 +400,17 @@ void FrameBatch::backward(int first, int count, int inlierThreshold2D, int inlie
 }
 
 // ---- the score-CNN seam on the batch ----------------------------------------------------------------------------------------------------
+void FrameBatch::setSamplingOptions() {
+    C_.setOption("pi_defer_tail", opt_.deferTail ? (opt_.deferScoreTail ? 2 : 1) : 0);
+    C_.setOption("pi_refstream", opt_.refstream > 0 ? 1 : 0);
+    if (opt_.refstream > 0) {
+        if (opt_.refstreamDiscard > (1ull << 24) || opt_.refstreamAttempts < 0 || opt_.refstreamAttempts > 0x7fffffffll)
+            throw Error(DSAC_ERR_INVALID, "FrameBatchOptions: refstreamDiscard is at most 2^24, refstreamAttempts 0 .. 2^31 - 1");
+        C_.setOption("pi_refstream_discard0", (int)opt_.refstreamDiscard);
+        C_.setOption("pi_refstream_attempts", (int)opt_.refstreamAttempts);
+    }
+}
+
 void FrameBatch::bindRange(int first, int count) {
     const size_t P = (size_t)H_ * W_, f0 = (size_t)first;
     unsigned flags = DSAC_FRAME_BORROW;
@@ -403,7 +425,8 @@ void FrameBatch::scoreImages(int first, int count, uint64_t seedOfFrame0, int in
     if (!opt_.errorImages) throw Error(DSAC_ERR_INVALID, "FrameBatch::scoreImages: the batch was made without FrameBatchOptions::errorImages");
     const size_t N = (size_t)N_, f0 = (size_t)first;
     dsac_ctx* c = C_.get();
-    C_.setOption("pi_defer_tail", opt_.deferTail ? (opt_.deferScoreTail ? 2 : 1) : 0);
+    setSamplingOptions();
+    const RefstreamScope rsScope{C_, opt_.refstream > 0};
     if (opt_.deferTail && opt_.deferScoreTail && first < lastFirst_ + lastCount_ && lastFirst_ < first + count) C_.check(dsac_join_tail(c), "dsac_join_tail");
     lastFirst_ = first; lastCount_ = count;
     // one slice per FRAME (like scores_ / w_), not one buffer per call: with the score tail deferred (pi_defer_tail = 2) K3 of this call reads its scores on
@@ -525,10 +548,12 @@ void FrameBatch::gatherFramesFrom(const FrameBatch& src, const std::vector<int32
 }
 
 void FrameBatch::processAll(uint64_t seedOfFrame0, int inlierThreshold2D, int inlierCount, float tau, float beta, double alpha) {
+    if (opt_.refstream > 0) C_.forceInitRand((unsigned)seedOfFrame0, opt_.refstream);  // ThreadRand::forceInit, once: the generators run on through the batches
     for (int f = 0; f < F_; f += maxCall_) processImages(f, std::min(maxCall_, F_ - f), seedOfFrame0, inlierThreshold2D, inlierCount, tau, beta, alpha);
 }
 
 void FrameBatch::processAll(uint64_t seedOfFrame0, int inlierThreshold2D, int inlierCount, const ScoreModel& model, float tau, float beta) {
+    if (opt_.refstream > 0) C_.forceInitRand((unsigned)seedOfFrame0, opt_.refstream);
     for (int f = 0; f < F_; f += maxCall_) processImages(f, std::min(maxCall_, F_ - f), seedOfFrame0, inlierThreshold2D, inlierCount, model, tau, beta);
 }
 

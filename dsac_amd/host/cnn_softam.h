@@ -208,6 +208,13 @@ struct FrameBatchOptions {
     bool quantiseInt16 = false;
     bool sampling = false;     // every frame brings its own H*W x 2 table of image positions (the reference's sub-sampled 40x40 maps: stochasticSubSample,
                                // core/cnn_softam.h:283-309, draws them per image); false: the full-resolution grid, cell (x, y) at pixel (x, y)
+    // The minimal sets from the reference's own generators (core/thread_rand.cpp:40-69) instead of the counter stream: dsac_set_option("pi_refstream", 1) for
+    // every call of this batch -- the sets of the reference run with `refstream` OpenMP threads and the same seed, at the speed of the batched path (the
+    // images of a call are sampled one after the other, as the reference's loop does; no host round trip).  processAll initialises the generators with
+    // its seed (Context::forceInitRand) before its first call; a caller of processImages / scoreImages does that itself, once.
+    int refstream = 0;                          // > 0: the reference's thread count
+    unsigned long long refstreamDiscard = 0;    // outputs generator 0 skips before every image (4 H W where stochasticSubSample drew the image's sampling grid)
+    long long refstreamAttempts = 0;            // attempt budget per stream and image; 0 = 256 per hypothesis wanted of a stream, at least 4 096
 };
 
 // The score model at the seam of the batched path -- the reference's score CNN (core/cnn_softam.h:1072: forward(diffMaps); core/train_ransac_softam.cpp:
@@ -288,6 +295,7 @@ private:
     DeviceArray<float> dErr_;              // softInlierModel's gradient images (maxCall x objHyps x H*W), allocated on first use
     int seamFirst_ = -1, seamCount_ = 0;   // the range whose error images err_ holds
     void bindRange(int first, int count);
+    void setSamplingOptions();  // "pi_defer_tail" and "pi_refstream*" of the context, as this batch's options say
     void ensureBackwardBuffers();
     std::vector<uint8_t> done_;
 };

@@ -49,6 +49,7 @@ struct EngineParameters {
     int refstream = 0;                // -refstream T : draw the minimal sets from the reference's own generators, std::mt19937(seed + t) of T OpenMP threads (core/thread_rand.cpp:40-69;
                                       //           dsac_sample_refstream): the evaluation program's sets equal the reference's for the same seed and thread count, no <stem>.sets
                                       //           replay file needed; frames with a stochastic sub-sampling grid skip the 6400 outputs it drew (-refsub 0: do not)
+                                      //           With -batch F the batches draw from those generators too (FrameBatchOptions::refstream, dsac_sample_refstream_frames): the same files
     int refsub = 1;
     int passes = 1;                   // -passes : process the data set this many times (the first pass warms the device up; timing is reported per pass)
     bool errorImages = true;          // -errimg : write the N error images of every image (the score CNN's input) as the reference does

@@ -74,7 +74,7 @@ int main(int argc, const char* argv[]) {
         // hypothesis counts take the per-image path.  Both give the same numbers image by image (tests/test_gpu_drivers.py).
         bool batchable = gp->eP.batch > 0 && nImg > 0 && (gp->eP.batch == 1 || objHyps % 128 == 0);
         for (const DriverFrame& fr : testDataset)
-            batchable = batchable && gp->eP.refstream <= 0 && fr.H == testDataset[0].H && fr.W == testDataset[0].W && fr.sets.empty() && fr.sampling.empty() == testDataset[0].sampling.empty() &&
+            batchable = batchable && fr.H == testDataset[0].H && fr.W == testDataset[0].W && fr.sets.empty() && fr.sampling.empty() == testDataset[0].sampling.empty() &&
                         (fr.pixelIdxs.empty() || fr.permSteps < refSteps);
         const int passes = std::max(1, gp->eP.passes);
         if (batchable) {
@@ -84,6 +84,10 @@ int main(int argc, const char* argv[]) {
             opt.sampling = !testDataset[0].sampling.empty();  // sub-sampled maps: every image has its own table of image positions
             opt.deferTail = gp->eP.defer >= 1;
             opt.deferScoreTail = gp->eP.defer >= 2;
+            // -refstream T -batch F: the batches draw their sets from the reference's own generators as the per-image path below does, generator 0 skipping
+            // the sub-sampler's draws before an image that has a sampling grid (-refsub)
+            opt.refstream = std::max(0, gp->eP.refstream);
+            opt.refstreamDiscard = (gp->eP.refsub && opt.sampling) ? 4ull * H * W : 0ull;
             const clk::time_point tUp = clk::now();
             FrameBatch batch(engine, (int)nImg, H, W, camMat, objHyps, refSteps, refinePermutations(H * W, refSteps), gp->eP.batch, opt);
             for (size_t i = 0; i < nImg; i++) batch.setFrame((int)i, testDataset[i].estObj.data(), testDataset[i].poseGT, opt.sampling ? testDataset[i].sampling.data() : nullptr);

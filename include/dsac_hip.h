@@ -127,6 +127,7 @@ DSAC_API int dsac_device_info(dsac_ctx* ctx, int* cus, int* clock_khz, uint64_t*
  *                 map of >= 16 384 cells (and no perturbed cells / fused loss) run every step as a scan of the step's cells + one LM launch instead (0.65 ms for the
  *                 same 128 walks, bit-identical again; "k6_walk_exact", "k6_scan_tune" above; profiles/r06_k6_walk.txt); a non-zero value keeps the fused kernel
  *   "refstream_mode"  see dsac_sample_refstream
+ *   "pi_refstream", "pi_refstream_discard0", "pi_refstream_attempts"   see dsac_sample_refstream_frames
  *   "k1_wpb", "k1_prio", "k1_hpw", "k1_minw"   K1 waves per workgroup (1), wave priority (3), hypotheses per wave (1), register budget in waves per SIMD (1)
  *   "k1_rl"       lanes per sampling attempt: 1 (default) = one lane per attempt, the quartic's roots in sequence, 64 attempts per round and
  *                 hypothesis; 4 = one lane per root, 16 attempts per round (the form the wpb / hpw / minw / share knobs below act on)
@@ -240,6 +241,34 @@ DSAC_API int dsac_refstream_init(dsac_ctx* ctx, unsigned seed, int threads);
 DSAC_API int dsac_refstream_discard(dsac_ctx* ctx, int thread, unsigned long long n32);
 DSAC_API int dsac_sample_refstream(dsac_ctx* ctx, int N, float thr, long long max_attempts, double* poses, int32_t* sets_out, uint8_t* ok,
                                    unsigned long long* consumed32_or_null, long long* attempts_or_null);
+
+/* The same loop, enqueue-only and for frame batches: what the reference's loop over its test images does with ThreadRand's static generators
+ * (core/thread_rand.cpp:40-69), image after image.  For every frame set with dsac_set_frame / dsac_set_frames, in order: generator 0 skips
+ * discard0_per_image outputs (stochasticSubSample drew them before the sampling loop, core/cnn_softam.h:283-309: 6 400 for its 40 x 40 grid; 0 where the
+ * frame came with a sampling grid of its own), then the sampling loop of core/cnn_softam.h:1010-1060 serves hyps_per_frame hypotheses as
+ * dsac_sample_refstream does.  Image f reads frame f, writes rows [f N, (f + 1) N) of poses / sets_out / ok and starts from the generator positions image
+ * f - 1 left; images are served one after the other because that is the reference's order.  consumed32_or_null / attempts_or_null:
+ * [frames][threads], outputs taken by / attempts made in the sampling loop of that image on that stream (the skipped outputs are not counted).
+ *   No host round trip: the windows of attempts are sized before anything is enqueued -- the first holds 16 attempts per hypothesis wanted of a stream,
+ *   as a power of two in [256, 16 384], every further one doubles up to 16 384, the last is trimmed so that they sum to max_attempts exactly
+ *   (rs::window_ladder, dsac_amd/csrc/refstream.h) -- and every window is two launches (one workgroup per stream selects the accepted attempts of the
+ *   previous window and parses the next; one lane per attempt evaluates it); a window behind the one that served a stream's last hypothesis returns at
+ *   once.  With device-resident arrays the call enqueues on the context's stream and returns: no hipStreamSynchronize, no blocking copy (unless the
+ *   window scratch has to grow: its first use and larger ladders allocate).  Host arrays are staged and copied back as everywhere else.
+ *   max_attempts: per stream and per image, charged by the attempts a stream made (not by window sizes); 0 = 256 per hypothesis wanted of a stream, at
+ *   least 4 096 (the reference has no cap; its golden frames need up to 148 per hypothesis).  A budget whose ladder needs more than 64 windows, or
+ *   discard0_per_image > 2^24, is DSAC_ERR_INVALID -- nothing is truncated silently (the default budget stays inside the limit up to 4 096 hypotheses per
+ *   stream).  Hypotheses a stream could not serve report ok = 0 and a zero pose,
+ *   and its generator stops where the budget ends, as in dsac_sample_refstream.
+ * dsac_set_option("pi_refstream", 1): dsac_process_images and dsac_process_images_begin draw their sets with this chain instead of K1's counter stream
+ * (`seed` and `max_tries` are then unused): the result is what this call followed by the rest of processImage on those sets gives, in every
+ * "pi_defer_tail" mode (generators, counters and window scratch are touched on the context's stream only).  "pi_refstream_discard0": outputs generator 0
+ * skips before every image (default 0); "pi_refstream_attempts": the budget (default 0 = as above).  Without dsac_refstream_init: DSAC_ERR_INVALID.
+ * Sets identical to the real reference's on both golden frames (threads 1, 3, 4) and to dsac_sample_refstream called image by image, counters included
+ * (tests/test_gpu_refstream_frames.py).  Measured (profiles/refstream_frames.txt): one 640 x 480 image, 256 hypotheses, default budget: 152 us on one stream
+ * (dsac_sample_refstream beside it: 284), 53 us on eight (94); inside dsac_process_images on 16 such images 225 / 151 us per image against 67 on the counter stream. */
+DSAC_API int dsac_sample_refstream_frames(dsac_ctx* ctx, int hyps_per_frame, float thr, long long max_attempts, unsigned long long discard0_per_image,
+                                          double* poses, int32_t* sets_out, uint8_t* ok, unsigned long long* consumed32_or_null, long long* attempts_or_null);
 
 /* ---- K2: batched reprojection -> error images and/or soft-inlier scores -------------------------- */
 /* Replaces the N getDiffMap calls of core/cnn_softam.h:1067-1069 (getDiffMap :319-362):
