@@ -45,7 +45,15 @@ EXPORTS = [
     "dsac_softmax_frames", "dsac_process_images_begin", "dsac_process_images_finish",
     "dsac_refine_fd_sets_frames", "dsac_loss_batch_frames", "dsac_select_frames", "dsac_soft_score_derr",
     "dsac_refstream_init", "dsac_refstream_discard", "dsac_sample_refstream", "dsac_sample_refstream_frames",
+    "dsac_get_option", "dsac_k2_range_census",
 ]
+
+# enum dsac_k2_form (dsac_get_option "k2_form_last") and the DSAC_K2_WHY_* bits ("k2_form_why_last")
+K2_FORMS = ("none", "fp32 valu", "fp32 mfma", "records in two pieces", "exact (vector build)", "exact (any-map build)", "precise")
+DSAC_K2_WHY_AUTO_OFF = 1
+DSAC_K2_WHY_FORCED = 2
+DSAC_K2_WHY_FOCAL = 4
+DSAC_K2_WHY_NO_POSES = 8
 
 
 class DsacError(RuntimeError):
@@ -99,6 +107,8 @@ def _load():
     lib.dsac_set_frames.argtypes = [vp, i32, vp, vp, i32, i32, i32, f32, f32, f32, f32, u32]
     lib.dsac_score_hypotheses_frames.argtypes = [vp, i32, u64, f32, i32, f32, f32, f32, f64, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.dsac_set_option.argtypes = [vp, C.c_char_p, i32]
+    lib.dsac_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i32)]
+    lib.dsac_k2_range_census.argtypes = [vp, i32, vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     lib.dsac_loss_frames.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.dsac_select.argtypes = [vp, i32, vp, vp, i32, f64, vp, vp, vp]
     lib.dsac_join_tail.argtypes = [vp]

@@ -73,6 +73,7 @@ struct dsac_ctx {
     struct Pending { void* host; const void* dev; size_t bytes; };
     std::vector<Pending> pending;
     dk::K2Opts k2;  // launch knobs, read once in dsac_create (DSAC_K2_*) or set with dsac_set_option; no process-wide state
+    int k2_last[2] = {0, 0};  // the arithmetic form of the last K2 launch this context enqueued and why it was not the exact one (dsac_get_option "k2_form_last" / "k2_form_why_last")
     dk::K1Opts k1;
     int k1_cus = 0;       // > 0: the auxiliary stream of the pipelined pair (K1 of the next step) is confined to that many CUs (DSAC_K1_CUS / "k1_cus")
     bool device_args = false;  // "device_args": every pointer argument is a device pointer (the caller's promise; skips hipPointerGetAttributes per argument)
@@ -236,6 +237,7 @@ struct ProfScope {
     dk::K2Opts k2(const double* poses64 = nullptr) const {
         dk::K2Opts o = c->k2;
         if (on && attached) { o.ev_start = p.a; o.ev_stop = p.b; }
+        o.report = c->k2_last;
         o.poses64 = poses64;  // the cv poses of this launch: what the precise form ("k2_flags" bit 25) projects with
         o.staged_lo = (poses64 && (o.flags & dk::K2_FLAG_RECLO)) ? c->staged_lo.as<float>() : nullptr;  // filled by k2_records_lo() before the launch
         o.split = (poses64 && dk::k2_wants_exact(o) && dk::pose_split_available(c->F)) ? c->staged_split.as<char>() : nullptr;  // likewise
@@ -1125,6 +1127,68 @@ int dsac_set_option(dsac_ctx* c, const char* key, int value) {
     else if (k == "k1_cus") { if (c->aux) return fail(c, DSAC_ERR_INVALID, "dsac_set_option: k1_cus must be set before the first dsac_sample_ahead"); c->k1_cus = value; }
     else return fail(c, DSAC_ERR_INVALID, "dsac_set_option: unknown key '%s'", key);
     return DSAC_OK;
+}
+
+static_assert(DSAC_K2_FORM_NONE == dk::K2_FORM_NONE && DSAC_K2_FORM_FP32_VALU == dk::K2_FORM_FP32_VALU && DSAC_K2_FORM_FP32_MFMA == dk::K2_FORM_FP32_MFMA &&
+              DSAC_K2_FORM_RECLO == dk::K2_FORM_RECLO && DSAC_K2_FORM_EXACT_VEC == dk::K2_FORM_EXACT_VEC && DSAC_K2_FORM_EXACT_ANY == dk::K2_FORM_EXACT_ANY &&
+              DSAC_K2_FORM_PRECISE == dk::K2_FORM_PRECISE, "enum dsac_k2_form follows the kernels' own numbering");
+static_assert(DSAC_K2_WHY_AUTO_OFF == dk::K2_WHY_AUTO_OFF && DSAC_K2_WHY_FORCED == dk::K2_WHY_FORCED && DSAC_K2_WHY_FOCAL == dk::K2_WHY_FOCAL &&
+              DSAC_K2_WHY_NO_POSES == dk::K2_WHY_NO_POSES, "the reason bits follow the kernels' own numbering");
+
+int dsac_get_option(dsac_ctx* c, const char* key, int* value) {
+    if (!c || !key || !value) return fail(c, DSAC_ERR_INVALID, "dsac_get_option: NULL argument");
+    const std::string k = key;
+    // host state only: nothing here touches the device or waits for it
+    if (k == "k2_form_last") *value = c->k2_last[0];
+    else if (k == "k2_form_why_last") *value = c->k2_last[1];
+    else if (k == "k2_variant") *value = c->k2.variant;
+    else if (k == "k2_order") *value = c->k2.pixel_minor ? 1 : 0;
+    else if (k == "k2_flags") *value = c->k2.flags;
+    else if (k == "k2_diag") *value = c->k2.diag;
+    else if (k == "k2_exact_auto") *value = c->k2.exact_auto ? 1 : 0;
+    else if (k == "k6_walk_exact") *value = c->k6_walk_exact;
+    else if (k == "k6_scan_tune") *value = dk::refine_scan_tune_get();
+    else if (k == "k6_waves") *value = c->k6_waves;
+    else if (k == "refstream_mode") *value = c->rs_mode;
+    else if (k == "pi_refstream") *value = c->pi_refstream;
+    else if (k == "pi_refstream_discard0") *value = c->pi_refstream_discard0;
+    else if (k == "pi_refstream_attempts") *value = c->pi_refstream_attempts;
+    else if (k == "k1_wpb") *value = c->k1.wpb;
+    else if (k == "k1_prio") *value = c->k1.prio;
+    else if (k == "k1_hpw") *value = c->k1.hpw;
+    else if (k == "k1_horn") *value = c->k1.horn ? 1 : 0;
+    else if (k == "k1_minw") *value = c->k1.minw;
+    else if (k == "k1_rl") *value = c->k1.rl;
+    else if (k == "k1_wide") *value = c->k1.wide;
+    else if (k == "k1_share") *value = c->k1.share_always ? -c->k1.share : c->k1.share;
+    else if (k == "k4_variant") *value = c->k4_variant;
+    else if (k == "device_args") *value = c->device_args ? 1 : 0;
+    else if (k == "tail_prio") *value = c->tail_prio;
+    else if (k == "seed_stride") *value = c->seed_stride;
+    else if (k == "pi_defer_tail") *value = c->pi_defer_tail;
+    else if (k == "k1_cus") *value = c->k1_cus;
+    else return fail(c, DSAC_ERR_INVALID, "dsac_get_option: unknown key '%s'", key);
+    return DSAC_OK;
+}
+
+int dsac_k2_range_census(dsac_ctx* c, int N, const double* poses, long long* far_chunks, long long* oor_poses) {
+    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_k2_range_census: ctx is NULL");
+    if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "dsac_k2_range_census: no frame set");
+    if (N < 0 || (N > 0 && !poses) || !far_chunks || !oor_poses) return fail(c, DSAC_ERR_INVALID, "dsac_k2_range_census: N >= 0 and non-NULL poses / outputs");
+    HIP_TRY(c, hipSetDevice(c->device));
+    begin_call(c);
+    const double* d_poses;
+    ARG_TRY(in_arg(c, poses, (size_t)N * 6, &d_poses));
+    DevBuf& cnt = next_slot(c);
+    HIP_TRY(c, cnt.reserve(2 * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemsetAsync(cnt.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    HIP_TRY(c, dk::k2_range_census(c->stream, N, d_poses, c->F, cnt.as<unsigned long long>()));
+    unsigned long long h[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(h, cnt.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *far_chunks = (long long)h[0];
+    *oor_poses = (long long)h[1];
+    return end_call(c);
 }
 
 int dsac_set_k2_events(dsac_ctx* c, void* wait_before_or_null, void* record_after_or_null) {

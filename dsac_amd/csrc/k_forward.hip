@@ -101,6 +101,27 @@ DM_INLINE double split_piece(double& rem, int grid_exp) {  // the multiple of 2^
     return p;
 }
 DM_INLINE _Float16 hf(double v, int e) { return (_Float16)(float)ldexp(v, e); }
+// does the split of one record row (three rotation entries and the translation, focal length folded in) clamp a piece or meet a non-finite entry?  Such a
+// hypothesis is outside the exact form's range (|t_z| >= 2047.5 x 2^6 mm, |f t_x| >= 2047.5 x 2^(E+6)): k_pose_prep_split marks it in the one half of its record
+// that multiplies a zero of the B operand, the any-map build of K2 sends its group down the fp32 transform, dsac_k2_range_census counts it
+DM_INLINE bool split_piece_bad(double& rem, int grid_exp) {  // split_piece, returning whether the piece had to be clamped (or is not a number)
+    const double n = rint(ldexp(rem, -grid_exp));
+    rem -= ldexp(fmin(fmax(n, -2047.0), 2047.0), grid_exp);
+    return !(fabs(n) <= 2047.0);
+}
+DM_INLINE bool split_row_bad(const double (&a)[4], int E) {
+    bool bad = false;
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+        double rem = a[q];
+        bad |= !(fabs(rem) < 1.0e300);
+        bad |= split_piece_bad(rem, E - 10); bad |= split_piece_bad(rem, E - 21); bad |= split_piece_bad(rem, E - 32);
+    }
+    double rem = a[3];
+    bad |= !(fabs(rem) < 1.0e300);
+    bad |= split_piece_bad(rem, E + 6); bad |= split_piece_bad(rem, E - 5); bad |= split_piece_bad(rem, E - 16); bad |= split_piece_bad(rem, E - 27);
+    return bad;
+}
 __global__ __launch_bounds__(256) void k_pose_prep_split(int N, const double* __restrict__ poses, float fx, float fy, int ex, h8* __restrict__ cross, h4* __restrict__ hi) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;  // one thread per (hypothesis, row)
     const int h = i / 3, r = i - 3 * h;
@@ -126,7 +147,8 @@ __global__ __launch_bounds__(256) void k_pose_prep_split(int N, const double* __
     double rem = a[3];
     const double tA = split_piece(rem, E + 6), tA2 = split_piece(rem, E - 5), tC = split_piece(rem, E - 16), tD = split_piece(rem, E - 27);
     // against B[q = 3] = the pieces of SPLIT_T_COORD = (2^10, 2^3, 2^11, 0, 0, 0, 1, 0)
-    oh[3] = h4{z, hf(tA2, -3), hf(tA, -11), z};
+    // the fourth half meets the 0 of B[q = 3]: the product is an exact zero whatever it holds, so it carries the out-of-range mark (1 or 0) for free
+    oh[3] = h4{z, hf(tA2, -3), hf(tA, -11), split_row_bad(a, E) ? (_Float16)1.f : z};
     oc[3] = h8{z, hf(tC, 11), z, z, z, z, hf(tD, 14), z};
 }
 
@@ -721,7 +743,17 @@ static hipError_t launch_reproject_hp(hipStream_t st, int N, const float* staged
 // component, L2-resident -- no LDS image, no barrier before the first MFMA), the pixel positions of the implicit grid from a
 // wave-uniform row / column (W % 64 == 0), and the only barrier is the one before the 16 NG partial soft sums leave the workgroup.
 // --------------------------------------------------------------------------------------------------
-template <int NG, int CHW, int WAVES, bool PW, bool ERR, bool SOFT, bool UV, bool G64, int MINW, bool LO = false, int EXF = 0>
+// ANY (the any-map build of the exact form): no 16-byte alignment of err / uv / xyz and no P % 4 == 0, the same arithmetic per cell.
+//   ANY = 1, the main launch: the vector build's code on every lane whose four cells exist -- a 16-byte buffer store and a 16-byte load need dword alignment only
+//            on this hardware, so the stores are the very same instructions and the sampled positions are read through a 4-byte-aligned vector type.  A lane that
+//            holds the map's last 1-3 cells is left out here (no store, no sigmoid).  Nothing else differs, so the register allocation is the vector build's
+//            (handling the last cells inside this kernel was built first: the <64, 256> err + soft instantiations spilled 60-460 bytes per lane).
+//            (Four dword stores per lane instead of the one 16-byte store were measured as a build of their own and removed: 562.6 against 169.5 us for
+//            256 x 641x479, 10 445 against 2 687 us for 16 x 256, profiles/k2_anymap_ab.txt.)
+//   ANY = 2, the tail launch (only when P % 4 != 0): one wave per hypothesis tile on the map's LAST 64-cell chunk, for that one lane alone -- its cells loaded,
+//            stored and summed one by one (per-cell validity: a padded cell never adds a sigmoid to a score), its sums in a partial row of their own.
+typedef f4 f4_a4 __attribute__((aligned(4)));
+template <int NG, int CHW, int WAVES, bool PW, bool ERR, bool SOFT, bool UV, bool G64, int MINW, bool LO = false, int EXF = 0, int ANY = 0>
 __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* __restrict__ staged, const float* __restrict__ xyz,
                                                              const float* __restrict__ uv, float* __restrict__ err,
                                                              float* __restrict__ soft_part, int N, int P, int W, int PT, float cx, float cy,
@@ -770,11 +802,13 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* 
     float sby[G64 ? CHW : 1];
     int p0[CHW];
     bool valid[CHW];
-    const int chunk0 = (pt * WAVES + wave) * CHW;
+    const int chunk0 = (pt * WAVES + wave) * CHW + (ANY == 2 ? (P - 1) >> 6 : 0);  // the tail launch: the map's last chunk
 #pragma unroll
     for (int ch = 0; ch < CHW; ch++) {
         p0[ch] = (chunk0 + ch) * 64 + 4 * c;
-        valid[ch] = p0[ch] < P;  // P % 4 == 0
+        if constexpr (ANY == 1) valid[ch] = p0[ch] + 3 < P;                      // all four cells exist
+        else if constexpr (ANY == 2) valid[ch] = p0[ch] < P && p0[ch] + 3 >= P;  // the lane of the map's last 1-3 cells
+        else valid[ch] = p0[ch] < P;  // P % 4 == 0
 #pragma unroll
         for (int m = 0; m < 4; m++) {
             const int pc = min(p0[ch] + m, P - 1);
@@ -847,7 +881,25 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* 
     for (int ch = 0; ch < CHW; ch++) {
         if (UV) {
             constexpr int pc = G64 ? 0 : 1;
-            if (valid[ch]) {
+            if constexpr (ANY != 0) {
+                if (valid[ch]) {
+                    f4 u0, u1;
+                    if constexpr (ANY != 2) {  // any 4-byte-aligned uv: the same two 16-byte loads with dword alignment
+                        const f4_a4* su = reinterpret_cast<const f4_a4*>(uv + (size_t)p0[ch] * 2);
+                        u0 = su[0]; u1 = su[1];
+                    } else {  // cell by cell; cells beyond the map repeat the last one, as their coordinates do
+                        const float* s1 = uv + (size_t)min(p0[ch] + 1, P - 1) * 2;
+                        const float* s2 = uv + (size_t)min(p0[ch] + 2, P - 1) * 2;
+                        const float* s3 = uv + (size_t)(P - 1) * 2;
+                        u0 = f4{uv[(size_t)p0[ch] * 2], uv[(size_t)p0[ch] * 2 + 1], s1[0], s1[1]};
+                        u1 = f4{s2[0], s2[1], s3[0], s3[1]};
+                    }
+                    ppix[ch * pc][0] = f2{u0.x - cx, u0.y - cy}; ppix[ch * pc][1] = f2{u0.z - cx, u0.w - cy};
+                    ppix[ch * pc][2] = f2{u1.x - cx, u1.y - cy}; ppix[ch * pc][3] = f2{u1.z - cx, u1.w - cy};
+                } else {
+                    ppix[ch * pc][0] = ppix[ch * pc][1] = ppix[ch * pc][2] = ppix[ch * pc][3] = splat(0.f);
+                }
+            } else if (valid[ch]) {
                 const f4* su = reinterpret_cast<const f4*>(uv + (size_t)p0[ch] * 2);
                 const f4 u0 = su[0], u1 = su[1];
                 ppix[ch * pc][0] = f2{u0.x - cx, u0.y - cy}; ppix[ch * pc][1] = f2{u0.z - cx, u0.w - cy};
@@ -881,6 +933,10 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* 
         }
         const float nax = EX ? 0.f : -ax[EX ? 0 : gi], nay = EX ? 0.f : -ay[EX ? 0 : gi];  // x and y rows negated: the MFMA yields (-xc, -yc, zc)
         const int hyp0 = 16 * gi + 4 * g;
+        // ANY: a group with a hypothesis whose split records clamp (k_pose_prep_split's mark in the translation quarter) takes the fp32 transform like a chunk of
+        // far coordinates -- small maps are where P3P returns such poses (5 x 7 cells: 3 of 64 with |t_z| > 200 m).  The vector build is left as it was
+        bool grp_far = false;
+        if constexpr (ANY != 0 && EX) grp_far = __any((float)aex[gi].hx[3] != 0.f || (float)aex[gi].hy[3] != 0.f || (float)aex[gi].hz[3] != 0.f);
         f2 ssum[4] = {splat(0.f), splat(0.f), splat(0.f), splat(0.f)};
 #pragma unroll
         for (int ch = 0; ch < CHW; ch++) {
@@ -894,7 +950,7 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* 
             }
             const f2 (&pp)[4] = ppix[G64 ? 0 : ch];
             if (EX) {
-                if (__builtin_expect(oor[ch], 0)) {
+                if (__builtin_expect(oor[ch] || grp_far, 0)) {
                     // a coordinate beyond the split's range: this chunk through the fp32 transform (operands fetched here, the rare path)
                     const int hyp = min(16 * gi + c, nh - 1);
                     const float* rec = staged + (size_t)(h0 + hyp) * POSE_STRIDE + g;
@@ -911,12 +967,42 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* 
             } else if (__builtin_expect(__any(hp_chunk<false, SOFT, LO>(nax, nay, az[EX ? 0 : gi], Bm[ch], pp, clampv, kA, kB, ev, sloc, &alo[LO ? gi : 0], B16[LO ? ch : 0])), 0)) {
                 (void)hp_chunk<true, SOFT, LO>(nax, nay, az[EX ? 0 : gi], Bm[ch], pp, clampv, kA, kB, ev, sloc, &alo[LO ? gi : 0], B16[LO ? ch : 0]);
             }
+            if constexpr (ANY == 2) {
+                // per-cell validity of the sigmoids: exactly 1.0 on real cells, 0.0 on the cells that pad the last 4-cell group
+                const int nv = P - p0[ch];
+                if (SOFT) {
+                    const f2 m01 = {nv > 0 ? 1.0f : 0.0f, nv > 1 ? 1.0f : 0.0f}, m23 = {nv > 2 ? 1.0f : 0.0f, nv > 3 ? 1.0f : 0.0f};
+#pragma unroll
+                    for (int r = 0; r < 4; r++)
+                        sloc[r] = pk_fma(soft_inlier2(f2{ev[r].x, ev[r].y}, kA, kB), m01, soft_inlier2(f2{ev[r].z, ev[r].w}, kA, kB) * m23);
+                }
+            }
             if (SOFT) {
                 const f2 vf = splat(valid[ch] ? 1.0f : 0.0f);
 #pragma unroll
                 for (int r = 0; r < 4; r++) ssum[r] = pk_fma(sloc[r], vf, ssum[r]);
             }
-            if (ERR && valid[ch]) {
+            bool fast_stores = true;
+            if constexpr (ANY != 0) {
+                // the tail launch's lane stores its cells one by one
+                fast_stores = ANY == 1;
+                if (ERR && valid[ch] && !fast_stores) {
+                    const int nv = P - p0[ch];
+                    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(err + (size_t)(h0 + 16 * gi) * P, 0, 0xffffffffu, 0x00020000);
+                    const unsigned loff = ((unsigned)(4 * g) * (unsigned)P + (unsigned)p0[ch]) * 4u;
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        if (hyp0 + r >= nh) continue;
+                        const unsigned soff = (unsigned)r * (unsigned)P * 4u;
+                        const float ex = ev[r].x, ey = ev[r].y, ez = ev[r].z, ew = ev[r].w;  // by value: a bit cast of a vector ELEMENT reads the vector's first dword
+                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ex), rsrc, loff, soff, 2);
+                        if (nv > 1) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ey), rsrc, loff + 4u, soff, 2);
+                        if (nv > 2) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ez), rsrc, loff + 8u, soff, 2);
+                        if (nv > 3) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ew), rsrc, loff + 12u, soff, 2);
+                    }
+                }
+            }
+            if (ERR && valid[ch] && fast_stores) {
                 // buffer store: the address is a wave-uniform row base in a scalar resource (the tile's first hypothesis of this group) + a scalar row offset +
                 // a 32-bit lane offset (the lane's hypothesis quarter and pixel).  A global store's 64-bit vector address cost one vector instruction per store
                 // (v_lshl_add_u64), 16 per 1 024 pairs of a kernel that is bound by vector issue; this form steps the rows on the scalar unit
@@ -1137,7 +1223,7 @@ static hipError_t launch_reproject_ps(hipStream_t st, int N, const float* staged
     return hipGetLastError();
 }
 
-template <int NG, int CHW, int WAVES, bool PW, int MINW = 1, bool LO = false, int EX = 0>
+template <int NG, int CHW, int WAVES, bool PW, int MINW = 1, bool LO = false, int EX = 0, int ANY = 0>
 static hipError_t launch_reproject_st(hipStream_t st, int N, const float* staged, const FrameDev& F, float clampv, float* err, float kA, float kB,
                                       float* soft_part, int* tiles_used, int Nf, int kflags, hipEvent_t evA, hipEvent_t evB, const float* staged_lo = nullptr,
                                       const void* split = nullptr) {
@@ -1151,12 +1237,36 @@ static hipError_t launch_reproject_st(hipStream_t st, int N, const float* staged
     const bool ERR = err != nullptr, SOFT = soft_part != nullptr, UV = F.uv != nullptr;
     const bool G64 = !UV && (F.W & 63) == 0;
 #define DSAC_K2S(E, S, U, G)                                                                                                               \
-    hipExtLaunchKernelGGL((k_reproject_st<NG, CHW, WAVES, PW, E, S, U, G, MINW, LO, EX>), dim3(grid), dim3(WAVES * 64), 0, st, evA, evB, 0, staged, F.xyz, F.uv, err, \
+    hipExtLaunchKernelGGL((k_reproject_st<NG, CHW, WAVES, PW, E, S, U, G, MINW, LO, EX, ANY>), dim3(grid), dim3(WAVES * 64), 0, st, evA, evB, 0, staged, F.xyz, F.uv, err, \
                           soft_part, N, F.P, F.W, PT, F.cx, F.cy, clampv, kA, kB, kflags, Nf, F.xyz_stride, F.uv_stride, staged_lo, split)
     if (ERR && SOFT) { if (UV) DSAC_K2S(true, true, true, false); else if (G64) DSAC_K2S(true, true, false, true); else DSAC_K2S(true, true, false, false); }
     else if (ERR) { if (UV) DSAC_K2S(true, false, true, false); else if (G64) DSAC_K2S(true, false, false, true); else DSAC_K2S(true, false, false, false); }
     else if (SOFT) { if (UV) DSAC_K2S(false, true, true, false); else if (G64) DSAC_K2S(false, true, false, true); else DSAC_K2S(false, true, false, false); }
 #undef DSAC_K2S
+    return hipGetLastError();
+}
+
+// The any-map build of the exact form: the main launch (ANY = 1) on the tile <16 NG hypotheses, 64 CHW cells>, then -- only when the cell count is no multiple
+// of 4 -- the tail launch (ANY = 2) for the lane of the last 1-3 cells, whose sums go to one more partial row.  A timing pair spans both launches.
+template <int NG, int CHW, int MINW>
+static hipError_t launch_reproject_any(hipStream_t st, int N, const float* staged, const FrameDev& F, float clampv, float* err, float kA, float kB, float* soft_part,
+                                       int* tiles_used, int Nf, int kflags, hipEvent_t evA, hipEvent_t evB, const void* split) {
+    const bool tail = (F.P & 3) != 0;
+    int rows = 0;
+    hipError_t e = launch_reproject_st<NG, CHW, 1, true, MINW, false, 2, 1>(st, N, staged, F, clampv, err, kA, kB, soft_part, &rows, Nf, kflags, evA, tail ? nullptr : evB, nullptr, split);
+    if (tiles_used) *tiles_used = rows;
+    if (e != hipSuccess || !tail) return e;
+    const int NTa = (N + 63) / 64;
+    float* part = soft_part ? soft_part + (size_t)rows * N : nullptr;  // row `rows` <= ceil(P / 64) < reproject_num_pixel_tiles(P)
+    const bool ERR = err != nullptr, SOFT = soft_part != nullptr, UV = F.uv != nullptr;
+#define DSAC_K2T(E, S, U)                                                                                                                              \
+    hipExtLaunchKernelGGL((k_reproject_st<4, 1, 1, true, E, S, U, false, 3, false, 2, 2>), dim3(NTa), dim3(64), 0, st, nullptr, evB, 0, staged, F.xyz, F.uv, err, part, N, \
+                          F.P, F.W, 1, F.cx, F.cy, clampv, kA, kB, kflags | 32, Nf, F.xyz_stride, F.uv_stride, nullptr, split)
+    if (ERR && SOFT) { if (UV) DSAC_K2T(true, true, true); else DSAC_K2T(true, true, false); }
+    else if (ERR) { if (UV) DSAC_K2T(true, false, true); else DSAC_K2T(true, false, false); }
+    else if (SOFT) { if (UV) DSAC_K2T(false, true, true); else DSAC_K2T(false, true, false); }
+#undef DSAC_K2T
+    if (tiles_used && SOFT) *tiles_used = rows + 1;
     return hipGetLastError();
 }
 
@@ -1339,6 +1449,48 @@ static hipError_t launch_reproject_prec(hipStream_t st, int N, const double* pos
     return hipGetLastError();
 }
 
+// --------------------------------------------------------------------------------------------------
+// The two degradations of the exact form made countable (dsac_k2_range_census; not in any hot path).  Wave w of the grid looks at 64-cell chunk w of the
+// frame batch exactly as k_reproject_st does (cells beyond the map repeat the last one; split_B's own predicate); thread t < N splits the records of
+// hypothesis t as k_pose_prep_split does and notes a clamped piece or a non-finite entry.
+// --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_k2_census(int N, const double* __restrict__ poses, float fx, float fy, int ex, const float* __restrict__ xyz, int P, int frames,
+                                                   long long xyz_stride, unsigned long long* __restrict__ out) {
+    const int t = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+    const int CR = (P + 63) >> 6;
+    const int w = t >> 6;  // wave-uniform
+    if (w < frames * CR) {
+        const int f = w / CR, chunk = w - f * CR;
+        const float* src = xyz + (long long)f * xyz_stride + (size_t)min(chunk * 64 + lane, P - 1) * 3;
+        bool o = false;
+#pragma unroll
+        for (int k = 0; k < 3; k++) (void)split_B(src[k], o);
+        if (__any(o) && lane == 0) atomicAdd(out, 1ull);
+    }
+    if (t < N) {
+        double rv[3] = {poses[6 * t], poses[6 * t + 1], poses[6 * t + 2]};
+        double R[9];
+        dm::rodrigues_v2m<false>(rv, R, nullptr);
+        bool bad = false;
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            const double f = r == 0 ? -(double)fx : r == 1 ? -(double)fy : 1.0;
+            const int E = r < 2 ? ex : 0;
+            const double a[4] = {f * R[3 * r], f * R[3 * r + 1], f * R[3 * r + 2], f * poses[6 * t + 3 + r]};
+            bad |= split_row_bad(a, E);
+        }
+        if (bad) atomicAdd(out + 1, 1ull);
+    }
+}
+hipError_t k2_range_census(hipStream_t st, int N, const double* poses, const FrameDev& F, unsigned long long* out2) {
+    const int frames = F.frames > 1 ? F.frames : 1;
+    const long long waves = (long long)frames * ((F.P + 63) / 64);
+    const long long threads = waves * 64 > N ? waves * 64 : N;
+    if (threads <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_k2_census, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, N, poses, F.fx, F.fy, pose_split_exponent(F), F.xyz, F.P, frames, F.xyz_stride, out2);
+    return hipGetLastError();
+}
+
 bool reproject_variant_known(int v) {
     return v == -1 || (v >= 0 && v <= 3) || (v >= 10 && v <= 13) || (v >= 20 && v <= 27) || (v >= 40 && v <= 62) || (v >= 65 && v <= 77) || (v >= 80 && v <= 85) || v == 89 || (v >= 93 && v <= 95);
 }
@@ -1389,23 +1541,40 @@ hipError_t reproject(hipStream_t st, int N, const float* staged, const FrameDev&
     // timing events (dsac_profile_enable): attached to the kernel's own dispatch (hipExtLaunchKernelGGL) instead of two event records on the
     // stream, which cost ~7 us of bubble each (one 640x480 frame: 100 us per step with them, 86 without)
     hipEvent_t evA = opts.ev_start, evB = opts.ev_stop;
+    // the form decision is taken from THIS frame (the one the launch reads), and reported: form + the reasons the exact form did not run
+    const bool split_ok = opts.split && pose_split_available(F);
+    const bool ex_variant = opts.variant == 84 || opts.variant == 85 || opts.variant == 89 || (opts.variant >= 93 && opts.variant <= 95);
+    int why = 0;
+    if (!(opts.flags & (K2_FLAG_EXACT | K2_FLAG_EXACT_ANY))) {
+        if (opts.variant >= 0 || (opts.flags & (K2_FLAG_PRECISE | K2_FLAG_RECLO | K2_FLAG_STORE_ONLY | (1 << 26)))) why |= K2_WHY_FORCED;
+        else if (!opts.exact_auto) why |= K2_WHY_AUTO_OFF;
+    } else if (opts.variant >= 0 && !ex_variant) why |= K2_WHY_FORCED;
+    if (!pose_split_available(F)) why |= K2_WHY_FOCAL;
+    if (!opts.poses64) why |= K2_WHY_NO_POSES;  // dsac_score_sampled without the cv poses: nothing to split
+    auto report = [&](int form) { if (opts.report) { opts.report[0] = form; opts.report[1] = (form == K2_FORM_EXACT_VEC || form == K2_FORM_EXACT_ANY) ? 0 : why; } };
     // An arithmetic form that was ASKED for (k2_flags bits 25 / 27 / 28) and cannot run on this map -- its kernels read 16-byte vectors: H*W % 4, aligned buffers
     // and, on the implicit grid, four cells of a lane in one row; the exact form also needs a focal length <= 2^10 -- is an error, not a silent fp32 launch
     // (a parity run must not measure the fast form unknowingly).  The auto policy's exact form simply falls back.
     if (opts.poses64 && (((opts.flags & K2_FLAG_PRECISE) && !(vec && (F.uv || F.W % 4 == 0))) || ((opts.flags & K2_FLAG_RECLO) && !vec) ||
-                         ((opts.flags & K2_FLAG_EXACT) && !(vec && opts.split))))
+                         ((opts.flags & K2_FLAG_EXACT) && !(vec && split_ok)) ||
+                         ((opts.flags & K2_FLAG_EXACT_ANY) && !(split_ok && (opts.variant < 0 || (ex_variant && vec))))))
         return hipErrorNotSupported;
+    // bit 29 (EXACT, any map) is what a parity run sets: besides the focal length only what would make it another form rules it out -- a k2_variant that names
+    // another form (the tile / tail trades 84 .. 95 exist in the vector build only), or a call without the cv poses the records are split from
+    if ((opts.flags & K2_FLAG_EXACT_ANY) && !opts.poses64) return hipErrorNotSupported;
     // the precise form (k2_flags bit 25): needs the cv poses themselves, 16-byte vectors and -- on the implicit grid -- four cells of a lane in one row
     if ((opts.flags & K2_FLAG_PRECISE) && opts.poses64 && vec && (F.uv || F.W % 4 == 0)) {
         const double nhp = (double)N * (double)F.P;
         const double kAd = (double)beta * 1.4426950408889634, kBd = -(double)beta * (double)tau * 1.4426950408889634;
         // hypothesis tile by size as the VALU forms: 32 for big launches, 16 for a single small frame (more workgroups)
         const int rec32 = (opts.flags >> 26) & 1;
+        report(K2_FORM_PRECISE);
         return nhp > 2.0e8 ? launch_reproject_prec<32>(st, N, opts.poses64, F, clampv, err, kAd, kBd, soft_part, tiles_used, Nf, evA, evB, rec32, opts.diag)
                            : launch_reproject_prec<16>(st, N, opts.poses64, F, clampv, err, kAd, kBd, soft_part, tiles_used, Nf, evA, evB, rec32, opts.diag);
     }
     // records in two pieces (k2_flags bit 27): the one-wave streaming form <64 hypotheses, 256 pixels> with the fp16 correction instructions, whatever the size
     if ((opts.flags & K2_FLAG_RECLO) && opts.staged_lo && vec && (opts.variant < 0 || (opts.variant >= 80 && opts.variant <= 83))) {
+        report(K2_FORM_RECLO);
 #define DSAC_LO(NG_, CH_, MW_) launch_reproject_st<NG_, CH_, 1, true, MW_, true>(st, N, staged, F, clampv, err, kA, kB, soft_part, tiles_used, Nf, kf | 32, evA, evB, opts.staged_lo)
         switch (opts.variant) {  // k2_variant 80..83 with the flag: the register / occupancy trades of this form (A/B); -1: the measured one
             case 80: return DSAC_LO(4, 4, 3);   // <64 hypotheses, 256 pixels>, 3 waves per SIMD (92 B of scratch)
@@ -1416,7 +1585,18 @@ hipError_t reproject(hipStream_t st, int N, const float* staged, const FrameDev&
 #undef DSAC_LO
     }
     // the exact-transform form (k2_flags bit 28, round 6): the one-wave streaming forms with the split records; k2_variant 84 / 89 / 93 = its tile / occupancy trades
-    if (k2_wants_exact(opts) && opts.split && vec && (opts.variant < 0 || (opts.variant == 84 || opts.variant == 85 || opts.variant == 89 || (opts.variant >= 93 && opts.variant <= 95)))) {
+    // Maps the vector build cannot read (H*W % 4, a buffer off the 16-byte grid) take the ANY build of the same kernel on the auto policy's tile for their
+    // size: the same arithmetic per cell, the same tile for the same P, so the two builds agree bit for bit on the same cells (but for groups that hold a hypothesis
+    // with clamped records, which only the ANY build sends through the fp32 transform: grp_far)
+    if (k2_wants_exact(opts) && split_ok && opts.variant < 0 && !vec) {
+        report(K2_FORM_EXACT_ANY);
+#define DSAC_EXA(NG_, CH_, MW_) launch_reproject_any<NG_, CH_, MW_>(st, N, staged, F, clampv, err, kA, kB, soft_part, tiles_used, Nf, kf | 32, evA, evB, opts.split)
+        if (F.P <= 16384) return DSAC_EXA(4, 1, 3);
+        return DSAC_EXA(4, 4, 2);
+#undef DSAC_EXA
+    }
+    if (k2_wants_exact(opts) && split_ok && vec && (opts.variant < 0 || ex_variant)) {
+        report(K2_FORM_EXACT_VEC);
 #define DSAC_EX(NG_, CH_, MW_, F_) launch_reproject_st<NG_, CH_, 1, true, MW_, false, F_>(st, N, staged, F, clampv, err, kA, kB, soft_part, tiles_used, Nf, kf | 32, evA, evB, nullptr, opts.split)
         switch (opts.variant) {
             // (85 .. 88: <64, 128 / 256> with a scheduling fence per m at three waves per SIMD, one / two / four waves per workgroup -- 44-480 B of scratch, 1.08-1.7 ms:
@@ -1438,6 +1618,7 @@ hipError_t reproject(hipStream_t st, int N, const float* staged, const FrameDev&
         }
 #undef DSAC_EX
     }
+    report((!vec || opts.variant < 0 ? !vec || !soft_part : opts.variant <= 13) ? K2_FORM_FP32_VALU : K2_FORM_FP32_MFMA);
     if (!vec) return launch_reproject<1, 32, false>(st, N, staged, F, clampv, err, kA, kB, soft_part, Nf, opts.pixel_minor, kf, evA, evB);
     const bool pm = opts.variant < 0 ? true : opts.pixel_minor;  // the auto policy's forms were all measured with pixel tiles innermost
 #define DSAC_VA(PX_, HT_, SP_) launch_reproject<PX_, HT_, SP_>(st, N, staged, F, clampv, err, kA, kB, soft_part, Nf, pm, kf, evA, evB)

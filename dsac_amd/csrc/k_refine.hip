@@ -968,6 +968,7 @@ static int scan_chunk_cells(int B, int P) {
 }
 // experiments: bits 0-7 problems per wave (1, 2, 4), bits 8-23 chunk cells, bit 24: no skip check  ("k6_scan_tune")
 void refine_scan_tune(int v) { g_scan_tune = v; }
+int refine_scan_tune_get() { return g_scan_tune; }
 // problems per wave: one up to 256 problems (19 200 light waves on a 640 x 480 map: 128 problems 36 us per step against 44 / 60 with two / four), four from
 // 512 problems of frames that hold a multiple of four (the cells then cross L2 -> L1 once per four problems: 16 frames x 128 3.20 -> 2.65 ms)
 static int scan_group(int B, int per_frame) {

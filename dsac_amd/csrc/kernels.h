@@ -46,14 +46,19 @@ struct K2Opts {
     const float* staged_lo = nullptr;  // per call: the low parts of the staged records (pose_prep_lo), for flags bit 27
     const void* split = nullptr;      // per call: the split fp16 records (pose_prep_split), for flags bit 28
     const double* poses64 = nullptr;  // per call: the cv poses (N x 6 doubles) the staged records were made from -- the precise form (flags bit 25) works from these
+    int* report = nullptr;            // per call: int[2] that receives the arithmetic form of the launch (K2_FORM_*) and why it is not the exact one (K2_WHY_*)
 };
 constexpr int K2_FLAG_RECLO = 1 << 27;    // k2_flags: pose records in two pieces -- the low parts through fp16 matrix-core instructions chained onto the fp32 ones
 constexpr int K2_FLAG_STORE_ONLY = 1 << 1;  // k2_flags: store schedule only (measurement)
 constexpr int K2_FLAG_EXACT = 1 << 28;    // k2_flags: exact transform -- split fp16 records through the fp16 matrix core, the camera-frame point rounded to float once (round 6)
 constexpr int K2_FLAG_PRECISE = 1 << 25;  // k2_flags: the fp64 projection of the reference (k_reproject_prec) instead of the fp32 matrix-core transform
-// does a K2 launch with these options want the split records?  (bit 28 asks for them; the auto policy wants them unless another arithmetic form or a measurement flag is set)
+constexpr int K2_FLAG_EXACT_ANY = 1 << 29;  // k2_flags: the exact transform on whatever build fits the map (vector or any-map); an error only where the focal length rules the split records out
+// what a launch computed with (dsac_get_option "k2_form_last"; the values of enum dsac_k2_form) and why it was not the exact form ("k2_form_why_last")
+enum { K2_FORM_NONE = 0, K2_FORM_FP32_VALU = 1, K2_FORM_FP32_MFMA = 2, K2_FORM_RECLO = 3, K2_FORM_EXACT_VEC = 4, K2_FORM_EXACT_ANY = 5, K2_FORM_PRECISE = 6 };
+enum { K2_WHY_AUTO_OFF = 1, K2_WHY_FORCED = 2, K2_WHY_FOCAL = 4, K2_WHY_NO_POSES = 8 };
+// does a K2 launch with these options want the split records?  (bits 28 / 29 ask for them; the auto policy wants them unless another arithmetic form or a measurement flag is set)
 inline bool k2_wants_exact(const K2Opts& o) {
-    if (o.flags & K2_FLAG_EXACT) return true;
+    if (o.flags & (K2_FLAG_EXACT | K2_FLAG_EXACT_ANY)) return true;
     return o.exact_auto && o.variant < 0 && !(o.flags & (K2_FLAG_PRECISE | K2_FLAG_RECLO | K2_FLAG_STORE_ONLY | (1 << 26)));
 }
 int reproject_num_pixel_tiles(int P);  // upper bound over both code paths
@@ -66,6 +71,9 @@ hipError_t reproject(hipStream_t st, int N, const float* staged, const FrameDev&
                      float* soft_part, const K2Opts& opts, int* tiles_used, int Nf = 0);
 // soft[h] = sum over pixel tiles of soft_part[tile][h]   (double, deterministic)
 hipError_t reduce_soft(hipStream_t st, int N, int tiles, const float* soft_part, double* soft);
+// what the exact form degrades on (dsac_k2_range_census): out[0] += 64-cell chunks of the frame(s) with a coordinate outside the split's range (split_B's
+// predicate: those chunks take the fp32 transform), out[1] += hypotheses whose split records clamp a piece or hold a non-finite entry.  One small kernel.
+hipError_t k2_range_census(hipStream_t st, int N, const double* poses, const FrameDev& F, unsigned long long* out2);
 // K3.
 // frames > 1: one independent softmax per consecutive group of N scores (outputs entropy[frames], avg6[frames][6])
 hipError_t softmax(hipStream_t st, int N, const double* scores, double scale, double* w, double* entropy, const double* poses, double* avg6,
@@ -164,6 +172,7 @@ hipError_t refine(hipStream_t st, int B, const double* init_poses, const int32_t
 // same results bit for bit.  refine_split_applies: >= 32 problems, >= 16 384 cells, no perturbation, no fused loss, "k6_waves" 0
 size_t refine_split_scratch_bytes(int B, int steps, int frames, int P, int max_inl);
 void refine_scan_tune(int v);  // experiments ("k6_scan_tune")
+int refine_scan_tune_get();   // the value last set
 bool refine_split_applies(int B, const FrameDev& F, const int32_t* pert_px_c, const double* loss_out4, int waves_per_problem);
 hipError_t refine_split(hipStream_t st, int B, const double* init_poses, const int32_t* perm, int steps, int max_inl, int min_inl, float thr, const FrameDev& F,
                         double* out_poses, int32_t* inlier_map, int32_t* steps_done, int map_stride, int per_frame, void* scratch, int exact_only = 0);

@@ -86,6 +86,25 @@ class Engine:
         """Per-context launch knob (dsac_set_option): k2_variant, k2_order, k2_flags, k1_wpb, k1_prio, k1_hpw, k1_horn, k4_variant, pi_defer_tail."""
         check(self._ctx, lib.dsac_set_option(self._ctx, str(key).encode(), int(value)))
 
+    def get_option(self, key):
+        """The current value of a launch knob (dsac_get_option), or of the read-only keys "k2_form_last" / "k2_form_why_last"."""
+        v = C.c_int()
+        check(self._ctx, lib.dsac_get_option(self._ctx, str(key).encode(), C.byref(v)))
+        return v.value
+
+    def k2_form(self):
+        """(name, why) of the last K2 launch this engine enqueued: name is one of capi.K2_FORMS, why is 0 when the exact form ran, else the
+        capi.DSAC_K2_WHY_* bits that kept it from running.  Host state only: no synchronisation."""
+        return capi.K2_FORMS[self.get_option("k2_form_last")], self.get_option("k2_form_why_last")
+
+    def k2_census(self, poses):
+        """(far_chunks, oor_poses) for the current frame(s) and these cv poses (N x 6): 64-cell chunks the exact K2 sends down its fp32 path because a
+        coordinate is outside the split's range, and hypotheses whose split records clamp a piece or hold a non-finite entry (dsac_k2_range_census)."""
+        poses = _np(poses, np.float64)
+        far, oor = C.c_longlong(), C.c_longlong()
+        check(self._ctx, lib.dsac_k2_range_census(self._ctx, int(poses.shape[0]), ptr(poses), C.byref(far), C.byref(oor)))
+        return far.value, oor.value
+
     def set_k2_events(self, wait_before=None, record_after=None):
         """Gate around the bandwidth-bound kernel (see dsac_set_k2_events).  Events: torch.cuda.Event or raw hipEvent_t."""
         def addr(ev):

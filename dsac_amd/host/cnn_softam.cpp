@@ -43,11 +43,17 @@ void Context::check(int rc, const char* what) {
 void Context::synchronize() { check(dsac_synchronize(ctx_), "dsac_synchronize"); }
 void Context::setOption(const char* key, int value) {
     check(dsac_set_option(ctx_, key, value), "dsac_set_option");
-    options_[key] = value;
 }
 int Context::option(const char* key, int unset) const {
-    const auto it = options_.find(key);
-    return it == options_.end() ? unset : it->second;
+    int v = unset;
+    return dsac_get_option(ctx_, key, &v) == DSAC_OK ? v : unset;
+}
+dsac_k2_form Context::k2FormLast(int* why) const {
+    int form = DSAC_K2_FORM_NONE, w = 0;
+    (void)dsac_get_option(ctx_, "k2_form_last", &form);
+    (void)dsac_get_option(ctx_, "k2_form_why_last", &w);
+    if (why) *why = w;
+    return static_cast<dsac_k2_form>(form);
 }
 void* Context::deviceAlloc(size_t bytes) { void* p = nullptr; check(dsac_device_alloc(ctx_, bytes, &p), "dsac_device_alloc"); return p; }
 void Context::deviceFree(void* p) noexcept { (void)dsac_device_free(ctx_, p); }

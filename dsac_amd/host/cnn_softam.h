@@ -23,7 +23,6 @@
 #pragma once
 #include <cstdint>
 #include <functional>
-#include <map>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -72,7 +71,9 @@ public:
     void forceInitRand(unsigned seed = 1305, int threads = 1) { check(dsac_refstream_init(ctx_, seed, threads), "dsac_refstream_init"); }
     void discardRand(int thread, unsigned long long outputs32) { check(dsac_refstream_discard(ctx_, thread, outputs32), "dsac_refstream_discard"); }
     void setOption(const char* key, int value);
-    int option(const char* key, int unset = 0) const;  // the value last given to setOption (the C ABI has no getter; scopes that change a knob restore it from here)
+    int option(const char* key, int unset = 0) const;  // the knob's current value, read through dsac_get_option (`unset` for a key the library does not know)
+    // the arithmetic form of the last K2 launch this context enqueued (dsac_get_option "k2_form_last"); *why: the DSAC_K2_WHY_* bits, 0 when the exact form ran
+    dsac_k2_form k2FormLast(int* why = nullptr) const;
     // HBM / page-locked host buffers and stream-ordered copies (dsac_device_alloc, dsac_host_alloc, dsac_copy_async)
     void* deviceAlloc(size_t bytes);
     void deviceFree(void* p) noexcept;
@@ -87,7 +88,6 @@ public:
 private:
     dsac_ctx* ctx_ = nullptr;
     const void* bound_ = nullptr;
-    std::map<std::string, int> options_;
 };
 
 // A typed buffer in HBM, freed with its owner.  upload / download are ordered on the context's stream; download() waits for the data.

@@ -108,12 +108,25 @@ DSAC_API int dsac_device_info(dsac_ctx* ctx, int* cus, int* clock_khz, uint64_t*
  *                 without a reciprocal of z (whose hardware approximation biases one hypothesis against another): e = n rsq(n z^2), n = (pu z - x)^2 + (pv z - y)^2
  *                 -- no cell above 1e-3 px over all cells of 256 x 640x480 (max 5.6e-4, mean 8.1e-6), softmax weights in a tie of unrelated hypotheses within
  *                 the stated 1e-4 (5.5e-5 .. 8.3e-5) at 1.03-1.05x the fast form's time in the same process (984-995 against 940-958 us; 0.64-0.65 of the HBM peak at the bench shape,
- *                 profiles/r06_k2_rsq_ab.txt; with reciprocal + Newton step + square root, k2_variant 84 / 93: 1 002-1 052; the precise mode: 1.85x).  Needs a map the vector kernels can read and a focal length
- *                 <= 1 024 px; coordinates beyond +-65.5 m take the fp32 transform chunk by chunk.  An arithmetic form that is ASKED for by bit 25 / 27 / 28 and
+ *                 profiles/r06_k2_rsq_ab.txt; with reciprocal + Newton step + square root, k2_variant 84 / 93: 1 002-1 052; the precise mode: 1.85x).  Bit 28 names the VECTOR build of
+ *                 this form: it needs a map the 16-byte vector kernels can read (H*W % 4 == 0, err / xyz / uv on 16-byte addresses) and a focal length
+ *                 <= 1 024 px; coordinates beyond +-65.5 m take the fp32 transform chunk by chunk.  An arithmetic form that is ASKED for by bit 25 / 27 / 28 / 29 and
  *                 cannot run on the frame is an error (round 6), never a silent launch of another form.  k2_variant 84 / 85 / 89 / 93 / 94 / 95 are its tile and tail trades.
- *   "k2_exact_auto"  1 (default since round 6): the auto policy (k2_variant -1, none of the bits 1 / 25 / 26 / 27 set) launches the exact-transform form wherever
- *                 it applies and falls back to the fp32 matrix-core forms where it does not -- the library's default K2 holds every stated tolerance; 0: the
- *                 fp32 forms of rounds 2-5 (DSAC_K2_EXACT_AUTO in the environment of dsac_create)
+ *                 bit 29 (0x20000000): EXACT, ANY MAP -- the same arithmetic on whatever build fits the map: the vector build where bit 28 would run, the any-map
+ *                 build of the same kernel elsewhere (any H*W, any 4-byte-aligned err / xyz / uv: 16-byte stores and position loads with dword alignment, the
+ *                 last 1-3 cells of a map with H*W % 4 != 0 in a small launch of their own; error images and partial sums of the two builds agree bit for bit on
+ *                 the same cells, with the one exception below).  An error where the focal length (> 1 024 px) rules the split records out, where k2_variant names
+ *                 another form (anything but -1 or, on a vector map, the vector build's trades 84 .. 95) and where the call carries no cv poses to split
+ *                 (dsac_score_sampled with poses == NULL): what a parity run sets so that it can never measure another form unknowingly.
+ *                 Hypotheses outside the records' range (a translation beyond 131 m in z or 2^27 / f mm in x / y -- small maps are where P3P returns them;
+ *                 dsac_k2_range_census counts them): the any-map build sends the group of 16 hypotheses that holds one through the fp32 transform, as
+ *                 chunks of far coordinates go in both builds; the vector build does NOT (its results are unchanged), so on a vector-readable map such a
+ *                 hypothesis still misses 1e-3 px, and those 16 rows differ between an aligned buffer and a slice of it
+ *   "k2_exact_auto"  1 (default since round 6): the auto policy (k2_variant -1, none of the bits 1 / 25 / 26 / 27 set) launches the exact-transform form on every
+ *                 frame with a focal length <= 1 024 px, whatever the shape of the map or the alignment of its buffers (the vector build or the any-map build,
+ *                 see bit 29) -- the library's default K2 holds every stated tolerance for poses inside the split records' range (see bit 29: on vector-readable maps a
+ *                 hypothesis with a translation beyond 131 m is outside it and the census is how to find one); the fp32 forms remain for focal lengths above 1 024 px (dsac_get_option
+ *                 "k2_form_last" tells); 0: the fp32 forms of rounds 2-5 (DSAC_K2_EXACT_AUTO in the environment of dsac_create)
  *   "k2_diag"     diagnostic switches of the precise form (bit 25): degrade ONE step at a time towards the fast forms' arithmetic (scripts/r06_k2_diag.py)
  *   "k6_walk_exact" 1: the scan of the two-launch refinement step (k_refine_walk, >= 32 problems on >= 16 384 cells) decides every cell by the reference's fp64
  *                 residual; 0 (default): an fp32 test with a proven error bound discards the cells that are certainly no inliers, the fp64 residual decides the
@@ -153,6 +166,29 @@ DSAC_API int dsac_device_info(dsac_ctx* ctx, int* cus, int* clock_khz, uint64_t*
  * The environment variables DSAC_K2_VARIANT, DSAC_K2_ORDER, DSAC_K2_FLAGS, DSAC_K1_WPB, DSAC_K1_PRIO, DSAC_K1_HPW, DSAC_K1_MINW, DSAC_K1_RL, DSAC_K1_WIDE, DSAC_K1_SHARE,
  * DSAC_K1_HORN, DSAC_K1_CUS, DSAC_K4_VARIANT, DSAC_TAIL_PRIO give the initial values at dsac_create. */
 DSAC_API int dsac_set_option(dsac_ctx* ctx, const char* key, int value);
+/* The current value of every key dsac_set_option accepts, and two read-only keys that describe the last K2 launch this context ENQUEUED (host state: no
+ * device access, no synchronisation):
+ *   "k2_form_last"      the arithmetic form of that launch, an enum dsac_k2_form (DSAC_K2_FORM_NONE before the first launch)
+ *   "k2_form_why_last"  0 when the exact form ran, else the DSAC_K2_WHY_* bits that kept it from running
+ * Unknown key, NULL context or NULL value: DSAC_ERR_INVALID. */
+typedef enum dsac_k2_form {
+    DSAC_K2_FORM_NONE = 0,      /* no K2 launch yet */
+    DSAC_K2_FORM_FP32_VALU = 1, /* fp32 transform on the vector ALU */
+    DSAC_K2_FORM_FP32_MFMA = 2, /* fp32 transform on the matrix core */
+    DSAC_K2_FORM_RECLO = 3,     /* pose records in two pieces (k2_flags bit 27) */
+    DSAC_K2_FORM_EXACT_VEC = 4, /* exact transform, vector build */
+    DSAC_K2_FORM_EXACT_ANY = 5, /* exact transform, any-map build */
+    DSAC_K2_FORM_PRECISE = 6    /* fp64 projection (k2_flags bit 25) */
+} dsac_k2_form;
+#define DSAC_K2_WHY_AUTO_OFF 1 /* "k2_exact_auto" is 0 */
+#define DSAC_K2_WHY_FORCED 2   /* another form forced by "k2_variant" / "k2_flags" */
+#define DSAC_K2_WHY_FOCAL 4    /* focal length above 1 024 px: no split records */
+#define DSAC_K2_WHY_NO_POSES 8 /* the call carried no cv poses to split (dsac_score_sampled with poses == NULL) */
+DSAC_API int dsac_get_option(dsac_ctx* ctx, const char* key, int* value);
+/* What the exact form degrades on, for the current frame(s) and these N cv poses (host or device pointer): *far_chunks = 64-cell chunks with a coordinate outside
+ * the split's range (|X| beyond ~65.5 m, NaN included), which the exact kernel sends down its fp32 path; *oor_poses = hypotheses whose split records clamp a piece
+ * (a translation beyond 2^17 mm in z, 2^27 / f mm in x / y) or hold a non-finite entry.  One small kernel, no state; synchronises like any call with host outputs. */
+DSAC_API int dsac_k2_range_census(dsac_ctx* ctx, int N, const double* poses, long long* far_chunks, long long* oor_poses);
 
 /* ---- device buffers for a host program that has no HIP toolchain --------------------------------------------- */
 /* The reference keeps every operand in host memory (cv::Mat: jp::img_coord_t estObj core/types.h:43-51, the hypothesis vectors of
