@@ -234,13 +234,14 @@ struct ProfScope {
         on = attached ? true : hipEventRecord(p.a, c->stream) == hipSuccess;
     }
     // the K2 options of this call: the context's, plus the event pair when this launch is sampled
-    dk::K2Opts k2(const double* poses64 = nullptr) const {
+    // F: the frame the launch reads (the slot's own frame in dsac_score_sampled, the current one everywhere else)
+    dk::K2Opts k2(const dk::FrameDev& F, const double* poses64 = nullptr) const {
         dk::K2Opts o = c->k2;
         if (on && attached) { o.ev_start = p.a; o.ev_stop = p.b; }
         o.report = c->k2_last;
         o.poses64 = poses64;  // the cv poses of this launch: what the precise form ("k2_flags" bit 25) projects with
         o.staged_lo = (poses64 && (o.flags & dk::K2_FLAG_RECLO)) ? c->staged_lo.as<float>() : nullptr;  // filled by k2_records_lo() before the launch
-        o.split = (poses64 && dk::k2_wants_exact(o) && dk::pose_split_available(c->F)) ? c->staged_split.as<char>() : nullptr;  // likewise
+        o.split = (poses64 && dk::k2_wants_exact(o) && dk::pose_split_available(F)) ? c->staged_split.as<char>() : nullptr;  // likewise
         return o;
     }
     void commit() { launched = true; }
@@ -253,18 +254,19 @@ struct ProfScope {
     }
 };
 
-// "k2_flags" bit 27: the low parts of the N staged records, derived from the cv poses on `st` right in front of the K2 launch that reads them
-static hipError_t k2_records_lo(dsac_ctx* c, hipStream_t st, int N, const double* d_poses) {
-    if (dk::k2_wants_exact(c->k2) && d_poses && N > 0 && dk::pose_split_available(c->F)) {  // the split records of the exact-transform form (the default; "k2_flags" bit 28)
+// "k2_flags" bit 27: the low parts of the N staged records, derived from the cv poses on `st` right in front of the K2 launch that reads them.
+// F is the frame of that launch: the records fold its fx, fy and split exponent, which in dsac_score_sampled are the slot's, not the current frame's
+static hipError_t k2_records_lo(dsac_ctx* c, hipStream_t st, int N, const double* d_poses, const dk::FrameDev& F) {
+    if (dk::k2_wants_exact(c->k2) && d_poses && N > 0 && dk::pose_split_available(F)) {  // the split records of the exact-transform form (the default; "k2_flags" bit 28)
         hipError_t e = c->staged_split.reserve(dk::pose_split_bytes(N));
         if (e != hipSuccess) return e;
-        e = dk::pose_prep_split(st, N, d_poses, c->F, c->staged_split.as<char>());
+        e = dk::pose_prep_split(st, N, d_poses, F, c->staged_split.as<char>());
         if (e != hipSuccess) return e;
     }
     if (!(c->k2.flags & dk::K2_FLAG_RECLO) || !d_poses || N <= 0) return hipSuccess;
     hipError_t e = c->staged_lo.reserve((size_t)N * dk::POSE_STRIDE * sizeof(float));
     if (e != hipSuccess) return e;
-    return dk::pose_prep_lo(st, N, d_poses, c->F, c->staged_lo.as<float>());
+    return dk::pose_prep_lo(st, N, d_poses, F, c->staged_lo.as<float>());
 }
 
 #define ARG_TRY(expr)                \
@@ -788,9 +790,9 @@ int dsac_reproject(dsac_ctx* c, int N, const double* poses, float clampv, float*
     int used = 0;
     if (c->k2_wait) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->k2_wait, 0));
     {
-        HIP_TRY(c, k2_records_lo(c, c->stream, N, d_poses));
+        HIP_TRY(c, k2_records_lo(c, c->stream, N, d_poses, c->F));
         ProfScope ps(c, 0, true);
-        HIP_TRY(c, dk::reproject(c->stream, N, c->staged.as<float>(), c->F, clampv, d_err, tau, beta, d_part, ps.k2(d_poses), &used, Nf));
+        HIP_TRY(c, dk::reproject(c->stream, N, c->staged.as<float>(), c->F, clampv, d_err, tau, beta, d_part, ps.k2(c->F, d_poses), &used, Nf));
         ps.commit();
     }
     if (c->k2_record) HIP_TRY(c, hipEventRecord(c->k2_record, c->stream));
@@ -889,9 +891,9 @@ static int score_hypotheses_common(dsac_ctx* c, int N, int Nf, uint64_t seed, co
         if (c->k2_wait) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->k2_wait, 0));
         hipEvent_t k2_done = nullptr;
         {
-            HIP_TRY(c, k2_records_lo(c, c->stream, N, d_poses));
+            HIP_TRY(c, k2_records_lo(c, c->stream, N, d_poses, c->F));
             ProfScope ps(c, 0, true);
-            dk::K2Opts o = ps.k2(d_poses);
+            dk::K2Opts o = ps.k2(c->F, d_poses);
             if (!o.ev_stop) o.ev_stop = c->pi_k2done;  // the tail's start rides on K2's own dispatch packet: no record between K2 and the next K1
             k2_done = o.ev_stop;
             HIP_TRY(c, dk::reproject(c->stream, N, c->staged.as<float>(), c->F, clampv, d_err, tau, beta, part.as<float>(), o, &used_d, Nf));
@@ -915,9 +917,9 @@ static int score_hypotheses_common(dsac_ctx* c, int N, int Nf, uint64_t seed, co
     int used = 0;
     if (c->k2_wait) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->k2_wait, 0));
     {
-        HIP_TRY(c, k2_records_lo(c, c->stream, N, d_poses));
+        HIP_TRY(c, k2_records_lo(c, c->stream, N, d_poses, c->F));
         ProfScope ps(c, 0, true);
-        HIP_TRY(c, dk::reproject(c->stream, N, c->staged.as<float>(), c->F, clampv, d_err, tau, beta, c->soft_part.as<float>(), ps.k2(d_poses), &used, Nf));
+        HIP_TRY(c, dk::reproject(c->stream, N, c->staged.as<float>(), c->F, clampv, d_err, tau, beta, c->soft_part.as<float>(), ps.k2(c->F, d_poses), &used, Nf));
         ps.commit();
     }
     if (c->k2_record) HIP_TRY(c, hipEventRecord(c->k2_record, c->stream));
@@ -1027,9 +1029,9 @@ int dsac_score_sampled(dsac_ctx* c, int slot, float clampv, float tau, float bet
     if (c->slot_reduced_recorded[slot]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->slot_reduced[slot], 0));  // partials of frame i-2 consumed
     int used = 0;
     {
-        HIP_TRY(c, k2_records_lo(c, c->stream, N, poses));
+        HIP_TRY(c, k2_records_lo(c, c->stream, N, poses, SF));
         ProfScope ps(c, 0, true);
-        HIP_TRY(c, dk::reproject(c->stream, N, c->slot_staged[slot].as<float>(), SF, clampv, err_or_null, tau, beta, part, ps.k2(poses), &used, Nf));
+        HIP_TRY(c, dk::reproject(c->stream, N, c->slot_staged[slot].as<float>(), SF, clampv, err_or_null, tau, beta, part, ps.k2(SF, poses), &used, Nf));
         ps.commit();
     }
     HIP_TRY(c, hipEventRecord(c->slot_free[slot], c->stream));
@@ -2027,9 +2029,9 @@ int dsac_process_images(dsac_ctx* c, int hyps_per_frame, uint64_t seed, float th
     // 18.6 us from the end of K2 to the start of the next K1 with the record and the wait below, profiles/r04_rank_timeline_mode2.txt)
     hipEvent_t k2_done = nullptr;
     {
-        HIP_TRY(c, k2_records_lo(c, c->stream, N, d_poses));
+        HIP_TRY(c, k2_records_lo(c, c->stream, N, d_poses, c->F));
         ProfScope ps(c, 0, true);
-        dk::K2Opts o = ps.k2(d_poses);
+        dk::K2Opts o = ps.k2(c->F, d_poses);
         if (mode == 2) {
             if (!o.ev_stop) o.ev_stop = c->pi_k2done;
             k2_done = o.ev_stop;
@@ -2115,9 +2117,9 @@ int dsac_process_images_begin(dsac_ctx* c, int hyps_per_frame, uint64_t seed, fl
     int used = 0;
     if (c->k2_wait) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->k2_wait, 0));
     {
-        HIP_TRY(c, k2_records_lo(c, c->stream, N, d_poses));
+        HIP_TRY(c, k2_records_lo(c, c->stream, N, d_poses, c->F));
         ProfScope ps(c, 0, true);
-        HIP_TRY(c, dk::reproject(c->stream, N, c->staged.as<float>(), c->F, clampv, d_err, tau, beta, d_part, ps.k2(d_poses), &used, Nf));
+        HIP_TRY(c, dk::reproject(c->stream, N, c->staged.as<float>(), c->F, clampv, d_err, tau, beta, d_part, ps.k2(c->F, d_poses), &used, Nf));
         ps.commit();
     }
     if (c->k2_record) HIP_TRY(c, hipEventRecord(c->k2_record, c->stream));

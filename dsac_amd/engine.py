@@ -420,7 +420,8 @@ class Engine:
                                                ptr(poses), ptr(sets_out), ptr(ok)))
 
     def scoreSampled(self, slot, poses, scores, w, ent=None, avg=None, err=None, clamp=CNN_OBJ_MAXINPUT, tau=10.0, beta=0.5, scale=0.1):
-        """K2 -> K3 for the hypotheses sampled into `slot` (device buffers only), see dsac_score_sampled."""
+        """K2 -> K3 for the hypotheses sampled into `slot` (device buffers only), see dsac_score_sampled.  The slot is scored against the frame it
+        was sampled from -- its coordinates, pixel positions, intrinsics and map geometry --, not the frame that is current now."""
         check(self._ctx, lib.dsac_score_sampled(self._ctx, int(slot), float(clamp), float(tau), float(beta), float(scale), ptr(poses), ptr(err),
                                                 ptr(scores), ptr(w), ptr(ent), ptr(avg)))
 

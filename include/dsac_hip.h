@@ -344,6 +344,9 @@ DSAC_API int dsac_score_hypotheses(dsac_ctx* ctx, int N, uint64_t seed, const in
  * (the library orders the slot's next dsac_sample_ahead behind the readers of its previous use), and dsac_synchronize
  * waits for all streams.  A slot remembers the frame that was current when it was sampled and is scored against that frame, so
  * a stream of different frames is pipelined by calling dsac_set_frame(..., DSAC_FRAME_BORROW) before each dsac_sample_ahead;
+ * "that frame" is everything dsac_set_frame(s) took: the coordinates and pixel positions, the intrinsics (fx, fy, cx, cy) and
+ * the map geometry (H, W, frame count, strides) -- the records K2 reads, the form it runs in and what "k2_form_last" reports
+ * follow the slot's frame, whatever frame is current at score time (tests/test_gpu_pipelined_frames.py);
  * frames the library copies itself (no DSAC_FRAME_BORROW) cannot be replaced while a slot is sampled but not yet scored
  * (DSAC_ERR_INVALID).  Each slot alternates strictly: sample_ahead, score_sampled, sample_ahead, ... */
 DSAC_API int dsac_sample_ahead(dsac_ctx* ctx, int slot, int N, uint64_t seed, const int32_t* sets_or_null, float thr, int max_tries, double* poses,

@@ -315,7 +315,9 @@ def test_pipeline_streams_different_frames_without_syncs(engine, synth):
     """The steady-state loop of the pipelined pair over a stream of DIFFERENT frames (DSAC_FRAME_BORROW before each dsac_sample_ahead),
     no synchronisation until the end: every step must give the bits of the fused call on its own frame.  Per-slot pose buffers are
     reused every second step, so K1 of step i+2 may only start once the K3 tail of step i has read them (the soft-argmax average),
-    and a slot must be scored against the frame it was sampled from, not the one current at score time."""
+    and a slot must be scored against the frame it was sampled from, not the one current at score time.  All frames here share one camera and one map
+    geometry, so this pins the slot's COORDINATES only; frames whose intrinsics, map size, pixel positions or frame count change between steps, and the
+    comparison of every step's error images with the oracle, are in tests/test_gpu_pipelined_frames.py."""
     import torch
     dev = torch.device("cuda", 0)
     H, W, N, S = 480, 640, 256, 7
