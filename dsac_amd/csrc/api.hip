@@ -233,17 +233,6 @@ struct ProfScope {
         else if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return;
         on = attached ? true : hipEventRecord(p.a, c->stream) == hipSuccess;
     }
-    // the K2 options of this call: the context's, plus the event pair when this launch is sampled
-    // F: the frame the launch reads (the slot's own frame in dsac_score_sampled, the current one everywhere else)
-    dk::K2Opts k2(const dk::FrameDev& F, const double* poses64 = nullptr) const {
-        dk::K2Opts o = c->k2;
-        if (on && attached) { o.ev_start = p.a; o.ev_stop = p.b; }
-        o.report = c->k2_last;
-        o.poses64 = poses64;  // the cv poses of this launch: what the precise form ("k2_flags" bit 25) projects with
-        o.staged_lo = (poses64 && (o.flags & dk::K2_FLAG_RECLO)) ? c->staged_lo.as<float>() : nullptr;  // filled by k2_records_lo() before the launch
-        o.split = (poses64 && dk::k2_wants_exact(o) && dk::pose_split_available(F)) ? c->staged_split.as<char>() : nullptr;  // likewise
-        return o;
-    }
     void commit() { launched = true; }
     ~ProfScope() {
         if (!on) return;
@@ -254,26 +243,87 @@ struct ProfScope {
     }
 };
 
-// "k2_flags" bit 27: the low parts of the N staged records, derived from the cv poses on `st` right in front of the K2 launch that reads them.
-// F is the frame of that launch: the records fold its fx, fy and split exponent, which in dsac_score_sampled are the slot's, not the current frame's
-static hipError_t k2_records_lo(dsac_ctx* c, hipStream_t st, int N, const double* d_poses, const dk::FrameDev& F) {
-    if (dk::k2_wants_exact(c->k2) && d_poses && N > 0 && dk::pose_split_available(F)) {  // the split records of the exact-transform form (the default; "k2_flags" bit 28)
-        hipError_t e = c->staged_split.reserve(dk::pose_split_bytes(N));
-        if (e != hipSuccess) return e;
-        e = dk::pose_prep_split(st, N, d_poses, F, c->staged_split.as<char>());
-        if (e != hipSuccess) return e;
-    }
-    if (!(c->k2.flags & dk::K2_FLAG_RECLO) || !d_poses || N <= 0) return hipSuccess;
-    hipError_t e = c->staged_lo.reserve((size_t)N * dk::POSE_STRIDE * sizeof(float));
-    if (e != hipSuccess) return e;
-    return dk::pose_prep_lo(st, N, d_poses, F, c->staged_lo.as<float>());
-}
-
 #define ARG_TRY(expr)                \
     do {                             \
         int rc__ = (expr);           \
         if (rc__ != DSAC_OK) return rc__; \
     } while (0)
+
+// The K2 stage: the one place a K2 launch is assembled.  Everything the launch is handed follows from one decision taken here -- from the context's options,
+// the cv poses (NULL only in dsac_score_sampled: nothing to split, the fp32 form on K1's records) and F, the frame the launch READS (the slot's own frame in
+// dsac_score_sampled, the current one everywhere else): the records fold its fx, fy and split exponent.  Records that are wanted are built on `st` right in
+// front of the launch and handed to it; records that are not wanted are neither.
+//   gated: the launch sits between the context's k2_wait / k2_record events (dsac_set_k2_events)
+//   fallback_stop: the stop event of the launch when profiling attaches no pair to it (the deferred score tails start behind it); *done receives the event
+//   that completes with K2 -- the pair's stop event, else fallback_stop
+// A launch that reproject() refuses (unknown variant, hipErrorNotSupported) records no k2_record, and its event pair goes back to the free list.
+int k2_stage(dsac_ctx* c, hipStream_t st, int N, int Nf, const float* staged, const dk::FrameDev& F, const double* poses, float clampv, float tau, float beta,
+             float* err, float* part, bool gated, hipEvent_t fallback_stop, int* tiles_used, hipEvent_t* done = nullptr) {
+    if (gated && c->k2_wait) HIP_TRY(c, hipStreamWaitEvent(st, c->k2_wait, 0));
+    const bool split = poses && dk::k2_wants_exact(c->k2) && dk::pose_split_available(F);  // the exact-transform form (the default; "k2_flags" bit 28)
+    const bool lo = poses && (c->k2.flags & dk::K2_FLAG_RECLO);                            // "k2_flags" bit 27: the low parts of the staged records
+    if (split) {
+        HIP_TRY(c, c->staged_split.reserve(dk::pose_split_bytes(N)));
+        HIP_TRY(c, dk::pose_prep_split(st, N, poses, F, c->staged_split.as<char>()));
+    }
+    if (lo) {
+        HIP_TRY(c, c->staged_lo.reserve((size_t)N * dk::POSE_STRIDE * sizeof(float)));
+        HIP_TRY(c, dk::pose_prep_lo(st, N, poses, F, c->staged_lo.as<float>()));
+    }
+    ProfScope ps(c, 0, true);
+    dk::K2Opts o = c->k2;
+    o.split = split ? c->staged_split.as<char>() : nullptr;
+    o.staged_lo = lo ? c->staged_lo.as<float>() : nullptr;
+    o.poses64 = poses;  // what the precise form ("k2_flags" bit 25) projects with
+    o.report = c->k2_last;
+    if (ps.on) { o.ev_start = ps.p.a; o.ev_stop = ps.p.b; }
+    else o.ev_stop = fallback_stop;
+    if (done) *done = o.ev_stop;
+    HIP_TRY(c, dk::reproject(st, N, staged, F, clampv, err, tau, beta, part, o, tiles_used, Nf));
+    ps.commit();
+    if (gated && c->k2_record) HIP_TRY(c, hipEventRecord(c->k2_record, st));
+    return DSAC_OK;
+}
+
+// Error images only on a big launch: the streaming form WITH the sigmoid arithmetic is the faster kernel -- the arithmetic spaces a wave's stores
+// (N = 4096: 860 us against 890-900 for any form without it; idling the wave instead, k2_flags bits 16-23, does not reproduce the effect:
+// profiles/r04_k2_err_ab.txt).  So the auto policy runs that kernel and drops its partial sums (1200 x N floats of scratch, 0.4 % of the
+// stores; no reduction launch).  k2_flags bit 24 switches the policy off (A/B).
+// *part: the context's buffer for the per-tile sums when the caller wants them (want_soft) or the policy applies, else NULL; tau / beta: any finite
+// sigmoid when the policy applies and the caller gave none (the sums are not used).
+int k2_soft_part(dsac_ctx* c, int N, bool want_err, bool want_soft, float* tau, float* beta, float** part) {
+    const bool fused_for_err = !want_soft && want_err && c->k2.variant < 0 && !(c->k2.flags & (1 << 24)) && (double)N * (double)c->F.P * 4.0 > 1.0e9;
+    *part = nullptr;
+    if (want_soft || fused_for_err) {
+        HIP_TRY(c, c->soft_part.reserve((size_t)dk::reproject_num_pixel_tiles(c->F.P) * N * sizeof(float)));
+        *part = c->soft_part.as<float>();
+    }
+    if (fused_for_err && !(*beta > 0.f)) { *tau = 10.f; *beta = 0.5f; }
+    return DSAC_OK;
+}
+
+// The scores array of a scoring call whose caller gave none: the parity's own buffer when the score tail is deferred (it outlives the call), else a staging slot.
+int scores_scratch(dsac_ctx* c, bool deferred, int b, int N, double** d_scores) {
+    DevBuf& s = deferred ? c->pi_scores[b] : next_slot(c);
+    HIP_TRY(c, s.reserve((size_t)N * sizeof(double)));
+    *d_scores = s.as<double>();
+    return DSAC_OK;
+}
+
+// The deferred score tail ("pi_defer_tail" 2) of call parity b on tail stream tk, behind the event that completes with K2.  This tail does not depend on the
+// previous call's (different arrays: the mode's contract); it follows the tail of the call two back, whose arrays it may have been given again -- in stream
+// order, or through that stream's completion event when the two used different streams.
+int pi_score_tail(dsac_ctx* c, int b, int tk, hipEvent_t k2_done, int Nf, int frames, int tiles, const float* part, double* scores, double scale, double* w,
+                  double* ent, const double* poses, double* avg) {
+    hipStream_t ts = c->tail[tk];
+    if (c->pi_tail_of[b] >= 0 && c->pi_tail_of[b] != tk) HIP_TRY(c, hipStreamWaitEvent(ts, c->tail_done[c->pi_tail_of[b]], 0));
+    c->pi_tail_of[b] = tk;
+    HIP_TRY(c, hipStreamWaitEvent(ts, k2_done, 0));
+    HIP_TRY(c, score_tail(ts, Nf, frames, tiles, part, scores, scale, w, ent, poses, avg));
+    HIP_TRY(c, hipEventRecord(c->pi_scored[b], ts));
+    c->pi_scored_rec[b] = true;
+    return DSAC_OK;
+}
 
 // The enqueue-only chain of dsac_sample_refstream_frames for the frames of c->F on the context's stream (also K1 of dsac_process_images with
 // "pi_refstream").  The generators, the window scratch and the counters are touched on that stream only, so calls order themselves; the scratch is sized
@@ -776,26 +826,9 @@ int dsac_reproject(dsac_ctx* c, int N, const double* poses, float clampv, float*
     HIP_TRY(c, c->staged.reserve((size_t)N * dk::POSE_STRIDE * sizeof(float)));
     HIP_TRY(c, dk::pose_prep(c->stream, N, d_poses, c->F, c->staged.as<float>()));
     float* d_part = nullptr;
-    const int tiles = dk::reproject_num_pixel_tiles(c->F.P);
-    // Error images only on a big launch: the streaming form WITH the sigmoid arithmetic is the faster kernel -- the arithmetic spaces a wave's stores
-    // (N = 4096: 860 us against 890-900 for any form without it; idling the wave instead, k2_flags bits 16-23, does not reproduce the effect:
-    // profiles/r04_k2_err_ab.txt).  So the auto policy runs that kernel and drops its partial sums (1200 x N floats of scratch, 0.4 % of the
-    // stores; no reduction launch).  k2_flags bit 24 switches the policy off (A/B).
-    const bool fused_for_err = !d_soft && d_err && c->k2.variant < 0 && !(c->k2.flags & (1 << 24)) && (double)N * (double)P * 4.0 > 1.0e9;
-    if (d_soft || fused_for_err) {
-        HIP_TRY(c, c->soft_part.reserve((size_t)tiles * N * sizeof(float)));
-        d_part = c->soft_part.as<float>();
-    }
-    if (fused_for_err && !(beta > 0.f)) { tau = 10.f; beta = 0.5f; }  // any finite sigmoid; the sums are not used
+    ARG_TRY(k2_soft_part(c, N, d_err != nullptr, d_soft != nullptr, &tau, &beta, &d_part));
     int used = 0;
-    if (c->k2_wait) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->k2_wait, 0));
-    {
-        HIP_TRY(c, k2_records_lo(c, c->stream, N, d_poses, c->F));
-        ProfScope ps(c, 0, true);
-        HIP_TRY(c, dk::reproject(c->stream, N, c->staged.as<float>(), c->F, clampv, d_err, tau, beta, d_part, ps.k2(c->F, d_poses), &used, Nf));
-        ps.commit();
-    }
-    if (c->k2_record) HIP_TRY(c, hipEventRecord(c->k2_record, c->stream));
+    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, d_part, /*gated=*/true, nullptr, &used));
     if (d_soft) HIP_TRY(c, dk::reduce_soft(c->stream, N, used, d_part, d_soft));
     return end_call(c);
 }
@@ -868,16 +901,7 @@ static int score_hypotheses_common(dsac_ctx* c, int N, int Nf, uint64_t seed, co
     if (want_defer && !defer) join_tail(c);
     const int b = defer ? (int)(c->pi_calls++ & 1u) : 0;
     if (defer) c->pi_open = false;
-    if (!d_scores) {
-        if (defer) {
-            HIP_TRY(c, c->pi_scores[b].reserve((size_t)N * sizeof(double)));
-            d_scores = c->pi_scores[b].as<double>();
-        } else {
-            DevBuf& s = next_slot(c);
-            HIP_TRY(c, s.reserve((size_t)N * sizeof(double)));
-            d_scores = s.as<double>();
-        }
-    }
+    if (!d_scores) ARG_TRY(scores_scratch(c, defer, b, N, &d_scores));
     const int tiles = dk::reproject_num_pixel_tiles(c->F.P);
     HIP_TRY(c, c->staged.reserve((size_t)N * dk::POSE_STRIDE * sizeof(float)));
     if (defer) {
@@ -888,26 +912,13 @@ static int score_hypotheses_common(dsac_ctx* c, int N, int Nf, uint64_t seed, co
         if (c->pi_scored_rec[b]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->pi_scored[b], 0));  // K3 of the call two back read this half's arrays
         HIP_TRY(c, dk::sample(c->stream, N, seed, nullptr, c->F, (int)thr, max_tries, d_poses, d_sets_out, d_ok, c->staged.as<float>(), Nf, c->k1));
         int used_d = 0;
-        if (c->k2_wait) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->k2_wait, 0));
         hipEvent_t k2_done = nullptr;
-        {
-            HIP_TRY(c, k2_records_lo(c, c->stream, N, d_poses, c->F));
-            ProfScope ps(c, 0, true);
-            dk::K2Opts o = ps.k2(c->F, d_poses);
-            if (!o.ev_stop) o.ev_stop = c->pi_k2done;  // the tail's start rides on K2's own dispatch packet: no record between K2 and the next K1
-            k2_done = o.ev_stop;
-            HIP_TRY(c, dk::reproject(c->stream, N, c->staged.as<float>(), c->F, clampv, d_err, tau, beta, part.as<float>(), o, &used_d, Nf));
-            ps.commit();
-        }
-        if (c->k2_record) HIP_TRY(c, hipEventRecord(c->k2_record, c->stream));
-        hipStream_t ts = c->tail[tk];
-        if (c->pi_tail_of[b] >= 0 && c->pi_tail_of[b] != tk) HIP_TRY(c, hipStreamWaitEvent(ts, c->tail_done[c->pi_tail_of[b]], 0));
-        c->pi_tail_of[b] = tk;
-        HIP_TRY(c, hipStreamWaitEvent(ts, k2_done, 0));
-        HIP_TRY(c, score_tail(ts, Nf > 0 ? Nf : N, frames, used_d, part.as<float>(), d_scores, scale, d_w, d_ent, avg6_or_null ? d_poses : nullptr, d_avg));
-        HIP_TRY(c, hipEventRecord(c->pi_scored[b], ts));
-        c->pi_scored_rec[b] = true;
-        HIP_TRY(c, hipEventRecord(c->tail_done[tk], ts));
+        // the tail's start rides on K2's own dispatch packet (pi_k2done as its stop event): no record between K2 and the next K1
+        ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, part.as<float>(), /*gated=*/true, c->pi_k2done,
+                         &used_d, &k2_done));
+        ARG_TRY(pi_score_tail(c, b, tk, k2_done, Nf > 0 ? Nf : N, frames, used_d, part.as<float>(), d_scores, scale, d_w, d_ent, avg6_or_null ? d_poses : nullptr,
+                              d_avg));
+        HIP_TRY(c, hipEventRecord(c->tail_done[tk], c->tail[tk]));
         c->tail_pending[tk] = true;
         return DSAC_OK;
     }
@@ -915,14 +926,7 @@ static int score_hypotheses_common(dsac_ctx* c, int N, int Nf, uint64_t seed, co
     // K1 writes the poses AND their staged K2 records (no separate pose_prep launch)
     HIP_TRY(c, dk::sample(c->stream, N, seed, d_sets_in, c->F, (int)thr, max_tries, d_poses, d_sets_out, d_ok, c->staged.as<float>(), Nf, c->k1));
     int used = 0;
-    if (c->k2_wait) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->k2_wait, 0));
-    {
-        HIP_TRY(c, k2_records_lo(c, c->stream, N, d_poses, c->F));
-        ProfScope ps(c, 0, true);
-        HIP_TRY(c, dk::reproject(c->stream, N, c->staged.as<float>(), c->F, clampv, d_err, tau, beta, c->soft_part.as<float>(), ps.k2(c->F, d_poses), &used, Nf));
-        ps.commit();
-    }
-    if (c->k2_record) HIP_TRY(c, hipEventRecord(c->k2_record, c->stream));
+    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, c->soft_part.as<float>(), /*gated=*/true, nullptr, &used));
     HIP_TRY(c, score_tail(c->stream, Nf > 0 ? Nf : N, frames, used, c->soft_part.as<float>(), d_scores, scale, d_w, d_ent, avg6_or_null ? d_poses : nullptr,
                           d_avg));
     return end_call(c);
@@ -1028,12 +1032,8 @@ int dsac_score_sampled(dsac_ctx* c, int slot, float clampv, float tau, float bet
     HIP_TRY(c, hipStreamWaitEvent(c->stream, c->slot_ready[slot], 0));  // normally long satisfied: K1 ran under the previous K2
     if (c->slot_reduced_recorded[slot]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->slot_reduced[slot], 0));  // partials of frame i-2 consumed
     int used = 0;
-    {
-        HIP_TRY(c, k2_records_lo(c, c->stream, N, poses, SF));
-        ProfScope ps(c, 0, true);
-        HIP_TRY(c, dk::reproject(c->stream, N, c->slot_staged[slot].as<float>(), SF, clampv, err_or_null, tau, beta, part, ps.k2(SF, poses), &used, Nf));
-        ps.commit();
-    }
+    // the slot's own frame and records; no k2_wait / k2_record gate around this launch (dsac_set_k2_events)
+    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->slot_staged[slot].as<float>(), SF, poses, clampv, tau, beta, err_or_null, part, /*gated=*/false, nullptr, &used));
     HIP_TRY(c, hipEventRecord(c->slot_free[slot], c->stream));
     c->slot_free_recorded[slot] = true;
     c->slot_pending[slot] = false;
@@ -1998,16 +1998,7 @@ int dsac_process_images(dsac_ctx* c, int hyps_per_frame, uint64_t seed, float th
     const bool defer = mode != 0;
     const int b = (int)(c->pi_calls++ & 1u);
     c->pi_open = false;  // a begin without its finish is abandoned by a whole call
-    if (!d_scores) {
-        if (mode == 2) {
-            HIP_TRY(c, c->pi_scores[b].reserve((size_t)N * sizeof(double)));
-            d_scores = c->pi_scores[b].as<double>();
-        } else {
-            DevBuf& s = next_slot(c);
-            HIP_TRY(c, s.reserve((size_t)N * sizeof(double)));
-            d_scores = s.as<double>();
-        }
-    }
+    if (!d_scores) ARG_TRY(scores_scratch(c, mode == 2, b, N, &d_scores));
     const int tiles = dk::reproject_num_pixel_tiles(c->F.P);
     DevBuf& part = mode == 2 ? c->pi_soft[b] : c->soft_part;
     HIP_TRY(c, c->staged.reserve((size_t)N * dk::POSE_STRIDE * sizeof(float)));
@@ -2023,34 +2014,16 @@ int dsac_process_images(dsac_ctx* c, int hyps_per_frame, uint64_t seed, float th
     if (c->pi_refstream) ARG_TRY(pi_refstream_k1(c, "dsac_process_images", hyps_per_frame, thr, d_poses, d_sets, d_ok));
     else HIP_TRY(c, dk::sample(c->stream, N, seed, nullptr, c->F, (int)thr, max_tries, d_poses, d_sets, d_ok, c->staged.as<float>(), Nf, c->k1));
     int used = 0;
-    if (c->k2_wait) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->k2_wait, 0));
     // mode 2: the tail starts behind K2.  The event it waits for rides on K2's own dispatch packet (hipExtLaunchKernelGGL's stop event) -- an event
     // RECORD between K2 and the next call's K1 is a packet of its own and a ~7 us bubble on the stream that bounds the loop (rank step of configs[3]:
     // 18.6 us from the end of K2 to the start of the next K1 with the record and the wait below, profiles/r04_rank_timeline_mode2.txt)
     hipEvent_t k2_done = nullptr;
-    {
-        HIP_TRY(c, k2_records_lo(c, c->stream, N, d_poses, c->F));
-        ProfScope ps(c, 0, true);
-        dk::K2Opts o = ps.k2(c->F, d_poses);
-        if (mode == 2) {
-            if (!o.ev_stop) o.ev_stop = c->pi_k2done;
-            k2_done = o.ev_stop;
-        }
-        HIP_TRY(c, dk::reproject(c->stream, N, c->staged.as<float>(), c->F, clampv, d_err, tau, beta, part.as<float>(), o, &used, Nf));
-        ps.commit();
-    }
-    if (c->k2_record) HIP_TRY(c, hipEventRecord(c->k2_record, c->stream));
+    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, part.as<float>(), /*gated=*/true,
+                     mode == 2 ? c->pi_k2done : nullptr, &used, &k2_done));
     hipStream_t ts = c->stream;
     if (mode == 2) {
-        // this tail does not depend on the previous call's (different arrays: the mode's contract); it follows the tail of the call two back, whose
-        // arrays it may have been given again -- in stream order, or through that stream's completion event when the two used different streams
         ts = c->tail[tk];
-        if (c->pi_tail_of[b] >= 0 && c->pi_tail_of[b] != tk) HIP_TRY(c, hipStreamWaitEvent(ts, c->tail_done[c->pi_tail_of[b]], 0));
-        c->pi_tail_of[b] = tk;
-        HIP_TRY(c, hipStreamWaitEvent(ts, k2_done, 0));
-        HIP_TRY(c, score_tail(ts, hyps_per_frame, frames, used, part.as<float>(), d_scores, scale, d_w, d_ent, d_poses, d_avg));
-        HIP_TRY(c, hipEventRecord(c->pi_scored[b], ts));
-        c->pi_scored_rec[b] = true;
+        ARG_TRY(pi_score_tail(c, b, tk, k2_done, hyps_per_frame, frames, used, part.as<float>(), d_scores, scale, d_w, d_ent, d_poses, d_avg));
     } else {
         HIP_TRY(c, dk::reduce_soft(c->stream, N, used, part.as<float>(), d_scores));
         // the previous call's tail reads the soft-argmax poses that K3 is about to overwrite.  After a batch it finished long ago (K1 and K2 ran since);
@@ -2101,28 +2074,14 @@ int dsac_process_images_begin(dsac_ctx* c, int hyps_per_frame, uint64_t seed, fl
     c->pi_open = true; c->pi_open_b = b; c->pi_open_N = hyps_per_frame; c->pi_open_frames = frames;
     // "pi_defer_tail" 2: K3 of the call two back (same half of the caller's alternating arrays) read the poses K1 is about to overwrite
     if (c->pi_defer_tail == 2 && c->pi_scored_rec[b]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->pi_scored[b], 0));
-    const int tiles = dk::reproject_num_pixel_tiles(c->F.P);
     HIP_TRY(c, c->staged.reserve((size_t)N * dk::POSE_STRIDE * sizeof(float)));
-    // the per-tile sums are reduced in stream order below, so the context's one buffer serves every call.  Error images only on a big launch still take
-    // the kernel form with the sigmoid arithmetic (dsac_reproject: it is the faster store schedule) and drop the sums
-    const bool fused_for_err = !d_soft && c->k2.variant < 0 && !(c->k2.flags & (1 << 24)) && (double)N * (double)P * 4.0 > 1.0e9;
+    // the per-tile sums are reduced in stream order below, so the context's one buffer serves every call
     float* d_part = nullptr;
-    if (d_soft || fused_for_err) {
-        HIP_TRY(c, c->soft_part.reserve((size_t)tiles * N * sizeof(float)));
-        d_part = c->soft_part.as<float>();
-    }
-    if (fused_for_err && !(beta > 0.f)) { tau = 10.f; beta = 0.5f; }
+    ARG_TRY(k2_soft_part(c, N, d_err != nullptr, d_soft != nullptr, &tau, &beta, &d_part));
     if (c->pi_refstream) ARG_TRY(pi_refstream_k1(c, "dsac_process_images_begin", hyps_per_frame, thr, d_poses, d_sets, d_ok));
     else HIP_TRY(c, dk::sample(c->stream, N, seed, nullptr, c->F, (int)thr, max_tries, d_poses, d_sets, d_ok, c->staged.as<float>(), Nf, c->k1));
     int used = 0;
-    if (c->k2_wait) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->k2_wait, 0));
-    {
-        HIP_TRY(c, k2_records_lo(c, c->stream, N, d_poses, c->F));
-        ProfScope ps(c, 0, true);
-        HIP_TRY(c, dk::reproject(c->stream, N, c->staged.as<float>(), c->F, clampv, d_err, tau, beta, d_part, ps.k2(c->F, d_poses), &used, Nf));
-        ps.commit();
-    }
-    if (c->k2_record) HIP_TRY(c, hipEventRecord(c->k2_record, c->stream));
+    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, d_part, /*gated=*/true, nullptr, &used));
     if (d_soft) HIP_TRY(c, dk::reduce_soft(c->stream, N, used, d_part, d_soft));
     return end_call(c);
 }

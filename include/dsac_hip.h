@@ -572,7 +572,10 @@ DSAC_API int dsac_backward_path1(dsac_ctx* ctx, int N, const double* poses, cons
  * `wait_before` (a hipEvent_t; a never-recorded event does not block), after it `record_after` is recorded.
  * Two contexts working on alternate frames cross-wire their events so that their K2 launches run back to back
  * -- never competing for HBM -- while the latency-bound kernels (K1 sampling, K3) of one frame fill the bubbles of
- * the other.  NULL removes the gate. */
+ * the other.  NULL removes the gate.
+ * The gate surrounds the K2 launch of dsac_reproject, dsac_score_hypotheses / dsac_score_hypotheses_frames (with and without a deferred
+ * score tail), dsac_process_images and dsac_process_images_begin.  It does NOT surround the K2 launch of dsac_score_sampled: the
+ * pipelined pair orders its launches with its own per-slot events.  A K2 launch that is refused (an error return) records nothing. */
 DSAC_API int dsac_set_k2_events(dsac_ctx* ctx, void* wait_before_or_null, void* record_after_or_null);
 
 /* ---- measurement hooks (bench.py's roofline leg) ----------------------------------------------------- */
