@@ -153,7 +153,10 @@ DM_INLINE float residual_f(const double R[9], const double t[3], const Cam& K, f
     float u, v;
     project_f(R, t, K, X, Y, Z, u, v);
     const float dx = pu - u, dy = pv - v;
-    return (float)fmin(sqrt((double)dx * dx + (double)dy * dy), clampv);
+    // std::min(norm, clamp) as the reference writes it: a NaN norm (a NaN coordinate; an infinite one, whose projection is inf x 0) stays NaN and is below no
+    // threshold.  fmin returns the clamp for it, which turned such cells into inliers of every threshold above the clamp.
+    const double d = sqrt((double)dx * dx + (double)dy * dy);
+    return (float)((clampv < d) ? clampv : d);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -573,7 +573,14 @@ static inline bool solve_linear(const double* A, const double* b, double* x, int
     return true;
 }
 
-struct LMStats { int iters; int evals; double err0; double err; };
+// Statistics of one solve (bookkeeping only: no operation of the solver depends on them).
+//   rejected        trials whose error grew and whose lambda was multiplied by 10
+//   max_lambda_lg10 the largest exponent lambdaLg10 took (17 when a rejection would have taken lambda past 1e16)
+//   forced          1 when that trial was accepted although its error grew (CvLevMarq's ceiling)
+//   min_margin      the smallest |errNorm - prevErrNorm| / prevErrNorm over the accept/reject decisions taken while the trial's relative
+//                   parameter change was still above 1e-6 (decisions on the converged plateau are at rounding level by nature and move the
+//                   pose by nothing); DBL_MAX when there was no such decision
+struct LMStats { int iters; int evals; double err0; double err; int rejected; int max_lambda_lg10; int forced; double min_margin; };
 
 static inline bool solve_pnp_iterative_guess(int n, const float* X, const float* uv, const Cam& K, double* rvec, double* tvec,
                                              LMStats* stats = nullptr, int max_iter = 20, double eps = FLT_EPSILON) {
@@ -583,6 +590,13 @@ static inline bool solve_pnp_iterative_guess(int n, const float* X, const float*
     double JtJ[36], JtErr[6];
     int lambdaLg10 = -3, iters = 0, evals = 0;
     double prevErrNorm = DBL_MAX, errNorm = 0;
+    int st_rejected = 0, st_max_lg10 = lambdaLg10, st_forced = 0;
+    double st_min_margin = DBL_MAX;
+    auto rel_change = [&]() {
+        double num = 0, den = 0;
+        for (int i = 0; i < 6; i++) { num += (param[i] - prev[i]) * (param[i] - prev[i]); den += prev[i] * prev[i]; }
+        return std::sqrt(num) / (std::sqrt(den) + DBL_EPSILON);
+    };
     auto residual = [&](const double* p, bool withJ) {
         project_points(n, X, p, p + 3, K, nullptr, proj.data(), withJ ? dpdr.data() : nullptr, withJ ? dpdt.data() : nullptr);
         double s = 0;
@@ -630,8 +644,12 @@ static inline bool solve_pnp_iterative_guess(int n, const float* X, const float*
         // CHECK_ERR loop
         for (;;) {
             errNorm = residual(param, false);
+            if (stats && rel_change() > 1e-6) st_min_margin = std::min(st_min_margin, std::fabs(errNorm - prevErrNorm) / prevErrNorm);
             if (errNorm > prevErrNorm) {
-                if (++lambdaLg10 <= 16) { step(); continue; }
+                ++lambdaLg10;
+                st_max_lg10 = std::max(st_max_lg10, lambdaLg10);
+                if (lambdaLg10 <= 16) { st_rejected++; step(); continue; }
+                st_forced = 1;
             }
             lambdaLg10 = std::max(lambdaLg10 - 1, -16);
             double num = 0, den = 0;
@@ -644,7 +662,10 @@ static inline bool solve_pnp_iterative_guess(int n, const float* X, const float*
         }
     }
     for (int i = 0; i < 3; i++) { rvec[i] = param[i]; tvec[i] = param[3 + i]; }
-    if (stats) { stats->iters = iters; stats->evals = evals; stats->err = errNorm; }
+    if (stats) {
+        stats->iters = iters; stats->evals = evals; stats->err = errNorm;
+        stats->rejected = st_rejected; stats->max_lambda_lg10 = st_max_lg10; stats->forced = st_forced; stats->min_margin = st_min_margin;
+    }
     return true;
 }
 

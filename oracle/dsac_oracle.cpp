@@ -465,12 +465,14 @@ int orc_solve_p3p(const float* X4, const float* uv4, const double* cam, double* 
     Cam K{cam[0], cam[1], cam[2], cam[3]};
     return safe_p3p(X4, uv4, K, pose6) ? 1 : 0;
 }
-int orc_solve_pnp_iterative(int n, const float* X, const float* uv, const double* cam, double* pose6, int* iters, double* err) {
+// lm4_or_null: {rejected trials, largest lambdaLg10, forced accept at the ceiling (0 / 1), smallest decision margin} of cvl::LMStats
+int orc_solve_pnp_iterative(int n, const float* X, const float* uv, const double* cam, double* pose6, int* iters, double* err, double* lm4_or_null) {
     Cam K{cam[0], cam[1], cam[2], cam[3]};
     cvl::LMStats st{};
     cvl::solve_pnp_iterative_guess(n, X, uv, K, pose6, pose6 + 3, &st);
     if (iters) *iters = st.iters;
     if (err) { err[0] = st.err0; err[1] = st.err; }
+    if (lm4_or_null) { lm4_or_null[0] = st.rejected; lm4_or_null[1] = st.max_lambda_lg10; lm4_or_null[2] = st.forced; lm4_or_null[3] = st.min_margin; }
     return 1;
 }
 

@@ -179,15 +179,22 @@ def solve_p3p(X4, uv4, cam):
     return bool(ok), pose
 
 
-def solve_pnp_iterative(X, uv, cam, pose6):
+def solve_pnp_iterative(X, uv, cam, pose6, stats=False):
+    """Returns (pose, iterations, [err0, err]); with stats also cvl::LMStats as a dict: iters, rejected (trials), max_lambda_lg10 (17: a rejection
+    would have passed the ceiling), forced (accept at the ceiling), min_margin (smallest relative error margin of an accept/reject decision taken
+    while the trial still moved the parameters by more than 1e-6; inf when there was none)."""
     X, Xp = _f(np.asarray(X).reshape(-1, 3))
     uv, up = _f(np.asarray(uv).reshape(-1, 2))
     cam, cp = _cam(cam)
     pose = np.array(pose6, dtype=np.float64).copy()
     it = C.c_int(0)
     err = np.zeros(2)
-    lib().orc_solve_pnp_iterative(X.shape[0], Xp, up, cp, pose.ctypes.data_as(c_dp), C.byref(it), err.ctypes.data_as(c_dp))
-    return pose, it.value, err
+    lm = np.zeros(4)
+    lib().orc_solve_pnp_iterative(X.shape[0], Xp, up, cp, pose.ctypes.data_as(c_dp), C.byref(it), err.ctypes.data_as(c_dp), lm.ctypes.data_as(c_dp))
+    if not stats:
+        return pose, it.value, err
+    return pose, it.value, err, dict(iters=it.value, rejected=int(lm[0]), max_lambda_lg10=int(lm[1]), forced=bool(lm[2]),
+                                     min_margin=float(lm[3]) if lm[3] < 1e300 else float("inf"))
 
 
 # ---- reference functions --------------------------------------------------------------------------

@@ -5,6 +5,11 @@ libm-vs-ocml last bits, the summation order of the normal equations and the 6x6 
   refined poses : 1e-7 relative          inlier maps / step counts : identical
   dRefineHyp/Obj: central differences divide LM outputs by 2e-3 / 4, so 1e-4 relative to the largest entry
   loss, dLossMax: 1e-9
+
+Every refinement here starts next to the right pose at thr = 10: about three accepted LM iterations per call and hardly a rejected trial.  The hard
+branches of lm_pnp belong to tests/test_gpu_refine_lm.py (problems from tests/lm_corpus.py, labelled and judged stable by the oracle alone): rejected trials
+and the state restored after them, 15 and more rejections in one call, lambda at 1e0 and above, the forced accept at the lambda ceiling, the 20-iteration
+cap, the zero step for a damped matrix that is not positive definite, and bit equality of k_refine<1, 2, 4, 8> and k_refine_walk + k_refine_lm on them.
 """
 import numpy as np
 import pytest
