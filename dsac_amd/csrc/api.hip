@@ -209,6 +209,20 @@ int out_arg(dsac_ctx* c, T* p, size_t count, T** out, bool preload = false) {
     return DSAC_OK;
 }
 
+// The error images of a K2 call as an output argument: floats, or IEEE binary16 (dk::K2_ELEM_F16) carried as 16-bit words.
+int err_out_arg(dsac_ctx* c, void* p, int elem, size_t count, void** out) {
+    if (elem == dk::K2_ELEM_F16) {
+        uint16_t* d = nullptr;
+        const int rc = out_arg(c, static_cast<uint16_t*>(p), count, &d);
+        *out = d;
+        return rc;
+    }
+    float* d = nullptr;
+    const int rc = out_arg(c, static_cast<float*>(p), count, &d);
+    *out = d;
+    return rc;
+}
+
 // End a call: copy pending host outputs back (synchronous only when there are any).
 int end_call(dsac_ctx* c) {
     if (c->pending.empty()) return DSAC_OK;
@@ -253,12 +267,14 @@ struct ProfScope {
 // the cv poses (NULL only in dsac_score_sampled: nothing to split, the fp32 form on K1's records) and F, the frame the launch READS (the slot's own frame in
 // dsac_score_sampled, the current one everywhere else): the records fold its fx, fy and split exponent.  Records that are wanted are built on `st` right in
 // front of the launch and handed to it; records that are not wanted are neither.
+//   err, elem: the error images and their element type -- dk::K2_ELEM_F32 (float) or dk::K2_ELEM_F16 (IEEE binary16: dsac_reproject_f16 /
+//   dsac_process_images_begin_f16, which have checked k2_f16_check before anything was enqueued; only the auto policy's exact vector build stores halves)
 //   gated: the launch sits between the context's k2_wait / k2_record events (dsac_set_k2_events)
 //   fallback_stop: the stop event of the launch when profiling attaches no pair to it (the deferred score tails start behind it); *done receives the event
 //   that completes with K2 -- the pair's stop event, else fallback_stop
 // A launch that reproject() refuses (unknown variant, hipErrorNotSupported) records no k2_record, and its event pair goes back to the free list.
 int k2_stage(dsac_ctx* c, hipStream_t st, int N, int Nf, const float* staged, const dk::FrameDev& F, const double* poses, float clampv, float tau, float beta,
-             float* err, float* part, bool gated, hipEvent_t fallback_stop, int* tiles_used, hipEvent_t* done = nullptr) {
+             void* err, int elem, float* part, bool gated, hipEvent_t fallback_stop, int* tiles_used, hipEvent_t* done = nullptr) {
     if (gated && c->k2_wait) HIP_TRY(c, hipStreamWaitEvent(st, c->k2_wait, 0));
     const bool split = poses && dk::k2_wants_exact(c->k2) && dk::pose_split_available(F);  // the exact-transform form (the default; "k2_flags" bit 28)
     const bool lo = poses && (c->k2.flags & dk::K2_FLAG_RECLO);                            // "k2_flags" bit 27: the low parts of the staged records
@@ -276,10 +292,11 @@ int k2_stage(dsac_ctx* c, hipStream_t st, int N, int Nf, const float* staged, co
     o.staged_lo = lo ? c->staged_lo.as<float>() : nullptr;
     o.poses64 = poses;  // what the precise form ("k2_flags" bit 25) projects with
     o.report = c->k2_last;
+    o.err_elem = elem;
     if (ps.on) { o.ev_start = ps.p.a; o.ev_stop = ps.p.b; }
     else o.ev_stop = fallback_stop;
     if (done) *done = o.ev_stop;
-    HIP_TRY(c, dk::reproject(st, N, staged, F, clampv, err, tau, beta, part, o, tiles_used, Nf));
+    HIP_TRY(c, dk::reproject(st, N, staged, F, clampv, static_cast<float*>(err), tau, beta, part, o, tiles_used, Nf));
     ps.commit();
     if (gated && c->k2_record) HIP_TRY(c, hipEventRecord(c->k2_record, st));
     return DSAC_OK;
@@ -299,6 +316,26 @@ int k2_soft_part(dsac_ctx* c, int N, bool want_err, bool want_soft, float* tau, 
         *part = c->soft_part.as<float>();
     }
     if (fused_for_err && !(*beta > 0.f)) { *tau = 10.f; *beta = 0.5f; }
+    return DSAC_OK;
+}
+
+// Half error images (dsac_reproject_f16, dsac_process_images_begin_f16) exist for the default arithmetic only: the exact-transform vector build.  Every condition is
+// checked here, before the call enqueues anything, and refused by name -- never a silent launch of another form, and "k2_form_last" keeps its value.
+int k2_f16_check(dsac_ctx* c, const char* who, const void* err16) {
+    const dk::FrameDev& F = c->F;
+    if (!err16) return fail(c, DSAC_ERR_INVALID, "%s: err16 must be non-NULL", who);
+    if (F.P % 8 != 0) return fail(c, DSAC_ERR_INVALID, "%s: half error images need H*W %% 8 == 0, this map has %d x %d = %d cells", who, F.H, F.W, F.P);
+    if (reinterpret_cast<uintptr_t>(err16) & 15) return fail(c, DSAC_ERR_INVALID, "%s: err16 (%p) must be on a 16-byte address", who, err16);
+    if ((reinterpret_cast<uintptr_t>(F.xyz) & 15) || (reinterpret_cast<uintptr_t>(F.uv) & 15))
+        return fail(c, DSAC_ERR_INVALID, "%s: half error images need the frame's xyz (%p) and uv (%p) on 16-byte addresses", who, (const void*)F.xyz, (const void*)F.uv);
+    if (!dk::pose_split_available(F))
+        return fail(c, DSAC_ERR_INVALID, "%s: half error images need a focal length <= 1024 px (the exact-transform form), got fx = %g, fy = %g", who, F.fx, F.fy);
+    if (c->k2.variant != -1) return fail(c, DSAC_ERR_INVALID, "%s: half error images need k2_variant -1 (the auto policy's tiles), it is %d", who, c->k2.variant);
+    const int ex_bits = dk::K2_FLAG_EXACT | dk::K2_FLAG_EXACT_ANY;
+    if (c->k2.flags & ~ex_bits)
+        return fail(c, DSAC_ERR_INVALID, "%s: half error images exist for the exact-transform form only: k2_flags 0x%x sets bits other than 28 / 29", who, c->k2.flags);
+    if (!c->k2.exact_auto && !(c->k2.flags & ex_bits))
+        return fail(c, DSAC_ERR_INVALID, "%s: half error images need the exact-transform form: k2_exact_auto is 0 and neither k2_flags bit 28 nor 29 is set", who);
     return DSAC_OK;
 }
 
@@ -805,32 +842,43 @@ int dsac_sample_refstream_frames(dsac_ctx* c, int hyps_per_frame, float thr, lon
     return end_call(c);
 }
 
-int dsac_reproject(dsac_ctx* c, int N, const double* poses, float clampv, float* err_or_null, float tau, float beta, double* soft_or_null) {
-    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_reproject: ctx is NULL");
-    if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "dsac_reproject: no frame set");
+// dsac_reproject and dsac_reproject_f16: one body, the element type of the error images (dk::K2_ELEM_*) travels to the K2 stage
+static int reproject_call(dsac_ctx* c, const char* who, int N, const double* poses, float clampv, void* err_or_null, int elem, float tau, float beta,
+                          double* soft_or_null) {
+    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "%s: ctx is NULL", who);
+    if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "%s: no frame set", who);
     // frame batch: N = frames x hypotheses per frame (a multiple of 128: no hypothesis tile of K2 straddles two frames), hypothesis h scores frame h / Nf
     const int Nf = c->F.frames > 1 ? N / c->F.frames : 0;
     if (c->F.frames > 1 && (N % c->F.frames != 0 || Nf % dk::K2_NF_MULTIPLE != 0))
-        return fail(c, DSAC_ERR_INVALID, "dsac_reproject: with a frame batch N must be frames x (a multiple of %d), got %d for %d frames", dk::K2_NF_MULTIPLE, N, c->F.frames);
-    if (N < 0 || !poses) return fail(c, DSAC_ERR_INVALID, "dsac_reproject: N >= 0 and poses must be non-NULL");
+        return fail(c, DSAC_ERR_INVALID, "%s: with a frame batch N must be frames x (a multiple of %d), got %d for %d frames", who, dk::K2_NF_MULTIPLE, N, c->F.frames);
+    if (N < 0 || !poses) return fail(c, DSAC_ERR_INVALID, "%s: N >= 0 and poses must be non-NULL", who);
+    if (elem == dk::K2_ELEM_F16) ARG_TRY(k2_f16_check(c, who, err_or_null));  // before anything is enqueued
     if (N == 0 || (!err_or_null && !soft_or_null)) return DSAC_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c);
     const size_t P = (size_t)c->F.P;
     const double* d_poses;
-    float* d_err;
+    void* d_err;
     double* d_soft;
     ARG_TRY(in_arg(c, poses, (size_t)N * 6, &d_poses));
-    ARG_TRY(out_arg(c, err_or_null, (size_t)N * P, &d_err));
+    ARG_TRY(err_out_arg(c, err_or_null, elem, (size_t)N * P, &d_err));
     ARG_TRY(out_arg(c, soft_or_null, (size_t)N, &d_soft));
     HIP_TRY(c, c->staged.reserve((size_t)N * dk::POSE_STRIDE * sizeof(float)));
     HIP_TRY(c, dk::pose_prep(c->stream, N, d_poses, c->F, c->staged.as<float>()));
     float* d_part = nullptr;
     ARG_TRY(k2_soft_part(c, N, d_err != nullptr, d_soft != nullptr, &tau, &beta, &d_part));
     int used = 0;
-    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, d_part, /*gated=*/true, nullptr, &used));
+    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, elem, d_part, /*gated=*/true, nullptr, &used));
     if (d_soft) HIP_TRY(c, dk::reduce_soft(c->stream, N, used, d_part, d_soft));
     return end_call(c);
+}
+
+int dsac_reproject(dsac_ctx* c, int N, const double* poses, float clampv, float* err_or_null, float tau, float beta, double* soft_or_null) {
+    return reproject_call(c, "dsac_reproject", N, poses, clampv, err_or_null, dk::K2_ELEM_F32, tau, beta, soft_or_null);
+}
+
+int dsac_reproject_f16(dsac_ctx* c, int N, const double* poses, float clampv, uint16_t* err16, float tau, float beta, double* soft_or_null) {
+    return reproject_call(c, "dsac_reproject_f16", N, poses, clampv, err16, dk::K2_ELEM_F16, tau, beta, soft_or_null);
 }
 
 static int softmax_common(dsac_ctx* c, const char* who, int frames, int N, const double* scores, double scale, double* w, double* entropy_or_null,
@@ -914,7 +962,7 @@ static int score_hypotheses_common(dsac_ctx* c, int N, int Nf, uint64_t seed, co
         int used_d = 0;
         hipEvent_t k2_done = nullptr;
         // the tail's start rides on K2's own dispatch packet (pi_k2done as its stop event): no record between K2 and the next K1
-        ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, part.as<float>(), /*gated=*/true, c->pi_k2done,
+        ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, dk::K2_ELEM_F32, part.as<float>(), /*gated=*/true, c->pi_k2done,
                          &used_d, &k2_done));
         ARG_TRY(pi_score_tail(c, b, tk, k2_done, Nf > 0 ? Nf : N, frames, used_d, part.as<float>(), d_scores, scale, d_w, d_ent, avg6_or_null ? d_poses : nullptr,
                               d_avg));
@@ -926,7 +974,7 @@ static int score_hypotheses_common(dsac_ctx* c, int N, int Nf, uint64_t seed, co
     // K1 writes the poses AND their staged K2 records (no separate pose_prep launch)
     HIP_TRY(c, dk::sample(c->stream, N, seed, d_sets_in, c->F, (int)thr, max_tries, d_poses, d_sets_out, d_ok, c->staged.as<float>(), Nf, c->k1));
     int used = 0;
-    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, c->soft_part.as<float>(), /*gated=*/true, nullptr, &used));
+    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, dk::K2_ELEM_F32, c->soft_part.as<float>(), /*gated=*/true, nullptr, &used));
     HIP_TRY(c, score_tail(c->stream, Nf > 0 ? Nf : N, frames, used, c->soft_part.as<float>(), d_scores, scale, d_w, d_ent, avg6_or_null ? d_poses : nullptr,
                           d_avg));
     return end_call(c);
@@ -1033,7 +1081,7 @@ int dsac_score_sampled(dsac_ctx* c, int slot, float clampv, float tau, float bet
     if (c->slot_reduced_recorded[slot]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->slot_reduced[slot], 0));  // partials of frame i-2 consumed
     int used = 0;
     // the slot's own frame and records; no k2_wait / k2_record gate around this launch (dsac_set_k2_events)
-    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->slot_staged[slot].as<float>(), SF, poses, clampv, tau, beta, err_or_null, part, /*gated=*/false, nullptr, &used));
+    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->slot_staged[slot].as<float>(), SF, poses, clampv, tau, beta, err_or_null, dk::K2_ELEM_F32, part, /*gated=*/false, nullptr, &used));
     HIP_TRY(c, hipEventRecord(c->slot_free[slot], c->stream));
     c->slot_free_recorded[slot] = true;
     c->slot_pending[slot] = false;
@@ -1075,6 +1123,10 @@ int dsac_set_option(dsac_ctx* c, const char* key, int value) {
     else if (k == "k2_flags") c->k2.flags = value;
     else if (k == "k2_diag") c->k2.diag = value;
     else if (k == "k2_exact_auto") c->k2.exact_auto = value != 0;
+    else if (k == "k2_f16_store") {
+        if (value != 0 && value != 1) return fail(c, DSAC_ERR_INVALID, "dsac_set_option: k2_f16_store is 0 (8-byte stores) or 1 (16-byte stores after a lane exchange)");
+        c->k2.f16_store = value;
+    }
     else if (k == "k6_walk_exact") c->k6_walk_exact = value != 0;
     else if (k == "k6_scan_tune") {  // A/B of the scan (process-wide): problems per wave | chunk cells << 8 | no skip check << 24
         const int g = value & 255, chunk = (value >> 8) & 0xffff;
@@ -1148,6 +1200,7 @@ int dsac_get_option(dsac_ctx* c, const char* key, int* value) {
     else if (k == "k2_flags") *value = c->k2.flags;
     else if (k == "k2_diag") *value = c->k2.diag;
     else if (k == "k2_exact_auto") *value = c->k2.exact_auto ? 1 : 0;
+    else if (k == "k2_f16_store") *value = c->k2.f16_store;
     else if (k == "k6_walk_exact") *value = c->k6_walk_exact;
     else if (k == "k6_scan_tune") *value = dk::refine_scan_tune_get();
     else if (k == "k6_waves") *value = c->k6_waves;
@@ -2018,7 +2071,7 @@ int dsac_process_images(dsac_ctx* c, int hyps_per_frame, uint64_t seed, float th
     // RECORD between K2 and the next call's K1 is a packet of its own and a ~7 us bubble on the stream that bounds the loop (rank step of configs[3]:
     // 18.6 us from the end of K2 to the start of the next K1 with the record and the wait below, profiles/r04_rank_timeline_mode2.txt)
     hipEvent_t k2_done = nullptr;
-    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, part.as<float>(), /*gated=*/true,
+    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, dk::K2_ELEM_F32, part.as<float>(), /*gated=*/true,
                      mode == 2 ? c->pi_k2done : nullptr, &used, &k2_done));
     hipStream_t ts = c->stream;
     if (mode == 2) {
@@ -2044,19 +2097,21 @@ int dsac_process_images(dsac_ctx* c, int hyps_per_frame, uint64_t seed, float th
 // core/cnn_softam.h:1066-1078 is  getDiffMap x N -> forward(diffMaps) -> softMax : begin leaves the error images of every frame in HBM, the caller's
 // score model (the reference's score CNN; any device code on the context's stream) turns them into frames x hyps_per_frame scores, finish continues
 // with K3 -> K6 -> K7.  The deferral modes of dsac_process_images apply to the pair (the tails start in finish).
-int dsac_process_images_begin(dsac_ctx* c, int hyps_per_frame, uint64_t seed, float thr, int max_tries, float clampv, float tau, float beta, double* poses,
-                              int32_t* sets_out, uint8_t* ok, float* err, double* soft_or_null) {
-    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_process_images_begin: ctx is NULL");
-    if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "dsac_process_images_begin: no frame set");
+// dsac_process_images_begin and dsac_process_images_begin_f16: one body, the element type of the error images (dk::K2_ELEM_*) travels to the K2 stage
+static int pi_begin_call(dsac_ctx* c, const char* who, int hyps_per_frame, uint64_t seed, float thr, int max_tries, float clampv, float tau, float beta, double* poses,
+                         int32_t* sets_out, uint8_t* ok, void* err, int elem, double* soft_or_null) {
+    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "%s: ctx is NULL", who);
+    if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "%s: no frame set", who);
     const int frames = c->F.frames > 1 ? c->F.frames : 1;
     if (hyps_per_frame <= 0 || (frames > 1 && hyps_per_frame % dk::K2_NF_MULTIPLE != 0))
-        return fail(c, DSAC_ERR_INVALID, "dsac_process_images_begin: hyps_per_frame must be positive (a multiple of %d for a frame batch), got %d", dk::K2_NF_MULTIPLE,
+        return fail(c, DSAC_ERR_INVALID, "%s: hyps_per_frame must be positive (a multiple of %d for a frame batch), got %d", who, dk::K2_NF_MULTIPLE,
                     hyps_per_frame);
-    if ((long long)hyps_per_frame * frames > (1ll << 24)) return fail(c, DSAC_ERR_INVALID, "dsac_process_images_begin: too many hypotheses");
+    if ((long long)hyps_per_frame * frames > (1ll << 24)) return fail(c, DSAC_ERR_INVALID, "%s: too many hypotheses", who);
     if (!poses || !sets_out || !ok || (!err && !soft_or_null))
-        return fail(c, DSAC_ERR_INVALID, "dsac_process_images_begin: poses / sets_out / ok and at least one of err / soft must be non-NULL");
-    if (max_tries <= 0 || c->F.P < 4) return fail(c, DSAC_ERR_INVALID, "dsac_process_images_begin: max_tries > 0 and a frame of at least 4 cells needed");
-    if (c->pi_refstream) ARG_TRY(pi_refstream_check(c, "dsac_process_images_begin (pi_refstream)", hyps_per_frame));  // before anything is enqueued
+        return fail(c, DSAC_ERR_INVALID, "%s: poses / sets_out / ok and at least one of err / soft must be non-NULL", who);
+    if (max_tries <= 0 || c->F.P < 4) return fail(c, DSAC_ERR_INVALID, "%s: max_tries > 0 and a frame of at least 4 cells needed", who);
+    if (elem == dk::K2_ELEM_F16) ARG_TRY(k2_f16_check(c, who, err));  // before anything is enqueued
+    if (c->pi_refstream) ARG_TRY(pi_refstream_check(c, (std::string(who) + " (pi_refstream)").c_str(), hyps_per_frame));  // before anything is enqueued
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c, /*keep_tail=*/c->pi_defer_tail != 0);
     const size_t P = (size_t)c->F.P;
@@ -2064,11 +2119,11 @@ int dsac_process_images_begin(dsac_ctx* c, int hyps_per_frame, uint64_t seed, fl
     double *d_poses, *d_soft;
     int32_t* d_sets;
     uint8_t* d_ok;
-    float* d_err;
+    void* d_err;
     ARG_TRY(out_arg(c, poses, (size_t)N * 6, &d_poses));
     ARG_TRY(out_arg(c, sets_out, (size_t)N * 4, &d_sets));
     ARG_TRY(out_arg(c, ok, (size_t)N, &d_ok));
-    ARG_TRY(out_arg(c, err, (size_t)N * P, &d_err));
+    ARG_TRY(err_out_arg(c, err, elem, (size_t)N * P, &d_err));
     ARG_TRY(out_arg(c, soft_or_null, (size_t)N, &d_soft));
     const int b = (int)(c->pi_calls++ & 1u);
     c->pi_open = true; c->pi_open_b = b; c->pi_open_N = hyps_per_frame; c->pi_open_frames = frames;
@@ -2078,12 +2133,23 @@ int dsac_process_images_begin(dsac_ctx* c, int hyps_per_frame, uint64_t seed, fl
     // the per-tile sums are reduced in stream order below, so the context's one buffer serves every call
     float* d_part = nullptr;
     ARG_TRY(k2_soft_part(c, N, d_err != nullptr, d_soft != nullptr, &tau, &beta, &d_part));
-    if (c->pi_refstream) ARG_TRY(pi_refstream_k1(c, "dsac_process_images_begin", hyps_per_frame, thr, d_poses, d_sets, d_ok));
+    if (c->pi_refstream) ARG_TRY(pi_refstream_k1(c, who, hyps_per_frame, thr, d_poses, d_sets, d_ok));
     else HIP_TRY(c, dk::sample(c->stream, N, seed, nullptr, c->F, (int)thr, max_tries, d_poses, d_sets, d_ok, c->staged.as<float>(), Nf, c->k1));
     int used = 0;
-    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, d_part, /*gated=*/true, nullptr, &used));
+    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, elem, d_part, /*gated=*/true, nullptr, &used));
     if (d_soft) HIP_TRY(c, dk::reduce_soft(c->stream, N, used, d_part, d_soft));
     return end_call(c);
+}
+
+int dsac_process_images_begin(dsac_ctx* c, int hyps_per_frame, uint64_t seed, float thr, int max_tries, float clampv, float tau, float beta, double* poses,
+                              int32_t* sets_out, uint8_t* ok, float* err, double* soft_or_null) {
+    return pi_begin_call(c, "dsac_process_images_begin", hyps_per_frame, seed, thr, max_tries, clampv, tau, beta, poses, sets_out, ok, err, dk::K2_ELEM_F32, soft_or_null);
+}
+
+int dsac_process_images_begin_f16(dsac_ctx* c, int hyps_per_frame, uint64_t seed, float thr, int max_tries, float clampv, float tau, float beta, double* poses,
+                                  int32_t* sets_out, uint8_t* ok, uint16_t* err16, double* soft_or_null) {
+    return pi_begin_call(c, "dsac_process_images_begin_f16", hyps_per_frame, seed, thr, max_tries, clampv, tau, beta, poses, sets_out, ok, err16, dk::K2_ELEM_F16,
+                         soft_or_null);
 }
 
 int dsac_process_images_finish(dsac_ctx* c, int hyps_per_frame, const double* scores, double scale, const int32_t* perm, int steps, int max_inl, int min_inl,

@@ -753,6 +753,51 @@ static hipError_t launch_reproject_hp(hipStream_t st, int N, const float* staged
 //   ANY = 2, the tail launch (only when P % 4 != 0): one wave per hypothesis tile on the map's LAST 64-cell chunk, for that one lane alone -- its cells loaded,
 //            stored and summed one by one (per-cell validity: a padded cell never adds a sigmoid to a score), its sums in a partial row of their own.
 typedef f4 f4_a4 __attribute__((aligned(4)));
+// The store of the half-precision build (k_reproject_st<.., EXF = 3 / 4>, dsac_reproject_f16): ev[r] = 4 consecutive cells of row r of the lane's four rows, each
+// value rounded to binary16 to nearest even (a plain conversion: the compiler's v_cvt_pk_f16_f32), P % 8 == 0.  base: the group's first row (wave-uniform);
+// full (wave-uniform): the hypothesis tile is whole, no test per row; else rows = how many of the lane's four rows exist.  The row stepping is the float build's: a scalar resource, a scalar row offset, a 32-bit lane offset.
+//   LAYOUT 1: four 8-byte stores per lane and chunk (a wave store is 4 rows x 128 B)
+//   LAYOUT 2: lanes c and c ^ 1 hold cells 8k .. 8k + 3 and 8k + 4 .. 8k + 7 of the same four rows (both exist or neither).  The even lane takes rows 0 and 1 of
+//             all eight cells, the odd lane rows 2 and 3: every dword of a stored row is the lane's own or its neighbour's (quad_perm [1, 0, 3, 2]), one select
+//             each; two 16-byte stores per lane and chunk
+typedef unsigned u2v __attribute__((ext_vector_type(2)));
+template <int LAYOUT>
+DM_INLINE void store_rows_h16(_Float16* base, const f4 (&ev)[4], int P, int p0, int g, int c, bool full, int rows) {
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0xffffffffu, 0x00020000);
+    unsigned pk[4][2];
+#pragma unroll
+    for (int r = 0; r < 4; r++) { pk[r][0] = pk_h2(ev[r].x, ev[r].y); pk[r][1] = pk_h2(ev[r].z, ev[r].w); }
+    if constexpr (LAYOUT == 1) {
+        const unsigned loff = ((unsigned)(4 * g) * (unsigned)P + (unsigned)p0) * 2u;
+        if (full) {
+#pragma unroll
+            for (int r = 0; r < 4; r++) __builtin_amdgcn_raw_buffer_store_b64(u2v{pk[r][0], pk[r][1]}, rsrc, loff, (unsigned)r * (unsigned)P * 2u, 2);
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+                if (r < rows) __builtin_amdgcn_raw_buffer_store_b64(u2v{pk[r][0], pk[r][1]}, rsrc, loff, (unsigned)r * (unsigned)P * 2u, 2);
+        }
+    } else {
+        const bool odd = (c & 1) != 0;
+        auto nb = [](unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true); };
+        // the neighbour's dwords are fetched by every lane of the pair BEFORE the selects: a cross-lane read under a condition on the lane's parity would find
+        // its source lane switched off
+        unsigned nk[4][2];
+#pragma unroll
+        for (int r = 0; r < 4; r++) { nk[r][0] = nb(pk[r][0]); nk[r][1] = nb(pk[r][1]); }
+        const u4v ra = {odd ? nk[2][0] : pk[0][0], odd ? nk[2][1] : pk[0][1], odd ? pk[2][0] : nk[0][0], odd ? pk[2][1] : nk[0][1]};
+        const u4v rb = {odd ? nk[3][0] : pk[1][0], odd ? nk[3][1] : pk[1][1], odd ? pk[3][0] : nk[1][0], odd ? pk[3][1] : nk[1][1]};
+        const int r0 = odd ? 2 : 0;  // this lane's rows: r0, r0 + 1
+        const unsigned loff = ((unsigned)(4 * g + r0) * (unsigned)P + (unsigned)(p0 & ~7)) * 2u;
+        if (full) {
+            __builtin_amdgcn_raw_buffer_store_b128(ra, rsrc, loff, 0u, 2);
+            __builtin_amdgcn_raw_buffer_store_b128(rb, rsrc, loff, (unsigned)P * 2u, 2);
+        } else {
+            if (r0 < rows) __builtin_amdgcn_raw_buffer_store_b128(ra, rsrc, loff, 0u, 2);
+            if (r0 + 1 < rows) __builtin_amdgcn_raw_buffer_store_b128(rb, rsrc, loff, (unsigned)P * 2u, 2);
+        }
+    }
+}
 template <int NG, int CHW, int WAVES, bool PW, bool ERR, bool SOFT, bool UV, bool G64, int MINW, bool LO = false, int EXF = 0, int ANY = 0>
 __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* __restrict__ staged, const float* __restrict__ xyz,
                                                              const float* __restrict__ uv, float* __restrict__ err,
@@ -761,7 +806,12 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* 
                                                              long long uv_stride, const float* __restrict__ staged_lo = nullptr,
                                                              const void* __restrict__ split = nullptr) {
     constexpr int HT = 16 * NG;
-    constexpr bool EX = EXF != 0, RSQ = EXF == 2;  // EXF: 0 = fp32 transform, 1 = exact transform (split fp16 records), 2 = the same with the one-transcendental tail (hp_chunk_ex)
+    constexpr bool EX = EXF != 0, RSQ = EXF >= 2;  // EXF: 0 = fp32 transform, 1 = exact transform (split fp16 records), 2 = the same with the one-transcendental tail (hp_chunk_ex)
+    // EXF = 3 / 4: EXF = 2 with the error images stored as IEEE binary16 (dsac_reproject_f16; `err` then points to halves).  Everything up to ev[r] and the sigmoid
+    // sums is EXF = 2's code; only the store differs: 3 = four 8-byte stores per lane and chunk, 4 = lanes c and c ^ 1 trade rows, two 16-byte stores of 8 cells each.
+    // The element type rides in EXF and not in a parameter of its own so that the float kernels keep their names (the Makefile's ISA-mix targets select by name)
+    constexpr int H16 = EXF >= 3 ? EXF - 2 : 0;
+    static_assert(H16 == 0 || (ERR && ANY == 0 && !LO), "half error images: the vector build of the exact form, with an error image to store");
     const int b = blockIdx.x;
     int ht, pt;
     if (kflags & 32) { pt = b % PT; ht = b / PT; }  // plain pixel-minor order
@@ -1002,7 +1052,10 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* 
                     }
                 }
             }
-            if (ERR && valid[ch] && fast_stores) {
+            if constexpr (H16 != 0) {
+                if (valid[ch]) store_rows_h16<H16>(reinterpret_cast<_Float16*>(err) + (size_t)(h0 + 16 * gi) * P, ev, P, p0[ch], g, c, nh == HT, nh - hyp0);
+            }
+            if (H16 == 0 && ERR && valid[ch] && fast_stores) {
                 // buffer store: the address is a wave-uniform row base in a scalar resource (the tile's first hypothesis of this group) + a scalar row offset +
                 // a 32-bit lane offset (the lane's hypothesis quarter and pixel).  A global store's 64-bit vector address cost one vector instruction per store
                 // (v_lshl_add_u64), 16 per 1 024 pairs of a kernel that is bound by vector issue; this form steps the rows on the scalar unit
@@ -1241,7 +1294,10 @@ static hipError_t launch_reproject_st(hipStream_t st, int N, const float* staged
                           soft_part, N, F.P, F.W, PT, F.cx, F.cy, clampv, kA, kB, kflags, Nf, F.xyz_stride, F.uv_stride, staged_lo, split)
     if (ERR && SOFT) { if (UV) DSAC_K2S(true, true, true, false); else if (G64) DSAC_K2S(true, true, false, true); else DSAC_K2S(true, true, false, false); }
     else if (ERR) { if (UV) DSAC_K2S(true, false, true, false); else if (G64) DSAC_K2S(true, false, false, true); else DSAC_K2S(true, false, false, false); }
-    else if (SOFT) { if (UV) DSAC_K2S(false, true, true, false); else if (G64) DSAC_K2S(false, true, false, true); else DSAC_K2S(false, true, false, false); }
+    else if (SOFT) {
+        if constexpr (EX >= 3) return hipErrorInvalidValue;  // the half-store builds exist with an error image only
+        else { if (UV) DSAC_K2S(false, true, true, false); else if (G64) DSAC_K2S(false, true, false, true); else DSAC_K2S(false, true, false, false); }
+    }
 #undef DSAC_K2S
     return hipGetLastError();
 }
@@ -1551,6 +1607,11 @@ hipError_t reproject(hipStream_t st, int N, const float* staged, const FrameDev&
     } else if (opts.variant >= 0 && !ex_variant) why |= K2_WHY_FORCED;
     if (!pose_split_available(F)) why |= K2_WHY_FOCAL;
     if (!opts.poses64) why |= K2_WHY_NO_POSES;  // dsac_score_sampled without the cv poses: nothing to split
+    // half error images (dsac_reproject_f16 / dsac_process_images_begin_f16): the auto policy's exact vector build and nothing else -- the entry points have refused
+    // every other request by name; a launch that gets here all the same is an error, never another form and never a float store into a half buffer
+    if (opts.err_elem == K2_ELEM_F16 && !(err && vec && F.P % 8 == 0 && split_ok && opts.variant < 0 && k2_wants_exact(opts) &&
+                                          !(opts.flags & ~(K2_FLAG_EXACT | K2_FLAG_EXACT_ANY))))
+        return hipErrorNotSupported;
     auto report = [&](int form) { if (opts.report) { opts.report[0] = form; opts.report[1] = (form == K2_FORM_EXACT_VEC || form == K2_FORM_EXACT_ANY) ? 0 : why; } };
     // An arithmetic form that was ASKED for (k2_flags bits 25 / 27 / 28) and cannot run on this map -- its kernels read 16-byte vectors: H*W % 4, aligned buffers
     // and, on the implicit grid, four cells of a lane in one row; the exact form also needs a focal length <= 2^10 -- is an error, not a silent fp32 launch
@@ -1612,6 +1673,11 @@ hipError_t reproject(hipStream_t st, int N, const float* staged, const FrameDev&
                       // r06_k2_rsq_parity.txt) on the <64, 256> tile at every size.  For one frame of 256 hypotheses the <64, 64> tile is 0.8 us faster by itself
                       // (62.6 against 63.4) but leaves four times the partial-sum rows: k_reduce_soft 27.6 against 8.9 us (profiles/r06_one_image_trace.txt)
                 // small maps keep the small tile: a 40 x 40 map is 7 tiles of 256 pixels (one image per call 116 -> 127 us with them), and its partial sums are 25 rows
+                // half error images: the same two tiles, EXF = 3 (8-byte stores) or 4 (rows traded between neighbouring lanes, 16-byte stores; "k2_f16_store")
+                if (opts.err_elem == K2_ELEM_F16) {
+                    if (opts.f16_store == 0) return F.P <= 16384 ? DSAC_EX(4, 1, 3, 3) : DSAC_EX(4, 4, 2, 3);
+                    return F.P <= 16384 ? DSAC_EX(4, 1, 3, 4) : DSAC_EX(4, 4, 2, 4);
+                }
                 if (F.P <= 16384) return DSAC_EX(4, 1, 3, 2);
                 return DSAC_EX(4, 4, 2, 2);
             case 84: default: return DSAC_EX(4, 4, 2, 1);  // <64, 256>, 2 waves per SIMD, reciprocal + Newton + square root (<64, 256> at three waves per SIMD spills: 1.7 ms, profiles/r06_k2_exact_ab.txt)

@@ -47,7 +47,11 @@ struct K2Opts {
     const void* split = nullptr;      // per call: the split fp16 records (pose_prep_split), for flags bit 28
     const double* poses64 = nullptr;  // per call: the cv poses (N x 6 doubles) the staged records were made from -- the precise form (flags bit 25) works from these
     int* report = nullptr;            // per call: int[2] that receives the arithmetic form of the launch (K2_FORM_*) and why it is not the exact one (K2_WHY_*)
+    int err_elem = 0;                 // per call: element type of `err` (K2_ELEM_*); K2_ELEM_F16: `err` points to N x P IEEE binary16 (the exact vector build only, P % 8 == 0)
+    int f16_store = 1;                // "k2_f16_store": store layout of the half build: 0 = four 8-byte stores per lane and chunk, 1 (default: 882 against 892 us at the
+                                      // bench shape, profiles/k2_f16_ab.txt) = two 16-byte stores after a lane exchange
 };
+enum { K2_ELEM_F32 = 0, K2_ELEM_F16 = 1 };
 constexpr int K2_FLAG_RECLO = 1 << 27;    // k2_flags: pose records in two pieces -- the low parts through fp16 matrix-core instructions chained onto the fp32 ones
 constexpr int K2_FLAG_STORE_ONLY = 1 << 1;  // k2_flags: store schedule only (measurement)
 constexpr int K2_FLAG_EXACT = 1 << 28;    // k2_flags: exact transform -- split fp16 records through the fp16 matrix core, the camera-frame point rounded to float once (round 6)

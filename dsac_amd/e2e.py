@@ -236,10 +236,13 @@ class ScoredFrameBatch:
                   378-383)  ->  F x H*W x 3 scene-coordinate gradients in HBM.
 
     The engine runs on torch's current stream: the three parties are ordered by the stream alone, nothing leaves the GPU, the host never waits.  Frame f
-    draws from the random stream of seed + f, so every frame's result equals the per-image path (TrainStep.forward_backward with seed + f)."""
+    draws from the random stream of seed + f, so every frame's result equals the per-image path (TrainStep.forward_backward with seed + f).
+
+    err_dtype=torch.float16: K2 writes the error images in half precision (dsac_process_images_begin_f16: half the bytes) and the score model runs on
+    them under torch.autocast; its gradient images are converted to float32 before dsac_score_backward (no K4 reads halves).  Default float32."""
 
     def __init__(self, device=0, frames=8, hyps=256, ref_steps=8, inlier_count=100, thr=10.0, sub_sample=0.01, cam=(525.0, 525.0, 320.0, 240.0), score_net=None,
-                 H=CNN_OBJ_PATCHSIZE, W=CNN_OBJ_PATCHSIZE, engine=None):
+                 H=CNN_OBJ_PATCHSIZE, W=CNN_OBJ_PATCHSIZE, engine=None, err_dtype=torch.float32):
         self.dev = torch.device("cuda", device)
         torch.cuda.set_device(self.dev)
         self.F, self.N, self.H, self.W, self.P = frames, hyps, H, W, H * W
@@ -249,7 +252,8 @@ class ScoredFrameBatch:
         F, N, P = frames, hyps, self.P
         f64 = dict(dtype=torch.float64, device=self.dev)
         self.poses, self.sets, self.ok = torch.zeros(F * N, 6, **f64), torch.zeros(F * N, 4, dtype=torch.int32, device=self.dev), torch.zeros(F * N, dtype=torch.uint8, device=self.dev)
-        self.err = torch.zeros(F * N, 1, H, W, dtype=torch.float32, device=self.dev)
+        self.err_dtype = err_dtype
+        self.err = torch.zeros(F * N, 1, H, W, dtype=err_dtype, device=self.dev)
         self.res = dict(sfScores=torch.zeros(F * N, **f64), sfEntropy=torch.zeros(F, **f64), avgHyp=torch.zeros(F, 6, **f64), refAvgHyp=torch.zeros(F, 6, **f64),
                         refSteps=torch.zeros(F, dtype=torch.int32, device=self.dev), inlierMaps=torch.zeros(F, P, dtype=torch.int32, device=self.dev), out4=torch.zeros(F, 4, **f64))
         self.grad_xyz = torch.zeros(F, P, 3, **f64)
@@ -262,7 +266,8 @@ class ScoredFrameBatch:
         eng.set_frames(xyz, uv, self.H, self.W, self.cam, uv_per_frame=uv_per_frame, borrow=True)
         eng.processImagesBegin(N, self.err, seed=seed, thr=self.thr, out=(self.poses, self.sets, self.ok))
         self._err_in = self.err.detach().requires_grad_(True)  # same storage: the score CNN reads what K2 wrote
-        self._scores = self.score_net(self._err_in)
+        with torch.autocast("cuda", dtype=torch.float16, enabled=self.err_dtype == torch.float16):
+            self._scores = self.score_net(self._err_in)
         self.scores = self._scores.detach().double().contiguous()
         eng.processImagesFinish(N, self.scores, perm, self.poses, gt_jp6=gt_jp6, scale=1.0, thr=self.thr, max_inl=self.inlier_count, out=self.res)
         return self.res
@@ -278,8 +283,8 @@ class ScoredFrameBatch:
         check(ctx, lib.dsac_backward_path1(ctx, F * N, ptr(self.poses), ptr(self.sets), ptr(r["sfScores"]), ptr(r["avgHyp"]), ptr(r["refAvgHyp"]), ptr(gt), ptr(perm),
                                            int(perm.shape[0]), int(self.inlier_count), 50, float(int(self.thr)), ptr(r["inlierMaps"]), float(self.sub_sample), 0.001, 2.0, 1.0,
                                            ptr(self.dpnp), ptr(self.grad_xyz), ptr(self.g), None, None))
-        self._scores.backward(gradient=self.g.float().clamp_(-CLAMP_E2E, CLAMP_E2E))
-        d = self._err_in.grad.reshape(F * N, H, W)
+        self._scores.backward(gradient=self.g.to(self._scores.dtype).clamp_(-CLAMP_E2E, CLAMP_E2E))
+        d = self._err_in.grad.reshape(F * N, H, W).float()  # K4 reads float32 gradient images (a no-op for a float32 model)
         # reference-exact seam: gradient images read back transposed (lua_calls.h:329-335) together with dScore's x*cols*3 + y*3 columns -- both or neither
         d_err = (d.transpose(1, 2) if quirk_transpose else d).reshape(F * N, P).contiguous()
         eng.dScore(self.poses, self.sets, d_err, dpnp=self.dpnp, quirk_transpose=quirk_transpose, grad=self.grad_xyz)

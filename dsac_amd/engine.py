@@ -33,6 +33,11 @@ def _np(a, dtype):
     return a  # torch tensor or address: caller guarantees dtype/layout
 
 
+def _is_f16(a):
+    """Is `a` a half-precision array or tensor (numpy float16 / torch.float16)?  Raw addresses and None are not."""
+    return str(getattr(a, "dtype", "")) in ("float16", "torch.float16")
+
+
 class Engine:
     """One DSAC engine context = one GPU stream.  Not thread-safe (one per host thread)."""
 
@@ -217,14 +222,16 @@ class Engine:
                            refstream=None):
         """First half of processImage for every frame set with set_frame / set_frames (cnn_softam.h:1010-1069): K1 sample + P3P, K2 -> the F*N error
         images in `err` (F*N x H*W float32, where the reference's score CNN reads them: lua_calls.h:98-104); soft (F*N float64, optional) receives the
-        soft-inlier sums as well.  out = (poses F*N x 6, sets F*N x 4, ok F*N) preallocated or None; returns it.  refstream: as processImages."""
+        soft-inlier sums as well.  out = (poses F*N x 6, sets F*N x 4, ok F*N) preallocated or None; returns it.  refstream: as processImages.
+        A float16 `err` (numpy or torch) takes dsac_process_images_begin_f16: the same values rounded to half, everything else bit for bit."""
         F, N = getattr(self, "frames", 1), int(hyps_per_frame)
         if out is None:
             out = (np.zeros((F * N, 6)), np.zeros((F * N, 4), np.int32), np.zeros(F * N, np.uint8))
         poses, sets_out, ok = out
         self._pi_refstream(refstream)
-        check(self._ctx, lib.dsac_process_images_begin(self._ctx, N, int(seed) & 0xFFFFFFFFFFFFFFFF, float(thr), int(max_tries), float(clamp), float(tau), float(beta),
-                                                       ptr(poses), ptr(sets_out), ptr(ok), ptr(err), ptr(soft)))
+        begin = lib.dsac_process_images_begin_f16 if _is_f16(err) else lib.dsac_process_images_begin
+        check(self._ctx, begin(self._ctx, N, int(seed) & 0xFFFFFFFFFFFFFFFF, float(thr), int(max_tries), float(clamp), float(tau), float(beta),
+                       ptr(poses), ptr(sets_out), ptr(ok), ptr(err), ptr(soft)))
         return out
 
     def processImagesFinish(self, hyps_per_frame, scores, perm, poses, gt_jp6=None, scale=1.0, thr=10.0, max_inl=100, min_inl=50, want_inlier_maps=False, out=None):
@@ -259,12 +266,13 @@ class Engine:
         return w, ent, avg
 
     def processImagesScored(self, hyps_per_frame, perm, score_fn, gt_jp6=None, seed=1305, thr=10.0, max_tries=1 << 20, clamp=CNN_OBJ_MAXINPUT, max_inl=100,
-                            min_inl=50, scale=1.0, err=None, want_inlier_maps=False, out=None, refstream=None):
+                            min_inl=50, scale=1.0, err=None, want_inlier_maps=False, out=None, refstream=None, err_dtype=None):
         """processImage of every frame with the reference's own kind of score: score_fn(err) -> F*N scores, err the F*N x H x W float32 error images
         as a torch DEVICE tensor that K2 has just written (nothing crosses PCIe: the reference pushes the same maps to Lua number by number,
         lua_calls.h:89-105).  score_fn runs on the engine's stream when the engine was made on torch's current stream (Engine(stream=...)); its result
         may be any floating torch tensor on the device.  perm / gt_jp6: device tensors or host arrays (host arrays are uploaded).  Returns the dict of
-        processImages with torch device tensors (plus "diffMaps").  refstream: as processImages."""
+        processImages with torch device tensors (plus "diffMaps").  refstream: as processImages.  err_dtype=torch.float16: the error images are
+        allocated, written by K2 and handed to score_fn in half precision (a given `err` decides by its own dtype); default float32."""
         import torch
         F, N = getattr(self, "frames", 1), int(hyps_per_frame)
         dev = torch.device("cuda", self.device)
@@ -278,7 +286,7 @@ class Engine:
                 return o[key]
             hyps, sets, ok = buf("hyps", (F * N, 6)), buf("sampledPoints", (F * N, 4), torch.int32), buf("ok", F * N, torch.uint8)
             if err is None:
-                err = torch.empty(F * N, self.H, self.W, dtype=torch.float32, device=dev)
+                err = torch.empty(F * N, self.H, self.W, dtype=err_dtype or torch.float32, device=dev)
             perm_d = perm if hasattr(perm, "data_ptr") else torch.as_tensor(np.ascontiguousarray(perm, dtype=np.int32), device=dev)
             gt_d = None if gt_jp6 is None else (gt_jp6 if hasattr(gt_jp6, "data_ptr") else
                                                 torch.as_tensor(np.ascontiguousarray(np.asarray(gt_jp6, dtype=np.float64).reshape(F, 6)), device=dev))
@@ -381,11 +389,13 @@ class Engine:
 
     # ---- K2 ---------------------------------------------------------------------------------------
     def reproject(self, poses, N=None, clamp=CNN_OBJ_MAXINPUT, err=None, soft=None, tau=10.0, beta=0.5):
-        """err[h] = getDiffMap(pose_h) (cnn_softam.h:319-362) and/or soft[h] = sum_p sigmoid(beta*(tau - err))."""
+        """err[h] = getDiffMap(pose_h) (cnn_softam.h:319-362) and/or soft[h] = sum_p sigmoid(beta*(tau - err)).  A float16 `err` (numpy or torch) takes
+        dsac_reproject_f16: the float call's values rounded to half, soft bit for bit; a float32 `err` is the float call."""
         poses = _np(poses, np.float64)
         if N is None:
             N = int(poses.shape[0])
-        check(self._ctx, lib.dsac_reproject(self._ctx, int(N), ptr(poses), float(clamp), ptr(err), float(tau), float(beta), ptr(soft)))
+        reproject = lib.dsac_reproject_f16 if _is_f16(err) else lib.dsac_reproject
+        check(self._ctx, reproject(self._ctx, int(N), ptr(poses), float(clamp), ptr(err), float(tau), float(beta), ptr(soft)))
         return err, soft
 
     def getDiffMap(self, poses, clamp=CNN_OBJ_MAXINPUT):

@@ -313,6 +313,23 @@ DSAC_API int dsac_sample_refstream_frames(dsac_ctx* ctx, int hyps_per_frame, flo
  * north_star (not in the reference).  Either output may be NULL. */
 DSAC_API int dsac_reproject(dsac_ctx* ctx, int N, const double* poses, float clamp, float* err_or_null, float tau, float beta,
                    double* soft_or_null);
+/* The same call with the error images in HALF precision, for a score model that reads halves (a PyTorch model under autocast casts them on its first layer
+ * anyway): err16 [N][H*W] IEEE binary16 in the same hypothesis-major layout, a host or a device pointer, non-NULL.  Each stored value is the float the float
+ * call would have stored (a residual clamped to [0, clamp]), rounded to nearest even -- at most 0.031 px of rounding at 100 px, 0.004 px near a 10 px threshold.
+ * soft is the float call's soft bit for bit: the sigmoid is taken from the fp32 residual before it is rounded for the store.  Everything else (frame
+ * batches, the K2 gate events, the profile hooks) is dsac_reproject's; K2 stores half the bytes.
+ * The half output exists for the DEFAULT arithmetic only, the exact-transform vector build ("k2_flags" bit 28), on the tiles of the auto policy.  The call is
+ * DSAC_ERR_INVALID -- nothing is launched, "k2_form_last" keeps its value, dsac_last_error names the condition -- unless
+ *   H*W % 8 == 0;  err16 and the frame's xyz and uv are on 16-byte addresses;  the focal length is <= 1 024 px;  "k2_variant" is -1;
+ *   no "k2_flags" bit other than 28 / 29 is set;  "k2_exact_auto" is 1 or bit 28 / 29 is set.
+ * After a successful call "k2_form_last" is DSAC_K2_FORM_EXACT_VEC and "k2_form_why_last" 0.  Chunks with far coordinates take the in-kernel fp32 path as in
+ * the float build; their values too are the float build's, rounded.
+ *   "k2_f16_store" (dsac_set_option)  the store layout of the half build: 0 = four 8-byte stores per lane and 64-cell chunk, 1 (default) = neighbouring lanes trade
+ *                 rows so that each issues two 16-byte stores of 8 cells (A/B: scripts/k2_f16_ab.py, profiles/k2_f16_ab.txt); the values do not depend on it.
+ * Not part of this: a K4 (dsac_score_backward) that reads half gradient images -- a half-precision score model's d_err is converted to float by the caller
+ * (dsac_amd/e2e.py, ScoredFrameBatch); the any-map build and the fp32 / precise / two-piece forms in half; dsac_score_hypotheses*, dsac_process_images and
+ * the pipelined pair in half; bf16. */
+DSAC_API int dsac_reproject_f16(dsac_ctx* ctx, int N, const double* poses, float clamp, uint16_t* err16, float tau, float beta, double* soft_or_null);
 
 /* ---- K3: softmax / entropy / soft-argmax pose --------------------------------------------------- */
 /* Replaces softMax core/cnn_softam.h:535-553, entropy :80-88 and the weighted pose average :1082-1094.
@@ -540,6 +557,13 @@ DSAC_API int dsac_process_images_begin(dsac_ctx* ctx, int hyps_per_frame, uint64
 DSAC_API int dsac_process_images_finish(dsac_ctx* ctx, int hyps_per_frame, const double* scores, double scale, const int32_t* perm, int steps, int max_inl,
                                int min_inl, float thr, const double* gt_jp6_or_null, const double* poses, double* w, double* entropy, double* avg6,
                                double* ref6, int32_t* steps_done, int32_t* inlier_maps_or_null, double* out4_or_null);
+/* dsac_process_images_begin with the error images in half precision: err16 [frames * hyps_per_frame][H*W] IEEE binary16, non-NULL, each value the float call's
+ * rounded to nearest even; poses, sets_out, ok and soft are the float call's bit for bit, "pi_refstream", "pi_defer_tail" and "seed_stride" apply as they do
+ * there, and dsac_process_images_finish follows it unchanged.  The conditions, the refusal (checked before K1 is enqueued) and "k2_f16_store" are those of
+ * dsac_reproject_f16.  The backward half of the seam stays in float: no K4 reads half gradient images, a half-precision score model's d_err is converted to
+ * float before dsac_score_backward. */
+DSAC_API int dsac_process_images_begin_f16(dsac_ctx* ctx, int hyps_per_frame, uint64_t seed, float thr, int max_tries, float clamp, float tau, float beta,
+                                  double* poses, int32_t* sets_out, uint8_t* ok, uint16_t* err16, double* soft_or_null);
 /* The same dependency for ANOTHER stream: `hip_stream` (a hipStream_t of the context's device) waits for the deferred tail that is in flight -- and
  * thereby for the dsac_process_images call it belongs to and everything the context's stream held before that call (the tail starts behind that call's
  * K3); the context's own stream is not held up, nothing is inserted into it, and the tail stays pending for it.  This is how a consumer of the tail's
