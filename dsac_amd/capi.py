@@ -47,6 +47,7 @@ EXPORTS = [
     "dsac_refstream_init", "dsac_refstream_discard", "dsac_sample_refstream", "dsac_sample_refstream_frames",
     "dsac_get_option", "dsac_k2_range_census",
     "dsac_reproject_f16", "dsac_process_images_begin_f16",
+    "dsac_score_backward_f16", "dsac_soft_score_derr_f16",
 ]
 
 # enum dsac_k2_form (dsac_get_option "k2_form_last") and the DSAC_K2_WHY_* bits ("k2_form_why_last")
@@ -92,6 +93,7 @@ def _load():
     lib.dsac_softmax.argtypes = [vp, i32, vp, f64, vp, vp, vp, vp]
     lib.dsac_dpnp.argtypes = [vp, i32, vp, f32, vp]
     lib.dsac_score_backward.argtypes = [vp, i32, vp, vp, vp, vp, u32, vp]
+    lib.dsac_score_backward_f16.argtypes = [vp, i32, vp, vp, vp, vp, u32, vp]
     lib.dsac_soft_score_backward.argtypes = [vp, i32, vp, vp, vp, f32, f32, f32, vp, u32, vp]
     lib.dsac_refine.argtypes = [vp, i32, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
     lib.dsac_refine_fd.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, f32, f32, f32, vp, vp, vp, i32, vp]
@@ -127,6 +129,7 @@ def _load():
     lib.dsac_loss_batch_frames.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     lib.dsac_select_frames.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.dsac_soft_score_derr.argtypes = [vp, i32, vp, vp, f32, f32, f32, vp]
+    lib.dsac_soft_score_derr_f16.argtypes = [vp, i32, vp, vp, f32, f32, f32, vp]
     lib.dsac_softmax_frames.argtypes = [vp, i32, i32, vp, f64, vp, vp, vp, vp]
     lib.dsac_process_images_begin.argtypes = [vp, i32, u64, f32, i32, f32, f32, f32, vp, vp, vp, vp, vp]
     lib.dsac_process_images_begin_f16.argtypes = [vp, i32, u64, f32, i32, f32, f32, f32, vp, vp, vp, vp, vp]

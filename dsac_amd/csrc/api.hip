@@ -12,6 +12,7 @@
 #include <cmath>
 #include <deque>
 #include <string>
+#include <type_traits>
 #include <vector>
 // std::uniform_int_distribution of the libstdc++ this library is built against: GCC >= 11 draws by Lemire's method, older ones by scaling and division
 // (refstream.h); "refstream_mode" overrides
@@ -1281,7 +1282,40 @@ int dsac_profile_read(dsac_ctx* c, int which, double* ms_total, int* launches, i
     return DSAC_OK;
 }
 
-static int score_backward_common(dsac_ctx* c, const char* who, int N, const double* poses, const int32_t* sets, const float* d_err,
+// What dsac_score_backward_f16 needs beyond the float call, checked before anything is staged or enqueued.  Half gradient images are read by the matrix-core form
+// only, and whether a call gets that form is backward_plan's decision alone: the check asks the plan itself, frame by frame (the single-frame plan of every frame
+// of a batch, on that frame's own xyz / uv and its slice of d_err16 -- a host d_err16 is held to the alignment its staged copy will have anyway), and refuses
+// where it answers with the VALU form.  The conditions spelled out below only put a name to the plan's answer for dsac_last_error; they decide nothing.
+static int k4_f16_check(dsac_ctx* c, const char* who, int N, const uint16_t* d_err16, unsigned flags) {
+    const dk::FrameDev& F = c->F;
+    if (flags & (DSAC_BWD_PARITY_FP64 | DSAC_BWD_QUIRK_ROT_WRITEBACK))
+        return fail(c, DSAC_ERR_INVALID, "%s: half gradient images exist for the fp32 matrix-core form only: DSAC_BWD_PARITY_FP64 / DSAC_BWD_QUIRK_ROT_WRITEBACK read floats "
+                                         "(dsac_score_backward)", who);
+    const int frames = F.frames > 1 ? F.frames : 1;
+    const int n1 = N / frames;
+    for (int f = 0; f < frames; f++) {
+        dk::FrameDev Fd = F;
+        Fd.frames = 1;
+        Fd.xyz = F.xyz + (size_t)f * F.xyz_stride;
+        if (Fd.uv) Fd.uv = F.uv + (size_t)f * F.uv_stride;
+        Fd.xyz_stride = Fd.uv_stride = 0;
+        const uint16_t* d = d_err16 + (size_t)f * n1 * F.P;
+        if (dk::backward_plan(n1, Fd, d, c->k4_variant, 0, dk::K4_ELEM_F16).variant > 0) continue;
+        if (F.P % 4 != 0) return fail(c, DSAC_ERR_INVALID, "%s: half gradient images need H*W %% 4 == 0, this map has %d x %d = %d cells", who, F.H, F.W, F.P);
+        if (!F.uv && F.W % 4 != 0) return fail(c, DSAC_ERR_INVALID, "%s: half gradient images on the implicit pixel grid need W %% 4 == 0, W is %d", who, F.W);
+        if ((reinterpret_cast<uintptr_t>(Fd.xyz) & 15) || (reinterpret_cast<uintptr_t>(Fd.uv) & 15))
+            return fail(c, DSAC_ERR_INVALID, "%s: half gradient images need every frame's xyz and uv on 16-byte addresses (frame %d: %p, %p)", who, f, (const void*)Fd.xyz,
+                        (const void*)Fd.uv);
+        if (reinterpret_cast<uintptr_t>(d) & 7) return fail(c, DSAC_ERR_INVALID, "%s: d_err16 (%p) must be on an 8-byte address", who, (const void*)d_err16);
+        if (c->k4_variant >= 0 && (c->k4_variant % 1000) % 10 == 0)
+            return fail(c, DSAC_ERR_INVALID, "%s: k4_variant %d names the VALU form, which reads no half gradient images", who, c->k4_variant);
+        return fail(c, DSAC_ERR_INVALID, "%s: the matrix-core form, the only one that reads half gradient images, is not available for this frame and k4_variant %d", who, c->k4_variant);
+    }
+    return DSAC_OK;
+}
+
+// d_err: N x P floats (elem == dk::K4_ELEM_F32) or IEEE binary16 carried as 16-bit words (dk::K4_ELEM_F16: dsac_score_backward_f16), NULL with g
+static int score_backward_common(dsac_ctx* c, const char* who, int N, const double* poses, const int32_t* sets, const void* d_err, int elem,
                                  const double* g, float clampv, float tau, float beta, const double* dpnp_or_null, unsigned flags,
                                  double* grad_xyz) {
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "%s: ctx is NULL", who);
@@ -1303,17 +1337,32 @@ static int score_backward_common(dsac_ctx* c, const char* who, int N, const doub
         return fail(c, DSAC_ERR_INVALID, "%s: DSAC_BWD_QUIRK_ROT_WRITEBACK needs DSAC_BWD_PARITY_FP64 (the write-back is a sequential recurrence)", who);
     if (parity && (!d_err || (long long)(frames > 1 ? Nf : N) * c->F.P > (1ll << 26)))
         return fail(c, DSAC_ERR_INVALID, "%s: DSAC_BWD_PARITY_FP64 takes a d_err volume with N*H*W <= 2^26 (reference-sized maps)", who);
+    const bool f16 = elem == dk::K4_ELEM_F16;
+    if (f16 && N > 0) ARG_TRY(k4_f16_check(c, who, N, static_cast<const uint16_t*>(d_err), flags));
     if (N == 0) return DSAC_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c);
     const size_t P = (size_t)c->F.P;
     const double *d_poses, *d_dpnp, *d_g;
     const int32_t* d_sets;
-    const float* d_derr;
+    const void* d_derr;
     double* d_grad;
     ARG_TRY(in_arg(c, poses, (size_t)N * 6, &d_poses));
     ARG_TRY(in_arg(c, sets, (size_t)N * 4, &d_sets));
-    ARG_TRY(in_arg(c, d_err, (size_t)N * P, &d_derr));
+    if (f16) {  // host halves are staged at 2 bytes per element
+        const uint16_t* d16;
+        ARG_TRY(in_arg(c, static_cast<const uint16_t*>(d_err), (size_t)N * P, &d16));
+        d_derr = d16;
+    } else {
+        const float* d32;
+        ARG_TRY(in_arg(c, static_cast<const float*>(d_err), (size_t)N * P, &d32));
+        d_derr = d32;
+    }
+    // hypothesis h0's row of the gradient images: the offset is in elements of either type
+    auto derr_row = [&](size_t h0) -> const void* {
+        if (!d_derr) return nullptr;
+        return f16 ? static_cast<const void*>(static_cast<const uint16_t*>(d_derr) + h0 * P) : static_cast<const void*>(static_cast<const float*>(d_derr) + h0 * P);
+    };
     ARG_TRY(in_arg(c, g, (size_t)N, &d_g));
     ARG_TRY(in_arg(c, dpnp_or_null, (size_t)N * 72, &d_dpnp));
     ARG_TRY(out_arg(c, grad_xyz, (size_t)frames * P * 3, &d_grad, /*preload=*/true));
@@ -1339,13 +1388,13 @@ static int score_backward_common(dsac_ctx* c, const char* who, int N, const doub
         HIP_TRY(c, c->g6.reserve((size_t)N * 6 * sizeof(double)));
         for (int f = 0; f < frames; f++) {
             const size_t h0 = (size_t)f * n1;
-            HIP_TRY(c, dk::score_backward_parity(c->stream, n1, d_poses + h0 * 6, frames > 1 ? frame_view(f) : c->F, d_derr + h0 * P, d_dpnp + h0 * 72, d_sets + h0 * 4, flags,
+            HIP_TRY(c, dk::score_backward_parity(c->stream, n1, d_poses + h0 * 6, frames > 1 ? frame_view(f) : c->F, static_cast<const float*>(derr_row(h0)), d_dpnp + h0 * 72, d_sets + h0 * 4, flags,
                                                  jac.as<double>(), d_grad + (size_t)f * P * 3, c->g6.as<double>() + h0 * 6));
         }
         c->g6_n = N;
         return end_call(c);
     }
-    dk::K4Plan plan = dk::backward_plan(N, c->F, d_derr, c->k4_variant, Nf);
+    dk::K4Plan plan = dk::backward_plan(N, c->F, d_derr, c->k4_variant, Nf, elem);
     // the direct form adds into the caller's buffer with hardware fp64 atomics (unsafeAtomicAdd): those are only defined on ordinary (coarse-grained)
     // device memory.  Managed / fine-grained memory takes the staged form (partial sums + a reduction launch; on a frame batch: frame by frame, below)
     const int staged_variant = (c->k4_variant < 0 ? 999 : c->k4_variant % 1000) + 1000;
@@ -1355,7 +1404,9 @@ static int score_backward_common(dsac_ctx* c, const char* who, int N, const doub
         plain = hipPointerGetAttributes(&attr, grad_xyz) == hipSuccess && attr.type == hipMemoryTypeDevice;
         if (!plain) (void)hipGetLastError();
     }
-    if (plan.direct && !plain) plan = dk::backward_plan(N, c->F, d_derr, staged_variant, Nf);  // Nf < 0 for a batch: frame by frame
+    if (plan.direct && !plain) plan = dk::backward_plan(N, c->F, d_derr, staged_variant, Nf, elem);  // Nf < 0 for a batch: frame by frame
+    // k4_f16_check has ruled out what sends a plan to the VALU form; a half call never takes it silently
+    if (f16 && plan.Nf >= 0 && plan.variant <= 0) return fail(c, DSAC_ERR_INVALID, "%s: no matrix-core form for this call (k4_variant %d)", who, c->k4_variant);
     // Round 4, the fused stage (plan.fused): two launches instead of four -- the main pass derives its hypothesis records from the poses in its prologue
     // and (one hypothesis tile: plan.direct) adds the gradient straight into grad_xyz, the finish kernel derives dR/drod itself.  The round-3 staging
     // (k_backward_prep -> main -> k_grad_reduce -> k_support_scatter) remains for the VALU form and behind k4_variant + 1000.
@@ -1372,7 +1423,7 @@ static int score_backward_common(dsac_ctx* c, const char* who, int N, const doub
         if (!pl.fused) HIP_TRY(c, dk::backward_prep(c->stream, n, ps, Fd, c->bwd_staged.as<float>(), c->dRdH.as<double>()));
         {
             ProfScope ps1(c, 1);
-            HIP_TRY(c, dk::score_backward(c->stream, n, c->bwd_staged.as<float>(), Fd, d_derr ? d_derr + h0 * P : nullptr, d_g ? d_g + h0 : nullptr, clampv, tau, beta,
+            HIP_TRY(c, dk::score_backward(c->stream, n, c->bwd_staged.as<float>(), Fd, derr_row(h0), d_g ? d_g + h0 : nullptr, clampv, tau, beta,
                                           c->grad_part.as<float>(), c->g12_part.as<float>(), pl, ps, gr, flags));
         }
         HIP_TRY(c, dk::score_backward_finish(c->stream, n, Fd, c->grad_part.as<float>(), pl.direct ? 0 : pl.NT * pl.glayers, c->g12_part.as<float>(), pl.rows,
@@ -1385,8 +1436,8 @@ static int score_backward_common(dsac_ctx* c, const char* who, int N, const doub
         // per frame that is not a multiple of 16 up to 256: frame by frame through the single-frame forms, the scratch buffers reused in stream order -- F times the launches, the same numbers as F single-frame calls
         for (int f = 0; f < frames; f++) {
             const dk::FrameDev Fd = frame_view(f);
-            const dk::K4Plan pf = dk::backward_plan(Nf, Fd, d_derr ? d_derr + (size_t)f * Nf * P : nullptr, plain ? c->k4_variant : staged_variant, 0);
-            if (pf.Nf < 0) return fail(c, DSAC_ERR_INVALID, "%s: no kernel form for this map (k4_variant %d)", who, c->k4_variant);
+            const dk::K4Plan pf = dk::backward_plan(Nf, Fd, derr_row((size_t)f * Nf), plain ? c->k4_variant : staged_variant, 0, elem);
+            if (pf.Nf < 0 || (f16 && pf.variant <= 0)) return fail(c, DSAC_ERR_INVALID, "%s: no kernel form for this map (k4_variant %d)", who, c->k4_variant);
             ARG_TRY(run(Nf, Fd, pf, (size_t)f * Nf, (size_t)f * P, 0));
         }
     } else {
@@ -1412,13 +1463,19 @@ int dsac_last_pose_gradients(dsac_ctx* c, int N, double* G6) {
 int dsac_score_backward(dsac_ctx* c, int N, const double* poses, const int32_t* sets, const float* d_err, const double* dpnp_or_null,
                         unsigned flags, double* grad_xyz) {
     if (c && !d_err) return fail(c, DSAC_ERR_INVALID, "dsac_score_backward: d_err is NULL");
-    return score_backward_common(c, "dsac_score_backward", N, poses, sets, d_err, nullptr, 100.0f, 0.f, 0.f, dpnp_or_null, flags, grad_xyz);
+    return score_backward_common(c, "dsac_score_backward", N, poses, sets, d_err, dk::K4_ELEM_F32, nullptr, 100.0f, 0.f, 0.f, dpnp_or_null, flags, grad_xyz);
+}
+
+int dsac_score_backward_f16(dsac_ctx* c, int N, const double* poses, const int32_t* sets, const uint16_t* d_err16, const double* dpnp_or_null,
+                            unsigned flags, double* grad_xyz) {
+    if (c && !d_err16) return fail(c, DSAC_ERR_INVALID, "dsac_score_backward_f16: d_err16 is NULL");
+    return score_backward_common(c, "dsac_score_backward_f16", N, poses, sets, d_err16, dk::K4_ELEM_F16, nullptr, 100.0f, 0.f, 0.f, dpnp_or_null, flags, grad_xyz);
 }
 
 int dsac_soft_score_backward(dsac_ctx* c, int N, const double* poses, const int32_t* sets, const double* g, float clampv, float tau, float beta,
                              const double* dpnp_or_null, unsigned flags, double* grad_xyz) {
     if (c && !g) return fail(c, DSAC_ERR_INVALID, "dsac_soft_score_backward: g is NULL");
-    return score_backward_common(c, "dsac_soft_score_backward", N, poses, sets, nullptr, g, clampv, tau, beta, dpnp_or_null, flags, grad_xyz);
+    return score_backward_common(c, "dsac_soft_score_backward", N, poses, sets, nullptr, dk::K4_ELEM_F32, g, clampv, tau, beta, dpnp_or_null, flags, grad_xyz);
 }
 int dsac_refine(dsac_ctx* c, int B, const double* init_poses, const int32_t* perm, int steps, int max_inl, int min_inl, float thr,
                 const int32_t* pert_px_c, const float* pert_value, double* out_poses, int32_t* inlier_map, int32_t* steps_done) {
@@ -1890,55 +1947,81 @@ int dsac_select_frames(dsac_ctx* c, int frames, int N, const double* probs, cons
 }
 
 // d_err[h][p] = g[h] * d soft[h] / d err[h][p] = g[h] * (-beta) * s (1 - s),  s = sigmoid(beta (tau - err[h][p])); zero where the residual sits on the clamp
-// (the score no longer depends on it there -- what K4's in-kernel form does, k_backward.hip).  One float4 per lane, the row index from the launch's y.
+// (the score no longer depends on it there -- what K4's in-kernel form does, k_backward.hip).  Four cells per lane (one float4, or four halves in 8 bytes:
+// dsac_soft_score_derr_f16 -- widened on the load, the same fp32 arithmetic, rounded to nearest even on the store), the row index from the launch's y.
+extern "C++" {  // templates: the element type of the images
 namespace {
-__global__ __launch_bounds__(256) void k_soft_derr(int P4, const float4* __restrict__ err, const double* __restrict__ g, float clampv, float tau, float beta,
-                                                   float4* __restrict__ d_err) {
+typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
+template <typename V4, typename E>  // V4: four cells as one vector -- float4 of E = float, or four E = _Float16 in 8 bytes
+__global__ __launch_bounds__(256) void k_soft_derr(int P4, const V4* __restrict__ err, const double* __restrict__ g, float clampv, float tau, float beta,
+                                                   V4* __restrict__ d_err) {
     const size_t h = blockIdx.y;
     const float gh = (float)g[h] * (-beta);
-    const float4* e = err + h * (size_t)P4;
-    float4* d = d_err + h * (size_t)P4;
+    const V4* e = err + h * (size_t)P4;
+    V4* d = d_err + h * (size_t)P4;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < P4; i += gridDim.x * blockDim.x) {
-        const float4 v = e[i];
-        float4 o;
-        const float in[4] = {v.x, v.y, v.z, v.w};
+        const V4 v = e[i];
+        V4 o;
+        const float in[4] = {(float)v.x, (float)v.y, (float)v.z, (float)v.w};
         float out[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const float s = 1.f / (1.f + __expf(-beta * (tau - in[k])));
             out[k] = in[k] >= clampv ? 0.f : gh * s * (1.f - s);
         }
-        o.x = out[0]; o.y = out[1]; o.z = out[2]; o.w = out[3];
+        if constexpr (std::is_same<E, _Float16>::value) {
+            // The half store rounds the fp32 result, the float kernel's float, to nearest even (v_cvt_f16_f32; subnormal results kept).  Left to itself the compiler
+            // folds the last multiply into the conversion (v_fma_mixlo_f16: the exact product rounded to half ONCE), which is one half ulp off the float call's
+            // rounded float on about 1 cell in 20 000.  There is no builtin for "convert, do not fuse"; the empty statement pins the float in a register first.
+            // tests/test_gpu_k4_f16.py::test_soft_score_derr_in_half compares the bits of every cell and fails if a compiler fuses the two again.
+#pragma unroll
+            for (int k = 0; k < 4; k++) asm volatile("" : "+v"(out[k]));
+        }
+        o.x = static_cast<E>(out[0]); o.y = static_cast<E>(out[1]); o.z = static_cast<E>(out[2]); o.w = static_cast<E>(out[3]);
         d[i] = o;
     }
 }
-}  // namespace
 
-int dsac_soft_score_derr(dsac_ctx* c, int N, const double* g, const float* err, float clampv, float tau, float beta, float* d_err) {
-    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_soft_score_derr: ctx is NULL");
-    if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "dsac_soft_score_derr: no frame set (the maps are H*W wide)");
-    if (N < 0 || !g || !err || !d_err || !(beta > 0.f)) return fail(c, DSAC_ERR_INVALID, "dsac_soft_score_derr: NULL argument, negative count or beta <= 0");
-    if (c->F.P % 4 != 0) return fail(c, DSAC_ERR_INVALID, "dsac_soft_score_derr: H*W must be a multiple of 4");
+// shared by dsac_soft_score_derr (V4 = float4, 16-byte vectors) and dsac_soft_score_derr_f16 (V4 = four halves, 8-byte vectors); T: the C ABI's element type
+template <typename V4, typename E, typename T>
+int soft_derr_call(dsac_ctx* c, const char* who, int N, const double* g, const T* err, float clampv, float tau, float beta, T* d_err) {
+    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "%s: ctx is NULL", who);
+    if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "%s: no frame set (the maps are H*W wide)", who);
+    if (N < 0 || !g || !err || !d_err || !(beta > 0.f)) return fail(c, DSAC_ERR_INVALID, "%s: NULL argument, negative count or beta <= 0", who);
+    if (c->F.P % 4 != 0) return fail(c, DSAC_ERR_INVALID, "%s: H*W must be a multiple of 4", who);
+    if (std::is_same<E, _Float16>::value && ((reinterpret_cast<uintptr_t>(err) | reinterpret_cast<uintptr_t>(d_err)) % sizeof(V4)) != 0)  // the half call: before anything is staged
+        return fail(c, DSAC_ERR_INVALID, "%s: err16 (%p) / d_err16 (%p) must be on 8-byte addresses", who, (const void*)err, (const void*)d_err);
     if (N == 0) return DSAC_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c);
     const size_t P = (size_t)c->F.P;
     const double* d_g;
-    const float* d_e;
-    float* d_o;
+    const T* d_e;
+    T* d_o;
     ARG_TRY(in_arg(c, g, (size_t)N, &d_g));
     ARG_TRY(in_arg(c, err, (size_t)N * P, &d_e));
     ARG_TRY(out_arg(c, d_err, (size_t)N * P, &d_o));
-    if ((reinterpret_cast<uintptr_t>(d_e) | reinterpret_cast<uintptr_t>(d_o)) % 16 != 0) return fail(c, DSAC_ERR_INVALID, "dsac_soft_score_derr: err / d_err must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_e) | reinterpret_cast<uintptr_t>(d_o)) % sizeof(V4) != 0)
+        return fail(c, DSAC_ERR_INVALID, "%s: err / d_err must be %d-byte aligned", who, (int)sizeof(V4));
     const int P4 = (int)(P / 4);
     const unsigned gx = (unsigned)std::min<int>((P4 + 255) / 256, 64);
     for (int h0 = 0; h0 < N; h0 += 65535) {
         const int n = std::min(N - h0, 65535);
-        hipLaunchKernelGGL(k_soft_derr, dim3(gx, (unsigned)n), dim3(256), 0, c->stream, P4, reinterpret_cast<const float4*>(d_e + (size_t)h0 * P), d_g + h0, clampv, tau, beta,
-                           reinterpret_cast<float4*>(d_o + (size_t)h0 * P));
+        hipLaunchKernelGGL((k_soft_derr<V4, E>), dim3(gx, (unsigned)n), dim3(256), 0, c->stream, P4, reinterpret_cast<const V4*>(d_e + (size_t)h0 * P), d_g + h0, clampv, tau, beta,
+                           reinterpret_cast<V4*>(d_o + (size_t)h0 * P));
         HIP_TRY(c, hipGetLastError());
     }
     return end_call(c);
+}
+}  // namespace
+}  // extern "C++"
+
+int dsac_soft_score_derr(dsac_ctx* c, int N, const double* g, const float* err, float clampv, float tau, float beta, float* d_err) {
+    return soft_derr_call<float4, float>(c, "dsac_soft_score_derr", N, g, err, clampv, tau, beta, d_err);
+}
+
+int dsac_soft_score_derr_f16(dsac_ctx* c, int N, const double* g, const uint16_t* err16, float clampv, float tau, float beta, uint16_t* d_err16) {
+    return soft_derr_call<half4_t, _Float16>(c, "dsac_soft_score_derr_f16", N, g, err16, clampv, tau, beta, d_err16);
 }
 
 // ---- shared by dsac_process_images and the begin / finish pair -------------------------------------------------------------------------------

@@ -17,6 +17,7 @@
 // The main pass reads d_err (N x P f32, streaming) once: 4 B per (h,p), HBM-read bound on paper and close
 // to the fp32 VALU ridge in practice (~55 VALU ops per pair).  All reductions are two-stage and
 // deterministic except the final fp64 scatter to the 4 support pixels (atomics).
+#include <type_traits>
 #include "kernels.h"
 #include "dmath.h"
 
@@ -345,9 +346,13 @@ DM_INLINE float row16_sum_f(float v) {  // sum over the 16 lanes of a DPP row, r
     return v;
 }
 
-template <int CH, bool SOFTMODE, bool UV, int MINW>
+// ET: element type of d_err -- float, or _Float16 (dsac_score_backward_f16: IEEE binary16 gradient images; the non-SOFTMODE builds only).  The half build is
+// the float build with an 8-byte load of a lane's 4 pixels instead of a 16-byte one and one widening conversion per (hypothesis, pixel) pair -- exact,
+// subnormal halves included --, so that under the same launch plan it returns the float build's result on the widened values bit for bit.
+typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+template <int CH, bool SOFTMODE, bool UV, int MINW, typename ET = float>
 __global__ __launch_bounds__(K4_THREADS, MINW) void k_score_backward_mfma(const float* __restrict__ rec, const float* __restrict__ xyz,
-                                                                    const float* __restrict__ uv, const float* __restrict__ d_err,
+                                                                    const float* __restrict__ uv, const ET* __restrict__ d_err,
                                                                     const double* __restrict__ g, float* __restrict__ grad_part,
                                                                     float* __restrict__ G12_part, int N, int P, int W, int PT, int NT, int G,
                                                                     float f, float cx, float cy, float clampv, float kA, float kB, float beta, int HT,
@@ -467,24 +472,27 @@ __global__ __launch_bounds__(K4_THREADS, MINW) void k_score_backward_mfma(const 
 #pragma unroll
             for (int pp = 0; pp < 2; pp++) gx[ch][pp] = gy[ch][pp] = gz[ch][pp] = zero2;
 
-        // d_err of the first group (one dwordx4 per chunk: 4 consecutive pixels of hypothesis c)
-        f4 wn[CH];
+        // d_err of the first group (one dwordx4 per chunk: 4 consecutive pixels of hypothesis c; the half build: one dwordx2, half the landing registers)
+        constexpr bool F16 = sizeof(ET) == 2;
+        using W4 = typename std::conditional<F16, h4, f4>::type;
+        const W4 zw = {0, 0, 0, 0};
+        W4 wn[CH];
         // Every lane loads, from a clamped address (ragged hypothesis end -> the tile's last row, pixels beyond the map -> the last 4): a load under a
         // lane mask is a branch around the instruction, hipcc's wait-count pass then no longer knows how many loads are in flight and waits vmcnt(0) at
         // the first use -- which also waited for the prefetch issued just before it (every second group paid a full memory round trip; round 3,
         // profiles/r03_k4_ablate.txt: 14 us of 124).  Lanes that must not contribute are switched off through `okscale` below.
-        auto load_w = [&](int gi, f4 (&dst)[CH]) {
+        auto load_w = [&](int gi, W4 (&dst)[CH]) {
             const int hyp = min(16 * gi + c, nh - 1);
 #pragma unroll
             for (int ch = 0; ch < CH; ch++) {
-                if (!(K4_ABLATE & 16) && !SOFTMODE) dst[ch] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(d_err + (size_t)(h0 + hyp) * P + min(p0[ch], P - 4)));
-                else dst[ch] = z4;
+                if (!(K4_ABLATE & 16) && !SOFTMODE) dst[ch] = __builtin_nontemporal_load(reinterpret_cast<const W4*>(d_err + (size_t)(h0 + hyp) * P + min(p0[ch], P - 4)));
+                else dst[ch] = zw;
             }
         };
         load_w(g_begin, wn);
 
         // one group of 16 hypotheses; `wv` = this group's d_err (the next group's is prefetched by the loop below)
-        auto group = [&](int gi, const f4 (&wv)[CH]) {
+        auto group = [&](int gi, const W4 (&wv)[CH]) {
             const float* simg = s_img + gi * 384;
             const float bx = simg[lane], by = simg[64 + lane], bz = simg[128 + lane];
             const f4* cf = reinterpret_cast<const f4*>(simg + 192 + c * 12);
@@ -549,7 +557,7 @@ __global__ __launch_bounds__(K4_THREADS, MINW) void k_score_backward_mfma(const 
                         const float gb = c2.y * (-beta);
                         w = (sg * f2{gb, gb}) * (f2{1.f, 1.f} - sg);
                     } else {
-                        w = pp ? f2{wv[ch].z, wv[ch].w} : f2{wv[ch].x, wv[ch].y};
+                        w = pp ? f2{(float)wv[ch].z, (float)wv[ch].w} : f2{(float)wv[ch].x, (float)wv[ch].y};  // half build: v_cvt_f32_f16, exact
                         if (K4_ABLATE & 16) w = f2{c2.y, c2.z} + ex;
                     }
                     w = w * keep;
@@ -603,13 +611,13 @@ __global__ __launch_bounds__(K4_THREADS, MINW) void k_score_backward_mfma(const 
             float* dst = s_G + ((size_t)(gi * 4 + wave) * 16 + c) * 12 + 3 * gq;  // private to this lane: plain read-modify-write
             dst[0] += a[0]; dst[1] += a[1]; dst[2] += a[2];
         };
-        // Software pipeline, distance one group: this group's d_err moves out of the landing registers (4 v_mov_b64 per chunk... the wait for the loads
+        // Software pipeline, distance one group: this group's d_err moves out of the landing registers (4 v_mov_b64 per chunk, half as many in the half build... the wait for the loads
         // issued a whole group ago sits here), the next group's loads are issued, then the arithmetic.  The prefetch is unconditional (the last group
         // of the range re-reads its own rows: 1 / 16 of the stream, from L2) and pinned: round 3 tried two register sets that swap roles through a
         // pair of calls -- the second call sits behind a branch, LLVM then sinks the first call's loads in front of their use and every other group
         // paid the memory round trip.
         for (int gi = g_begin; gi < g_end; gi++) {
-            f4 wv[CH];
+            W4 wv[CH];
 #pragma unroll
             for (int ch = 0; ch < CH; ch++) wv[ch] = wn[ch];
             load_w(min(gi + 1, g_end - 1), wn);
@@ -703,9 +711,12 @@ bool backward_variant_known(int v) {
     return form <= 7 && tile <= 3 && wgs <= 8;
 }
 
-K4Plan backward_plan(int N, const FrameDev& F, const float* d_err, int variant, int Nf) {
+K4Plan backward_plan(int N, const FrameDev& F, const void* d_err, int variant, int Nf, int elem) {
     K4Plan pl{};
     pl.glayers = 1;
+    pl.elem = elem;
+    // a lane reads its 4 pixels of d_err as one vector: 16 bytes of floats, 8 bytes of halves -- everything else of the plan is the same for both
+    const uintptr_t derr_mask = elem == K4_ELEM_F16 ? 7 : 15;
     const bool batch = Nf > 0 && F.frames > 1;
     // a frame's hypotheses as ONE tile up to 256, beyond that (round 6) as several equal tiles of the same launch: the largest multiple of 16 up to 256 that
     // divides the count (384 -> 192, 512 -> 256, 1024 -> 256); the tiles of a frame add into its gradient with fp64 atomics like the tiles of one big frame
@@ -715,7 +726,7 @@ K4Plan backward_plan(int N, const FrameDev& F, const float* d_err, int variant, 
             if (t > 0 && Nf % t == 0) { batch_ht = t; break; }
     }
     if (batch && (batch_ht == 0 || N % Nf != 0 || (variant >= 0 && variant % 10 == 0) || variant >= 1000)) { pl.variant = 0; pl.Nf = -1; return pl; }
-    const bool vec = (F.P % 4 == 0) && ((reinterpret_cast<uintptr_t>(d_err) & 15) == 0) && ((reinterpret_cast<uintptr_t>(F.xyz) & 15) == 0) &&
+    const bool vec = (F.P % 4 == 0) && ((reinterpret_cast<uintptr_t>(d_err) & derr_mask) == 0) && ((reinterpret_cast<uintptr_t>(F.xyz) & 15) == 0) &&
                      ((reinterpret_cast<uintptr_t>(F.uv) & 15) == 0) && F.P >= 4;
     // experiment knobs folded into the value: variant = form + 10 * tile code (0 auto, 1: 64, 2: 128, 3: 256) + 100 * workgroups per CU (0 auto = 2)
     int ht_code = 0, wg_per_cu = 0;
@@ -780,12 +791,15 @@ K4Plan backward_plan(int N, const FrameDev& F, const float* d_err, int variant, 
     return pl;
 }
 
-hipError_t score_backward(hipStream_t st, int N, const float* staged_bwd, const FrameDev& F, const float* d_err, const double* g, float clampv,
+hipError_t score_backward(hipStream_t st, int N, const float* staged_bwd, const FrameDev& F, const void* d_err_any, const double* g, float clampv,
                           float tau, float beta, float* grad_part, float* G12_part, const K4Plan& plan, const double* poses, double* grad_xyz,
                           unsigned flags) {
     if (N <= 0) return hipSuccess;
     const int HT = plan.HT, NT = plan.NT;
-    const bool soft = d_err == nullptr;
+    const bool soft = d_err_any == nullptr;
+    const bool f16 = plan.elem == K4_ELEM_F16;
+    if (f16 && (soft || plan.variant <= 0)) return hipErrorInvalidValue;  // half gradient images: the matrix-core form only, nothing takes another form silently
+    const float* d_err = f16 ? nullptr : static_cast<const float*>(d_err_any);  // the VALU form below reads floats
     const float LOG2E = 1.4426950408889634f;
     const float kA = beta * LOG2E, kB = -beta * tau * LOG2E;
     const bool UV = F.uv != nullptr;
@@ -800,19 +814,21 @@ hipError_t score_backward(hipStream_t st, int N, const float* staged_bwd, const 
         const int G = plan.rows;
         const int grid = G * NT;
         const size_t lds = k4m_lds_bytes(HT);
-#define DSAC_K4M(C_, S_, U_, W_)                                                                                                           \
+#define DSAC_K4M(C_, S_, U_, W_, E_)                                                                                                       \
     do {                                                                                                                                    \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score_backward_mfma<C_, S_, U_, W_>),                            \
+        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score_backward_mfma<C_, S_, U_, W_, E_>),                        \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                            \
         if (e_ != hipSuccess) return e_;                                                                                                    \
-        hipLaunchKernelGGL((k_score_backward_mfma<C_, S_, U_, W_>), dim3(grid), dim3(K4_THREADS), lds, st, staged_bwd, F.xyz, F.uv, d_err, g,   \
+        hipLaunchKernelGGL((k_score_backward_mfma<C_, S_, U_, W_, E_>), dim3(grid), dim3(K4_THREADS), lds, st, staged_bwd, F.xyz, F.uv,         \
+                           static_cast<const E_*>(d_err_any), g,                                                                               \
                            grad_part, G12_part, N, F.P, F.W, PT, NT, G, F.fx, F.cx, F.cy, clampv, kA, kB, beta, HT, k_poses, k_direct, flags,   \
                            plan.Nf, F.xyz_stride, F.uv_stride);                                                                                  \
     } while (0)
 #define DSAC_K4M_CH(C_, W_)                                                                              \
     do {                                                                                                 \
-        if (soft) { if (UV) DSAC_K4M(C_, true, true, W_); else DSAC_K4M(C_, true, false, W_); }          \
-        else { if (UV) DSAC_K4M(C_, false, true, W_); else DSAC_K4M(C_, false, false, W_); }             \
+        if (soft) { if (UV) DSAC_K4M(C_, true, true, W_, float); else DSAC_K4M(C_, true, false, W_, float); }          \
+        else if (f16) { if (UV) DSAC_K4M(C_, false, true, W_, _Float16); else DSAC_K4M(C_, false, false, W_, _Float16); } \
+        else { if (UV) DSAC_K4M(C_, false, true, W_, float); else DSAC_K4M(C_, false, false, W_, float); }             \
     } while (0)
         if (plan.variant == 6) DSAC_K4M_CH(2, 4);
         else if (plan.variant == 7) DSAC_K4M_CH(3, 3);

@@ -134,17 +134,21 @@ struct K4Plan {
     bool fused = false;   // round 4: no backward_prep launch -- the main pass derives its records from the poses, the finish kernel dR/drod; G12_part [hyp][row][12]
     bool direct = false;  // ... and (one hypothesis tile) the main pass adds its gradient straight into grad_xyz: no grad_part, no gradient reduction launch
     int Nf = 0;           // frame batch: hypotheses per frame (= HT), 0 = one frame
+    int elem = 0;         // element type of d_err (K4_ELEM_*); K4_ELEM_F16: N x P IEEE binary16, the matrix-core form only (variant > 0, not the soft mode)
 };
+enum { K4_ELEM_F32 = 0, K4_ELEM_F16 = 1 };
 // Nf > 0 (frame batch): N = frames x Nf hypotheses, one hypothesis tile per frame (Nf a multiple of 16, <= 256), gradient per frame (grad_xyz frames x P x 3);
 // plan.variant == 0 then means: not available for a batch
-K4Plan backward_plan(int N, const FrameDev& F, const float* d_err, int variant, int Nf = 0);
+// elem: what d_err points to (K4_ELEM_*).  The half plan is the float plan -- same variant, tiles, rows, fused / direct -- with d_err on an 8-byte address
+// where the float plan wants 16; variant 0 (the VALU form) does not read halves: the caller refuses
+K4Plan backward_plan(int N, const FrameDev& F, const void* d_err, int variant, int Nf = 0, int elem = K4_ELEM_F32);
 bool backward_variant_known(int variant);  // -1 (auto), 0 .. 5, or a form + 10 * tile code + 100 * workgroups per CU (see backward_plan)
 constexpr int BWD_DRDH = 54;  // per hypothesis: dR/drod (27) and Omega_i = (dR/drod_i) R^T (27)
 hipError_t backward_prep(hipStream_t st, int N, const double* poses, const FrameDev& F, float* staged_bwd, double* dRdH /*N x BWD_DRDH*/);
-// K4 main pass.  d_err (N x P) or nullptr with g (N doubles) for the soft-inlier score.
+// K4 main pass.  d_err (N x P floats, or halves with plan.elem == K4_ELEM_F16) or nullptr with g (N doubles) for the soft-inlier score.
 //   grad_part : [hyp_tiles][P*3] floats       G12_part : [partial rows][N][12] floats
 // poses (cv, N x 6) / grad_xyz (P x 3 fp64, accumulated into) / flags: used when plan.fused / plan.direct (staged_bwd and grad_part may then be nullptr)
-hipError_t score_backward(hipStream_t st, int N, const float* staged_bwd, const FrameDev& F, const float* d_err, const double* g,
+hipError_t score_backward(hipStream_t st, int N, const float* staged_bwd, const FrameDev& F, const void* d_err, const double* g,
                           float clampv, float tau, float beta, float* grad_part, float* G12_part, const K4Plan& plan, const double* poses = nullptr,
                           double* grad_xyz = nullptr, unsigned flags = 0);
 // Epilogue: grad_xyz (P x 3 double) += sum over hyp tiles; then per hypothesis G6 = [G9 * dRdH, G3],

@@ -239,7 +239,8 @@ class ScoredFrameBatch:
     draws from the random stream of seed + f, so every frame's result equals the per-image path (TrainStep.forward_backward with seed + f).
 
     err_dtype=torch.float16: K2 writes the error images in half precision (dsac_process_images_begin_f16: half the bytes) and the score model runs on
-    them under torch.autocast; its gradient images are converted to float32 before dsac_score_backward (no K4 reads halves).  Default float32."""
+    them under torch.autocast; its gradient images stay in half precision and go to K4 as they are (dsac_score_backward_f16: no conversion pass, the float
+    call's result on the same values).  Default float32."""
 
     def __init__(self, device=0, frames=8, hyps=256, ref_steps=8, inlier_count=100, thr=10.0, sub_sample=0.01, cam=(525.0, 525.0, 320.0, 240.0), score_net=None,
                  H=CNN_OBJ_PATCHSIZE, W=CNN_OBJ_PATCHSIZE, engine=None, err_dtype=torch.float32):
@@ -284,7 +285,7 @@ class ScoredFrameBatch:
                                            int(perm.shape[0]), int(self.inlier_count), 50, float(int(self.thr)), ptr(r["inlierMaps"]), float(self.sub_sample), 0.001, 2.0, 1.0,
                                            ptr(self.dpnp), ptr(self.grad_xyz), ptr(self.g), None, None))
         self._scores.backward(gradient=self.g.to(self._scores.dtype).clamp_(-CLAMP_E2E, CLAMP_E2E))
-        d = self._err_in.grad.reshape(F * N, H, W).float()  # K4 reads float32 gradient images (a no-op for a float32 model)
+        d = self._err_in.grad.reshape(F * N, H, W)  # float32, or float16 from a half-precision model: K4 reads either (Engine.dScore picks the call)
         # reference-exact seam: gradient images read back transposed (lua_calls.h:329-335) together with dScore's x*cols*3 + y*3 columns -- both or neither
         d_err = (d.transpose(1, 2) if quirk_transpose else d).reshape(F * N, P).contiguous()
         eng.dScore(self.poses, self.sets, d_err, dpnp=self.dpnp, quirk_transpose=quirk_transpose, grad=self.grad_xyz)

@@ -462,18 +462,34 @@ class Engine:
     def dScore(self, poses, sets, d_err, dpnp=None, quirk_transpose=False, grad=None, parity_fp64=False, quirk_rot_writeback=False):
         """dScore part (iii) (cnn_softam.h:609-645) summed over hypotheses (train_ransac_softam.cpp:382-383).
         grad (H*W x 3 float64) is accumulated into and returned.  parity_fp64: the fp64 parity mode (the reference's evaluation order, one lane
-        per hypothesis; reference-sized maps), quirk_rot_writeback: with it, quirk 7 (cnn_softam.h:506-508)."""
+        per hypothesis; reference-sized maps), quirk_rot_writeback: with it, quirk 7 (cnn_softam.h:506-508).
+        A float16 `d_err` (numpy or torch) takes dsac_score_backward_f16: K4 reads the halves as they are (no converted copy) and returns the float call's
+        result on the widened values; the fp64 parity mode does not read halves.  Everything else is the float call."""
         poses = _np(poses, np.float64)
         sets = _np(sets, np.int32)
-        d_err = _np(d_err, np.float32)
+        half = _is_f16(d_err)
+        if half and (parity_fp64 or quirk_rot_writeback):
+            raise ValueError("dsac_amd: parity_fp64 / quirk_rot_writeback read float32 gradient images, d_err is float16")
+        if not half:
+            d_err = _np(d_err, np.float32)
         N = int(sets.shape[0])
         if grad is None:
             grad = np.zeros((getattr(self, "frames", 1) * self.P, 3))  # frame batch: one P x 3 gradient per frame
         flags = (capi.DSAC_BWD_QUIRK_TRANSPOSE if quirk_transpose else 0) | (capi.DSAC_BWD_PARITY_FP64 if (parity_fp64 or quirk_rot_writeback) else 0) | \
                 (capi.DSAC_BWD_QUIRK_ROT_WRITEBACK if quirk_rot_writeback else 0)
-        check(self._ctx, lib.dsac_score_backward(self._ctx, N, ptr(poses), ptr(sets), ptr(d_err), ptr(_np(dpnp, np.float64) if dpnp is not None else None),
-                                                 flags, ptr(grad)))
+        backward = lib.dsac_score_backward_f16 if half else lib.dsac_score_backward
+        check(self._ctx, backward(self._ctx, N, ptr(poses), ptr(sets), ptr(d_err), ptr(_np(dpnp, np.float64) if dpnp is not None else None), flags, ptr(grad)))
         return grad
+
+    def softScoreDErr(self, g, err, d_err, tau=10.0, beta=0.5, clamp=CNN_OBJ_MAXINPUT):
+        """The soft-inlier score's gradient images (dsac_soft_score_derr): d_err[h] = g[h] * d soft[h] / d err[h], 0 where err sits on the clamp.  err and
+        d_err are N x H*W of one dtype, float32 or float16 (numpy or torch): halves take dsac_soft_score_derr_f16 (fp32 arithmetic, rounded on the store)."""
+        if _is_f16(err) != _is_f16(d_err):
+            raise ValueError("dsac_amd: err and d_err must have the same dtype")
+        derr = lib.dsac_soft_score_derr_f16 if _is_f16(err) else lib.dsac_soft_score_derr
+        g = _np(g, np.float64)
+        check(self._ctx, derr(self._ctx, int(g.shape[0]), ptr(g), ptr(err), float(clamp), float(tau), float(beta), ptr(d_err)))
+        return d_err
 
     def dSoftScore(self, poses, sets, g, tau=10.0, beta=0.5, clamp=CNN_OBJ_MAXINPUT, dpnp=None, quirk_transpose=False, grad=None):
         poses = _np(poses, np.float64)

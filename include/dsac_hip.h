@@ -326,9 +326,9 @@ DSAC_API int dsac_reproject(dsac_ctx* ctx, int N, const double* poses, float cla
  * the float build; their values too are the float build's, rounded.
  *   "k2_f16_store" (dsac_set_option)  the store layout of the half build: 0 = four 8-byte stores per lane and 64-cell chunk, 1 (default) = neighbouring lanes trade
  *                 rows so that each issues two 16-byte stores of 8 cells (A/B: scripts/k2_f16_ab.py, profiles/k2_f16_ab.txt); the values do not depend on it.
- * Not part of this: a K4 (dsac_score_backward) that reads half gradient images -- a half-precision score model's d_err is converted to float by the caller
- * (dsac_amd/e2e.py, ScoredFrameBatch); the any-map build and the fp32 / precise / two-piece forms in half; dsac_score_hypotheses*, dsac_process_images and
- * the pipelined pair in half; bf16. */
+ * The backward half of the seam in half precision is dsac_score_backward_f16 (K4 reads a half-precision score model's gradient images as they are).
+ * Not part of this: the any-map build and the fp32 / precise / two-piece forms in half; dsac_score_hypotheses*, dsac_process_images and the pipelined pair
+ * in half; bf16. */
 DSAC_API int dsac_reproject_f16(dsac_ctx* ctx, int N, const double* poses, float clamp, uint16_t* err16, float tau, float beta, double* soft_or_null);
 
 /* ---- K3: softmax / entropy / soft-argmax pose --------------------------------------------------- */
@@ -390,6 +390,21 @@ DSAC_API int dsac_dpnp(dsac_ctx* ctx, int N, const int32_t* sets, float eps, dou
  * batch; under "device_args" = 1 the caller's promise includes that. */
 DSAC_API int dsac_score_backward(dsac_ctx* ctx, int N, const double* poses, const int32_t* sets, const float* d_err, const double* dpnp_or_null,
                         unsigned flags, double* grad_xyz);
+/* The same call on HALF-precision gradient images, the backward twin of dsac_reproject_f16: d_err16 [N][H*W] IEEE binary16, hypothesis-major, a host or a
+ * device pointer (host arrays are staged at 2 bytes per element), non-NULL.  K4's matrix-core form loads a lane's four cells as 8 bytes and widens them in
+ * registers -- exact, subnormal halves included -- on the launch plan the float call would take, so the result is the float call's on the widened values: with
+ * grad_xyz zeroed beforehand bit for bit (on other contents within the last bit of a cell, as two runs of the float call: see Determinism above), and
+ * dsac_last_pose_gradients bit for bit.  Frame batches, DSAC_BWD_QUIRK_TRANSPOSE, the internally computed dPNP, the profile scope, the managed-memory
+ * fallback to the staged form and the accumulation into grad_xyz are dsac_score_backward's.
+ * The half input exists for the matrix-core form only (every "k4_variant" whose form is not 0, the staged 1000 + v and 1999 included).  The call is
+ * DSAC_ERR_INVALID -- nothing is staged or enqueued (not even the dPNP launch), grad_xyz and the count behind dsac_last_pose_gradients keep their values,
+ * dsac_last_error names the condition -- when
+ *   d_err16 is NULL or off an 8-byte address;  DSAC_BWD_PARITY_FP64 (and with it DSAC_BWD_QUIRK_ROT_WRITEBACK) is set;  H*W % 4 != 0;  a frame's xyz or uv
+ *   is off a 16-byte address;  the implicit pixel grid has W % 4 != 0;  "k4_variant" names the VALU form (0, 1000, or either plus a multiple of 10);
+ * and wherever dsac_score_backward refuses (fx != fy, ...).  Nothing takes another form silently.
+ * Not part of this: the VALU and fp64 parity forms in half; bf16. */
+DSAC_API int dsac_score_backward_f16(dsac_ctx* ctx, int N, const double* poses, const int32_t* sets, const uint16_t* d_err16, const double* dpnp_or_null,
+                            unsigned flags, double* grad_xyz);
 /* The backward calls need fx == fy: the reference's Jacobians use the single focal length camMat(0,0) for both axes
  * (core/cnn_softam.h:406,466); a camera with two focal lengths is rejected with DSAC_ERR_INVALID rather than differentiated
  * inconsistently with the forward kernels.  Quirk 7 of the reference (dProjectdHyp writes the re-derived rotation back into the
@@ -409,8 +424,12 @@ DSAC_API int dsac_soft_score_backward(dsac_ctx* ctx, int N, const double* poses,
  * drives the whole score-CNN seam -- error images out, scores in, score gradients out, gradient images in -- and must reproduce the built-in
  * dsac_soft_score_backward to fp32 rounding (tests/test_gpu_seam.py, train_ransac_softam -seam 1). */
 DSAC_API int dsac_soft_score_derr(dsac_ctx* ctx, int N, const double* g, const float* err, float clamp, float tau, float beta, float* d_err);
+/* The same on half-precision images, so that such a host drives the whole seam in half (dsac_process_images_begin_f16 -> this -> dsac_score_backward_f16):
+ * err16 / d_err16 N x H*W IEEE binary16 on 8-byte addresses, 4 | H*W (else DSAC_ERR_INVALID, before anything is staged).  The input is widened to float,
+ * the arithmetic is dsac_soft_score_derr's in fp32, the result is rounded to nearest even on the store (small gradients land in the half subnormals). */
+DSAC_API int dsac_soft_score_derr_f16(dsac_ctx* ctx, int N, const double* g, const uint16_t* err16, float clamp, float tau, float beta, uint16_t* d_err16);
 
-/* The per-hypothesis 1 x 6 pose gradients of the most recent dsac_score_backward / dsac_soft_score_backward call on
+/* The per-hypothesis 1 x 6 pose gradients of the most recent dsac_score_backward / dsac_score_backward_f16 / dsac_soft_score_backward call on
  * this context: G6[h] = sum over cells of d_err[h][p] * dProjectdHyp(p) (the accumulation of core/cnn_softam.h:631-632
  * before its product with dPNP; columns = jp Rodrigues vector, translation in mm).  N must not exceed that call's N. */
 DSAC_API int dsac_last_pose_gradients(dsac_ctx* ctx, int N, double* G6);
@@ -560,8 +579,8 @@ DSAC_API int dsac_process_images_finish(dsac_ctx* ctx, int hyps_per_frame, const
 /* dsac_process_images_begin with the error images in half precision: err16 [frames * hyps_per_frame][H*W] IEEE binary16, non-NULL, each value the float call's
  * rounded to nearest even; poses, sets_out, ok and soft are the float call's bit for bit, "pi_refstream", "pi_defer_tail" and "seed_stride" apply as they do
  * there, and dsac_process_images_finish follows it unchanged.  The conditions, the refusal (checked before K1 is enqueued) and "k2_f16_store" are those of
- * dsac_reproject_f16.  The backward half of the seam stays in float: no K4 reads half gradient images, a half-precision score model's d_err is converted to
- * float before dsac_score_backward. */
+ * dsac_reproject_f16.  The backward half of the seam in half precision is dsac_score_backward_f16: K4 reads a half-precision score model's gradient images as
+ * they are, no conversion pass in between. */
 DSAC_API int dsac_process_images_begin_f16(dsac_ctx* ctx, int hyps_per_frame, uint64_t seed, float thr, int max_tries, float clamp, float tau, float beta,
                                   double* poses, int32_t* sets_out, uint8_t* ok, uint16_t* err16, double* soft_or_null);
 /* The same dependency for ANOTHER stream: `hip_stream` (a hipStream_t of the context's device) waits for the deferred tail that is in flight -- and
