@@ -1855,7 +1855,10 @@ __global__ __launch_bounds__(K3_THREADS) void k_softmax(int N, const double* __r
         const double e = exp(x);
         w[i] = e;
         acc[0] += e;
-        acc[1] += e * (x * 1.4426950408889634);  // e * log2(e); exactly 0 when e underflows, like the reference's w > 0 test
+        // e * log2(e); 0 when e is 0, like the reference's w > 0 test -- also for a score of -inf (a masked hypothesis), where e * x would be 0 * -inf = NaN.
+        // The select sits on x, not on the product, so that the multiply-add below is the one finite scores have always had, bit for bit.
+        const double xl = (e == 0.0) ? 0.0 : x;
+        acc[1] += e * (xl * 1.4426950408889634);
         if (want_avg) {
 #pragma unroll
             for (int k = 0; k < 6; k++) acc[2 + k] += e * poses[6 * (size_t)i + k];

@@ -4,7 +4,7 @@ Both sides run the same fp64 arithmetic (lazy getDiffMap residuals, CvLevMarq st
 libm-vs-ocml last bits, the summation order of the normal equations and the 6x6 solve (L D L^T on the GPU, Gaussian elimination in the oracle).
   refined poses : 1e-7 relative          inlier maps / step counts : identical
   dRefineHyp/Obj: central differences divide LM outputs by 2e-3 / 4, so 1e-4 relative to the largest entry
-  loss, dLossMax: 1e-9
+  loss, dLossMax: 1e-9 at ordinary poses; singular ones (jp angle pi and 0, the exits and clamps of k_pose_loss) have a bound per case: tests/test_gpu_tail_edges.py
 
 Every refinement here starts next to the right pose at thr = 10: about three accepted LM iterations per call and hardly a rejected trial.  The hard
 branches of lm_pnp belong to tests/test_gpu_refine_lm.py (problems from tests/lm_corpus.py, labelled and judged stable by the oracle alone): rejected trials
