@@ -303,6 +303,82 @@ int k2_stage(dsac_ctx* c, hipStream_t st, int N, int Nf, const float* staged, co
     return DSAC_OK;
 }
 
+// The finite-difference stage of K6: the one place the chain plan -> run -> finish (dk::refine_fd_*) is assembled, for the soft-argmax lists (dsac_refine_fd,
+// dsac_backward_path1: one list per frame) and the DSAC variant's (dsac_refine_fd_set / _sets / _sets_frames: one per hypothesis).  fd_stage_check refuses a bad
+// sub_sample or eps by the caller's name before anything is enqueued; fd_stage_begin reserves the replica arrays and the plan's scratch in staging slots (reused
+// once grown) and enqueues plan and run; fd_stage_finish the central differences.  The two halves leave dsac_backward_path1 room for K5 beside the replicas.
+struct FdStage {
+    int skip = 0;
+    float eps_hyp = 0.f, eps_obj = 0.f;  // eps_hyp: the soft-argmax lists only
+    dk::FdLists L{};
+    dk::FdReplicas rep{};
+};
+// eps_hyp: NULL for the DSAC variant
+int fd_stage_check(dsac_ctx* c, const char* who, float sub_sample, const float* eps_hyp, float eps_obj, FdStage* s) {
+    if (eps_hyp) {
+        if (!(sub_sample > 0.f) || !(*eps_hyp > 0.f) || !(eps_obj > 0.f)) return fail(c, DSAC_ERR_INVALID, "%s: sub_sample, eps_hyp, eps_obj must be > 0", who);
+        s->eps_hyp = *eps_hyp;
+    } else if (!(sub_sample > 0.f) || !(eps_obj > 0.f)) return fail(c, DSAC_ERR_INVALID, "%s: sub_sample and eps_obj must be > 0", who);
+    s->eps_obj = eps_obj;
+    s->skip = (int)(1 / sub_sample);  // core/cnn_softam.h:871, core/cnn.h:933
+    if (s->skip < 1) return fail(c, DSAC_ERR_INVALID, "%s: sub_sample > 1", who);
+    return DSAC_OK;
+}
+// init_poses: the start poses (lists x 6) of the soft-argmax lists, sets: the minimal sets (lists x 4) of the DSAC variant's, the other one NULL; planned: an
+// event to record behind the plan
+int fd_stage_begin(dsac_ctx* c, FdStage* s, const dk::FdLists& L, const double* init_poses, const int32_t* sets, const int32_t* maps, const int32_t* perm, int steps,
+                   int max_inl, int min_inl, float thr, int32_t* obj_pixels, int32_t* n_obj, hipEvent_t planned = nullptr) {
+    s->L = L;
+    const size_t B = (size_t)L.replicas() * (size_t)L.lists;
+    DevBuf& rp = next_slot(c); HIP_TRY(c, rp.reserve(B * 6 * sizeof(double)));
+    DevBuf& rx = next_slot(c); HIP_TRY(c, rx.reserve(B * 2 * sizeof(int32_t)));
+    DevBuf& rv = next_slot(c); HIP_TRY(c, rv.reserve(B * sizeof(float)));
+    DevBuf& ro = next_slot(c); HIP_TRY(c, ro.reserve(B * 6 * sizeof(double)));
+    s->rep = {rp.as<double>(), rx.as<int32_t>(), rv.as<float>(), ro.as<double>()};
+    int32_t* plan_scratch = nullptr;
+    if (const size_t ni = dk::refine_fd_plan_scratch_ints(c->F)) {
+        DevBuf& ps = next_slot(c);
+        HIP_TRY(c, ps.reserve(ni * (size_t)L.lists * sizeof(int32_t)));
+        plan_scratch = ps.as<int32_t>();
+    }
+    HIP_TRY(c, dk::refine_fd_plan(c->stream, L, init_poses, sets, maps, c->F, s->skip, s->eps_hyp, s->eps_obj, s->rep, obj_pixels, n_obj, plan_scratch));
+    if (planned) HIP_TRY(c, hipEventRecord(planned, c->stream));
+    HIP_TRY(c, dk::refine_fd_run(c->stream, L, n_obj, perm, steps, max_inl, min_inl, thr, c->F, s->rep));
+    return DSAC_OK;
+}
+int fd_stage_finish(dsac_ctx* c, const FdStage& s, const int32_t* n_obj, double* J_head, double* J_obj) {
+    HIP_TRY(c, dk::refine_fd_finish(c->stream, s.L, s.rep.out, n_obj, s.skip, s.eps_hyp, s.eps_obj, J_head, J_obj));
+    return DSAC_OK;
+}
+
+// K6 over B problems: the split form where it applies (many problems, long walks: a step as two launches, k_refine.hip), else the fused kernel
+int refine_stage(dsac_ctx* c, int B, const double* init, const int32_t* perm, int steps, int max_inl, int min_inl, float thr, const int32_t* pert_px_c,
+                 const float* pert_value, double* out, int32_t* maps, int32_t* steps_done, int map_stride, int per_frame) {
+    if (dk::refine_split_applies(B, c->F, pert_px_c, nullptr, c->k6_waves)) {
+        HIP_TRY(c, c->k6_scratch.reserve(dk::refine_split_scratch_bytes(B, steps, c->F.frames > 1 ? c->F.frames : 1, c->F.P, max_inl)));
+        HIP_TRY(c, dk::refine_split(c->stream, B, init, perm, steps, max_inl, min_inl, thr, c->F, out, maps, steps_done, map_stride, per_frame, c->k6_scratch.p,
+                                    c->k6_walk_exact));
+        return DSAC_OK;
+    }
+    HIP_TRY(c, dk::refine(c->stream, B, init, perm, steps, max_inl, min_inl, thr, pert_px_c, pert_value, c->F, out, maps, steps_done, map_stride, per_frame, nullptr,
+                          nullptr, c->k6_waves));
+    return DSAC_OK;
+}
+
+// K7 behind the four dsac_loss* calls: B estimates against gt_count ground truths (gt_stride, gt_group: dk::pose_loss)
+int loss_common(dsac_ctx* c, size_t B, size_t gt_count, int gt_stride, int gt_group, const double* est_cv6, const double* gt_jp6, double* out4, double* J6_or_null) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    begin_call(c);
+    const double *d_est, *d_gt;
+    double *d_out, *d_J;
+    ARG_TRY(in_arg(c, est_cv6, B * 6, &d_est));
+    ARG_TRY(in_arg(c, gt_jp6, gt_count * 6, &d_gt));
+    ARG_TRY(out_arg(c, out4, B * 4, &d_out));
+    ARG_TRY(out_arg(c, J6_or_null, B * 6, &d_J));
+    HIP_TRY(c, dk::pose_loss(c->stream, (int)B, d_est, d_gt, d_out, d_J, gt_stride, gt_group));
+    return end_call(c);
+}
+
 // Error images only on a big launch: the streaming form WITH the sigmoid arithmetic is the faster kernel -- the arithmetic spaces a wave's stores
 // (N = 4096: 860 us against 890-900 for any form without it; idling the wave instead, k2_flags bits 16-23, does not reproduce the effect:
 // profiles/r04_k2_err_ab.txt).  So the auto policy runs that kernel and drops its partial sums (1200 x N floats of scratch, 0.4 % of the
@@ -1505,14 +1581,7 @@ int dsac_refine(dsac_ctx* c, int B, const double* init_poses, const int32_t* per
     // one frame: the map of problem 0 (H*W counters, += 1 per selection); frame batch: one map per problem (B x H*W)
     ARG_TRY(out_arg(c, inlier_map, frames > 1 ? (size_t)B * P : P, &d_map, /*preload=*/true));
     ARG_TRY(out_arg(c, steps_done, (size_t)B, &d_sd));
-    if (dk::refine_split_applies(B, c->F, d_px, nullptr, c->k6_waves)) {  // many problems, long walks: a step as two launches (k_refine.hip)
-        HIP_TRY(c, c->k6_scratch.reserve(dk::refine_split_scratch_bytes(B, steps, frames > 1 ? frames : 1, (int)P, max_inl)));
-        HIP_TRY(c, dk::refine_split(c->stream, B, d_init, d_perm, steps, max_inl, min_inl, thr, c->F, d_out, d_map, d_sd, frames > 1 ? (int)P : 0,
-                                    frames > 1 ? B / frames : 0, c->k6_scratch.p, c->k6_walk_exact));
-        return end_call(c);
-    }
-    HIP_TRY(c, dk::refine(c->stream, B, d_init, d_perm, steps, max_inl, min_inl, thr, d_px, d_pv, c->F, d_out, d_map, d_sd, frames > 1 ? (int)P : 0,
-                          frames > 1 ? B / frames : 0, nullptr, nullptr, c->k6_waves));
+    ARG_TRY(refine_stage(c, B, d_init, d_perm, steps, max_inl, min_inl, thr, d_px, d_pv, d_out, d_map, d_sd, frames > 1 ? (int)P : 0, frames > 1 ? B / frames : 0));
     return end_call(c);
 }
 
@@ -1525,9 +1594,8 @@ int dsac_refine_fd(dsac_ctx* c, const double* init_pose, const int32_t* perm, in
     if (!init_pose || !perm || !inlier_map || !J_hyp || !obj_pixels || !J_obj || !n_obj || cap < 0 || steps < 0)
         return fail(c, DSAC_ERR_INVALID, "dsac_refine_fd: NULL argument or negative count");
     if (max_inl < 1 || max_inl > 256) return fail(c, DSAC_ERR_INVALID, "dsac_refine_fd: need 1 <= max_inl <= 256");
-    if (!(sub_sample > 0.f) || !(eps_hyp > 0.f) || !(eps_obj > 0.f)) return fail(c, DSAC_ERR_INVALID, "dsac_refine_fd: sub_sample, eps_hyp, eps_obj must be > 0");
-    const int skip = (int)(1 / sub_sample);  // core/cnn_softam.h:871
-    if (skip < 1) return fail(c, DSAC_ERR_INVALID, "dsac_refine_fd: sub_sample > 1");
+    FdStage fd;
+    ARG_TRY(fd_stage_check(c, "dsac_refine_fd", sub_sample, &eps_hyp, eps_obj, &fd));
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c);
     const size_t P = (size_t)c->F.P;
@@ -1543,40 +1611,16 @@ int dsac_refine_fd(dsac_ctx* c, const double* init_pose, const int32_t* perm, in
     ARG_TRY(out_arg(c, obj_pixels, Fz * (size_t)cap, &d_px));
     ARG_TRY(out_arg(c, J_obj, Fz * (size_t)cap * 18, &d_Jo));
     ARG_TRY(out_arg(c, n_obj, Fz, &d_n));
-    const size_t B = (12 + 6 * (size_t)cap) * Fz;
-    DevBuf& rp = next_slot(c); HIP_TRY(c, rp.reserve(B * 6 * sizeof(double)));
-    DevBuf& rx = next_slot(c); HIP_TRY(c, rx.reserve(B * 2 * sizeof(int32_t)));
-    DevBuf& rv = next_slot(c); HIP_TRY(c, rv.reserve(B * sizeof(float)));
-    DevBuf& ro = next_slot(c); HIP_TRY(c, ro.reserve(B * 6 * sizeof(double)));
-    DevBuf& px = next_slot(c); HIP_TRY(c, px.reserve(((size_t)cap * Fz + 1) * sizeof(int32_t)));
-    int32_t* d_pxbuf = d_px ? d_px : px.as<int32_t>();
-    int32_t* plan_scratch = nullptr;
-    if (const size_t ni = dk::refine_fd_plan_scratch_ints(c->F)) {
-        DevBuf& ps = next_slot(c);
-        HIP_TRY(c, ps.reserve(ni * Fz * sizeof(int32_t)));
-        plan_scratch = ps.as<int32_t>();
-    }
-    HIP_TRY(c, dk::refine_fd_plan(c->stream, d_init, d_map, c->F, skip, eps_hyp, eps_obj, cap, rp.as<double>(), rx.as<int32_t>(), rv.as<float>(), d_pxbuf, d_n,
-                                  plan_scratch, frames, cap));
-    HIP_TRY(c, dk::refine_fd_run(c->stream, cap, d_n, rp.as<double>(), d_perm, steps, max_inl, min_inl, thr, rx.as<int32_t>(), rv.as<float>(), c->F, ro.as<double>(),
-                                 frames));
-    HIP_TRY(c, dk::refine_fd_finish(c->stream, ro.as<double>(), d_n, cap, skip, eps_hyp, eps_obj, d_Jh, d_Jo, frames));
+    ARG_TRY(fd_stage_begin(c, &fd, {dk::FD_HEAD_POSE, frames, cap, cap, /*list_is_frame=*/true, nullptr}, d_init, nullptr, d_map, d_perm, steps, max_inl, min_inl, thr,
+                           d_px, d_n));
+    ARG_TRY(fd_stage_finish(c, fd, d_n, d_Jh, d_Jo));
     return end_call(c);
 }
 
 int dsac_loss(dsac_ctx* c, const double* est_cv6, const double* gt_jp6, double* out4, double* J6_or_null) {
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_loss: ctx is NULL");
     if (!est_cv6 || !gt_jp6 || (!out4 && !J6_or_null)) return fail(c, DSAC_ERR_INVALID, "dsac_loss: NULL argument");
-    HIP_TRY(c, hipSetDevice(c->device));
-    begin_call(c);
-    const double *d_est, *d_gt;
-    double *d_out, *d_J;
-    ARG_TRY(in_arg(c, est_cv6, 6, &d_est));
-    ARG_TRY(in_arg(c, gt_jp6, 6, &d_gt));
-    ARG_TRY(out_arg(c, out4, 4, &d_out));
-    ARG_TRY(out_arg(c, J6_or_null, 6, &d_J));
-    HIP_TRY(c, dk::pose_loss(c->stream, 1, d_est, d_gt, d_out, d_J));
-    return end_call(c);
+    return loss_common(c, 1, 1, 0, 1, est_cv6, gt_jp6, out4, J6_or_null);
 }
 
 static int refine_fd_sets_common(dsac_ctx* c, const char* who, int M, const int32_t* sets, const int32_t* frame_of_or_null, const int32_t* perm, int steps, int max_inl,
@@ -1590,11 +1634,10 @@ static int refine_fd_sets_common(dsac_ctx* c, const char* who, int M, const int3
     if (frames > 1 && !frame_of_or_null && M % frames != 0)
         return fail(c, DSAC_ERR_INVALID, "%s: with a frame batch M must be frames x (hypotheses per frame) -- or give every hypothesis its frame (dsac_refine_fd_sets_frames)", who);
     if (max_inl < 1 || max_inl > 256) return fail(c, DSAC_ERR_INVALID, "%s: need 1 <= max_inl <= 256", who);
-    if (!(sub_sample > 0.f) || !(eps_obj > 0.f)) return fail(c, DSAC_ERR_INVALID, "%s: sub_sample and eps_obj must be > 0", who);
-    const int skip = (int)(1 / sub_sample);  // core/cnn.h:933
-    if (skip < 1) return fail(c, DSAC_ERR_INVALID, "%s: sub_sample > 1", who);
+    FdStage fd;
+    ARG_TRY(fd_stage_check(c, who, sub_sample, nullptr, eps_obj, &fd));
     if (M == 0) return DSAC_OK;
-    const size_t R = 18 + 6 * (size_t)cap, B = R * (size_t)M;
+    const size_t B = (18 + 6 * (size_t)cap) * (size_t)M;
     if (B > (1u << 26)) return fail(c, DSAC_ERR_INVALID, "%s: M * (18 + 6*cap) = %zu replicas is too many", who, B);
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c);
@@ -1626,21 +1669,9 @@ static int refine_fd_sets_common(dsac_ctx* c, const char* who, int M, const int3
     ARG_TRY(out_arg(c, obj_pixels, (size_t)M * cap, &d_px));
     ARG_TRY(out_arg(c, J_obj, (size_t)M * cap * 18, &d_Jo));
     ARG_TRY(out_arg(c, n_obj, (size_t)M, &d_n));
-    DevBuf& rp = next_slot(c); HIP_TRY(c, rp.reserve(B * 6 * sizeof(double)));
-    DevBuf& rx = next_slot(c); HIP_TRY(c, rx.reserve(B * 2 * sizeof(int32_t)));
-    DevBuf& rv = next_slot(c); HIP_TRY(c, rv.reserve(B * sizeof(float)));
-    DevBuf& ro = next_slot(c); HIP_TRY(c, ro.reserve(B * 6 * sizeof(double)));
-    int32_t* plan_scratch = nullptr;
-    if (const size_t ni = dk::refine_fd_plan_scratch_ints(c->F)) {
-        DevBuf& ps = next_slot(c);
-        HIP_TRY(c, ps.reserve(ni * (size_t)M * sizeof(int32_t)));
-        plan_scratch = ps.as<int32_t>();
-    }
-    HIP_TRY(c, dk::refine_fd_plan_set(c->stream, d_sets, d_maps, c->F, skip, eps_obj, cap, rp.as<double>(), rx.as<int32_t>(), rv.as<float>(), d_px, d_n, M,
-                                      plan_scratch, d_fof));
-    HIP_TRY(c, dk::refine_fd_run_set(c->stream, cap, d_n, rp.as<double>(), d_perm, steps, max_inl, min_inl, thr, rx.as<int32_t>(), rv.as<float>(), c->F,
-                                     ro.as<double>(), M, d_fof));
-    HIP_TRY(c, dk::refine_fd_finish_set(c->stream, ro.as<double>(), d_n, cap, skip, eps_obj, d_Js, d_Jo, M));
+    ARG_TRY(fd_stage_begin(c, &fd, {dk::FD_HEAD_SET, M, cap, cap, /*list_is_frame=*/false, d_fof}, nullptr, d_sets, d_maps, d_perm, steps, max_inl, min_inl, thr, d_px,
+                           d_n));
+    ARG_TRY(fd_stage_finish(c, fd, d_n, d_Js, d_Jo));
     return end_call(c);
 }
 
@@ -1683,16 +1714,7 @@ int dsac_loss_batch(dsac_ctx* c, int B, const double* est_cv6, const double* gt_
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_loss_batch: ctx is NULL");
     if (B < 0 || !est_cv6 || !gt_jp6 || (!out4 && !J6_or_null)) return fail(c, DSAC_ERR_INVALID, "dsac_loss_batch: NULL argument or negative count");
     if (B == 0) return DSAC_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    begin_call(c);
-    const double *d_est, *d_gt;
-    double *d_out, *d_J;
-    ARG_TRY(in_arg(c, est_cv6, (size_t)B * 6, &d_est));
-    ARG_TRY(in_arg(c, gt_jp6, 6, &d_gt));
-    ARG_TRY(out_arg(c, out4, (size_t)B * 4, &d_out));
-    ARG_TRY(out_arg(c, J6_or_null, (size_t)B * 6, &d_J));
-    HIP_TRY(c, dk::pose_loss(c->stream, B, d_est, d_gt, d_out, d_J));
-    return end_call(c);
+    return loss_common(c, B, 1, 0, 1, est_cv6, gt_jp6, out4, J6_or_null);
 }
 
 int dsac_refine_all(dsac_ctx* c, int N, const double* init_poses, const int32_t* perm, int steps, int max_inl, int min_inl, float thr,
@@ -1720,13 +1742,9 @@ int dsac_refine_all(dsac_ctx* c, int N, const double* init_poses, const int32_t*
     ARG_TRY(out_arg(c, inlier_maps_or_null, (size_t)N * P, &d_maps, /*preload=*/false));
     ARG_TRY(out_arg(c, steps_done_or_null, (size_t)N, &d_sd));
     if (d_maps) HIP_TRY(c, hipMemsetAsync(d_maps, 0, (size_t)N * P * sizeof(int32_t), c->stream));
-    if (dk::refine_split_applies(N, c->F, nullptr, nullptr, c->k6_waves)) {  // the DSAC variant on a big map: every hypothesis walks most of it -- walk and LM as separate launches
-        HIP_TRY(c, c->k6_scratch.reserve(dk::refine_split_scratch_bytes(N, steps, frames_ra > 1 ? frames_ra : 1, (int)P, max_inl)));
-        HIP_TRY(c, dk::refine_split(c->stream, N, d_init, d_perm, steps, max_inl, min_inl, thr, c->F, d_out, d_maps, d_sd, d_maps ? (int)P : 0,
-                                    frames_ra > 1 ? N / frames_ra : 0, c->k6_scratch.p, c->k6_walk_exact));
-    } else
-    HIP_TRY(c, dk::refine(c->stream, N, d_init, d_perm, steps, max_inl, min_inl, thr, nullptr, nullptr, c->F, d_out, d_maps, d_sd, d_maps ? (int)P : 0,
-                          frames_ra > 1 ? N / frames_ra : 0, nullptr, nullptr, c->k6_waves));
+    // (the DSAC variant on a big map: every hypothesis walks most of it -- the split form)
+    ARG_TRY(refine_stage(c, N, d_init, d_perm, steps, max_inl, min_inl, thr, nullptr, nullptr, d_out, d_maps, d_sd, d_maps ? (int)P : 0,
+                         frames_ra > 1 ? N / frames_ra : 0));
     if (d_maps && d_sets) HIP_TRY(c, dk::zero_set_cells(c->stream, N, d_sets, (int)P, d_maps));
     return end_call(c);
 }
@@ -1739,41 +1757,8 @@ int dsac_refine_fd_set(dsac_ctx* c, const int32_t* set4, const int32_t* perm, in
     if (c->F.frames > 1) return fail(c, DSAC_ERR_INVALID, "dsac_refine_fd_set: a frame batch is set (one hypothesis: dsac_set_frame of its image, or dsac_refine_fd_sets_frames)");
     if (!set4 || !perm || !inlier_map || !J_set || !obj_pixels || !J_obj || !n_obj || cap < 0 || steps < 0)
         return fail(c, DSAC_ERR_INVALID, "dsac_refine_fd_set: NULL argument or negative count");
-    if (max_inl < 1 || max_inl > 256) return fail(c, DSAC_ERR_INVALID, "dsac_refine_fd_set: need 1 <= max_inl <= 256");
-    if (!(sub_sample > 0.f) || !(eps_obj > 0.f)) return fail(c, DSAC_ERR_INVALID, "dsac_refine_fd_set: sub_sample and eps_obj must be > 0");
-    const int skip = (int)(1 / sub_sample);  // core/cnn.h:933
-    if (skip < 1) return fail(c, DSAC_ERR_INVALID, "dsac_refine_fd_set: sub_sample > 1");
-    HIP_TRY(c, hipSetDevice(c->device));
-    begin_call(c);
-    const size_t P = (size_t)c->F.P;
-    const int32_t *d_set, *d_perm, *d_map;
-    double *d_Js, *d_Jo;
-    int32_t *d_px, *d_n;
-    ARG_TRY(in_arg(c, set4, 4, &d_set));
-    ARG_TRY(in_arg(c, perm, (size_t)steps * P, &d_perm));
-    ARG_TRY(in_arg(c, inlier_map, P, &d_map));
-    ARG_TRY(out_arg(c, J_set, 54, &d_Js));
-    ARG_TRY(out_arg(c, obj_pixels, (size_t)cap, &d_px));
-    ARG_TRY(out_arg(c, J_obj, (size_t)cap * 18, &d_Jo));
-    ARG_TRY(out_arg(c, n_obj, 1, &d_n));
-    const size_t B = 18 + 6 * (size_t)cap;
-    DevBuf& rp = next_slot(c); HIP_TRY(c, rp.reserve(B * 6 * sizeof(double)));
-    DevBuf& rx = next_slot(c); HIP_TRY(c, rx.reserve(B * 2 * sizeof(int32_t)));
-    DevBuf& rv = next_slot(c); HIP_TRY(c, rv.reserve(B * sizeof(float)));
-    DevBuf& ro = next_slot(c); HIP_TRY(c, ro.reserve(B * 6 * sizeof(double)));
-    DevBuf& px = next_slot(c); HIP_TRY(c, px.reserve(((size_t)cap + 1) * sizeof(int32_t)));
-    int32_t* d_pxbuf = d_px ? d_px : px.as<int32_t>();
-    int32_t* plan_scratch = nullptr;
-    if (const size_t ni = dk::refine_fd_plan_scratch_ints(c->F)) {
-        DevBuf& ps = next_slot(c);
-        HIP_TRY(c, ps.reserve(ni * sizeof(int32_t)));
-        plan_scratch = ps.as<int32_t>();
-    }
-    HIP_TRY(c, dk::refine_fd_plan_set(c->stream, d_set, d_map, c->F, skip, eps_obj, cap, rp.as<double>(), rx.as<int32_t>(), rv.as<float>(), d_pxbuf, d_n, 1,
-                                      plan_scratch));
-    HIP_TRY(c, dk::refine_fd_run_set(c->stream, cap, d_n, rp.as<double>(), d_perm, steps, max_inl, min_inl, thr, rx.as<int32_t>(), rv.as<float>(), c->F, ro.as<double>()));
-    HIP_TRY(c, dk::refine_fd_finish_set(c->stream, ro.as<double>(), d_n, cap, skip, eps_obj, d_Js, d_Jo));
-    return end_call(c);
+    return refine_fd_sets_common(c, "dsac_refine_fd_set", 1, set4, nullptr, perm, steps, max_inl, min_inl, thr, inlier_map, sub_sample, eps_obj, J_set, obj_pixels, J_obj,
+                                 cap, n_obj);
 }
 
 int dsac_backward_path1(dsac_ctx* c, int N, const double* poses, const int32_t* sets, const double* w, const double* avg_cv6, const double* ref_cv6,
@@ -1789,9 +1774,8 @@ int dsac_backward_path1(dsac_ctx* c, int N, const double* poses, const int32_t* 
     if (!poses || !sets || !w || !avg_cv6 || !ref_cv6 || !gt_jp6 || !perm || !inlier_map || !grad_xyz || !g || steps < 0)
         return fail(c, DSAC_ERR_INVALID, "dsac_backward_path1: NULL argument or bad count");
     if (max_inl < 1 || max_inl > 256) return fail(c, DSAC_ERR_INVALID, "dsac_backward_path1: need 1 <= max_inl <= 256");
-    if (!(sub_sample > 0.f) || !(eps_hyp > 0.f) || !(eps_obj > 0.f)) return fail(c, DSAC_ERR_INVALID, "dsac_backward_path1: sub_sample, eps_hyp, eps_obj must be > 0");
-    const int skip = (int)(1 / sub_sample);  // core/cnn_softam.h:871
-    if (skip < 1) return fail(c, DSAC_ERR_INVALID, "dsac_backward_path1: sub_sample > 1");
+    FdStage fd;
+    ARG_TRY(fd_stage_check(c, "dsac_backward_path1", sub_sample, &eps_hyp, eps_obj, &fd));
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c);
     const size_t P = (size_t)c->F.P, Fz = (size_t)frames;
@@ -1813,20 +1797,15 @@ int dsac_backward_path1(dsac_ctx* c, int N, const double* poses, const int32_t* 
     ARG_TRY(out_arg(c, dL_out_or_null, Fz * 6, &d_dL));
     ARG_TRY(out_arg(c, v6_out_or_null, Fz * 6, &d_v6));
     // the inlier map holds at most steps * max_inl hits, every skip-th of them is differentiated
-    const int cap = (int)std::min<size_t>(4096, (size_t)steps * (size_t)max_inl / (size_t)skip + 1);
-    const size_t R = 12 + 6 * (size_t)cap, B = R * Fz;
-    DevBuf& sc = next_slot(c);  // per frame: dL 6 | out4 4 | v6 6 | J_hyp 36 | J_obj cap*18 ; then rep poses B*6 | rep out B*6   (doubles)
-    const size_t nd = Fz * (6 + 4 + 6 + 36 + (size_t)cap * 18) + B * 6 + B * 6;
-    HIP_TRY(c, sc.reserve(nd * sizeof(double)));
+    const int cap = (int)std::min<size_t>(4096, (size_t)steps * (size_t)max_inl / (size_t)fd.skip + 1);
+    DevBuf& sc = next_slot(c);  // per frame: dL 6 | out4 4 | v6 6 | J_hyp 36 | J_obj cap*18  (doubles)
+    HIP_TRY(c, sc.reserve(Fz * (6 + 4 + 6 + 36 + (size_t)cap * 18) * sizeof(double)));
     double* base = sc.as<double>();
     double *s_dL = d_dL ? d_dL : base, *s_out4 = base + Fz * 6, *s_v6 = d_v6 ? d_v6 : base + Fz * 10, *s_Jh = base + Fz * 16, *s_Jo = base + Fz * 52;
-    double *s_rp = s_Jo + Fz * (size_t)cap * 18, *s_ro = s_rp + B * 6;
-    DevBuf& si = next_slot(c);  // rep px/c B*2 | obj pixels frames*cap + 1 | n frames  (int32) ; rep value B (float)
-    HIP_TRY(c, si.reserve((B * 2 + Fz * (size_t)cap + 1 + Fz) * sizeof(int32_t) + B * sizeof(float)));
-    int32_t* s_rx = si.as<int32_t>();
-    int32_t* s_px = s_rx + B * 2;
+    DevBuf& si = next_slot(c);  // obj pixels frames*cap + 1 | n frames  (int32)
+    HIP_TRY(c, si.reserve((Fz * (size_t)cap + 1 + Fz) * sizeof(int32_t)));
+    int32_t* s_px = si.as<int32_t>();
     int32_t* s_n = s_px + Fz * (size_t)cap + 1;
-    float* s_rv = reinterpret_cast<float*>(s_n + Fz);
     if (!d_dpnp) {
         DevBuf& sd = next_slot(c);
         HIP_TRY(c, sd.reserve((size_t)N * 72 * sizeof(double)));
@@ -1843,17 +1822,11 @@ int dsac_backward_path1(dsac_ctx* c, int N, const double* poses, const int32_t* 
     // dLossMax at the refined pose (train_ransac_softam.cpp:301-304), one ground truth per frame
     HIP_TRY(c, dk::pose_loss(c->stream, frames, d_ref, d_gt, s_out4, s_dL, 6));
     // dRefineObj / dRefineHyp as one batch of finite-difference replicas (:307-341)
-    int32_t* plan_scratch = nullptr;
-    if (const size_t ni = dk::refine_fd_plan_scratch_ints(c->F)) {
-        DevBuf& ps = next_slot(c);
-        HIP_TRY(c, ps.reserve(ni * Fz * sizeof(int32_t)));
-        plan_scratch = ps.as<int32_t>();
-    }
-    HIP_TRY(c, dk::refine_fd_plan(c->stream, d_avg, d_map, c->F, skip, eps_hyp, eps_obj, cap, s_rp, s_rx, s_rv, s_px, s_n, plan_scratch, frames, cap));
     // the two cross-stream hand-overs cost ~7 us each (profiles/r05_k5_side_stream.txt): worth it from about 3 000 minimal sets (K5: 10 ns per set)
     const bool k5_beside = N >= 3072;
-    if (k5_beside) HIP_TRY(c, hipEventRecord(c->bwd_fork, c->stream));  // the fork point is the end of the plan: K5 becomes eligible together with the replicas ...
-    HIP_TRY(c, dk::refine_fd_run(c->stream, cap, s_n, s_rp, d_perm, steps, max_inl, min_inl, thr, s_rx, s_rv, c->F, s_ro, frames));
+    // the fork point is the end of the plan: K5 becomes eligible together with the replicas ...
+    ARG_TRY(fd_stage_begin(c, &fd, {dk::FD_HEAD_POSE, frames, cap, cap, /*list_is_frame=*/true, nullptr}, d_avg, nullptr, d_map, d_perm, steps, max_inl, min_inl, thr, s_px,
+                           s_n, k5_beside ? c->bwd_fork : nullptr));
     // ... but is enqueued behind them: the replicas' few hundred waves take their SIMDs first, K5's thousands fill in around them (launched in front,
     // K5 held every wave slot for its first 20 us and the chain started late: 127 against 101 us, nothing gained)
     if (k5_beside) {
@@ -1861,7 +1834,7 @@ int dsac_backward_path1(dsac_ctx* c, int N, const double* poses, const int32_t* 
         HIP_TRY(c, dk::dpnp(c->bwd_side, N, d_sets, c->F, 0.1f, d_dpnp, Nf));
         HIP_TRY(c, hipEventRecord(c->bwd_join, c->bwd_side));
     }
-    HIP_TRY(c, dk::refine_fd_finish(c->stream, s_ro, s_n, cap, skip, eps_hyp, eps_obj, s_Jh, s_Jo, frames));
+    ARG_TRY(fd_stage_finish(c, fd, s_n, s_Jh, s_Jo));
     HIP_TRY(c, dk::path1_assemble(c->stream, s_dL, s_Jh, s_px, s_Jo, s_n, cap, (int)P, d_grad, s_v6, frames, cap));
     // sum_h w_h dPNP_h to the support points and the softmax backward (:344-376)
     if (k5_beside) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->bwd_join, 0));
@@ -1892,16 +1865,7 @@ int dsac_loss_frames(dsac_ctx* c, int B, const double* est_cv6, const double* gt
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_loss_frames: ctx is NULL");
     if (B < 0 || !est_cv6 || !gt_jp6 || (!out4 && !J6_or_null)) return fail(c, DSAC_ERR_INVALID, "dsac_loss_frames: NULL argument or negative count");
     if (B == 0) return DSAC_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    begin_call(c);
-    const double *d_est, *d_gt;
-    double *d_out, *d_J;
-    ARG_TRY(in_arg(c, est_cv6, (size_t)B * 6, &d_est));
-    ARG_TRY(in_arg(c, gt_jp6, (size_t)B * 6, &d_gt));
-    ARG_TRY(out_arg(c, out4, (size_t)B * 4, &d_out));
-    ARG_TRY(out_arg(c, J6_or_null, (size_t)B * 6, &d_J));
-    HIP_TRY(c, dk::pose_loss(c->stream, B, d_est, d_gt, d_out, d_J, 6));
-    return end_call(c);
+    return loss_common(c, B, B, 6, 1, est_cv6, gt_jp6, out4, J6_or_null);
 }
 
 int dsac_loss_batch_frames(dsac_ctx* c, int frames, int per_frame, const double* est_cv6, const double* gt_jp6, double* out4, double* J6_or_null) {
@@ -1909,17 +1873,7 @@ int dsac_loss_batch_frames(dsac_ctx* c, int frames, int per_frame, const double*
     if (frames < 0 || per_frame <= 0 || !est_cv6 || !gt_jp6 || (!out4 && !J6_or_null)) return fail(c, DSAC_ERR_INVALID, "dsac_loss_batch_frames: NULL argument or bad count");
     if ((long long)frames * per_frame > (1ll << 26)) return fail(c, DSAC_ERR_INVALID, "dsac_loss_batch_frames: too many estimates");
     if (frames == 0) return DSAC_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    begin_call(c);
-    const size_t B = (size_t)frames * per_frame;
-    const double *d_est, *d_gt;
-    double *d_out, *d_J;
-    ARG_TRY(in_arg(c, est_cv6, B * 6, &d_est));
-    ARG_TRY(in_arg(c, gt_jp6, (size_t)frames * 6, &d_gt));
-    ARG_TRY(out_arg(c, out4, B * 4, &d_out));
-    ARG_TRY(out_arg(c, J6_or_null, B * 6, &d_J));
-    HIP_TRY(c, dk::pose_loss(c->stream, (int)B, d_est, d_gt, d_out, d_J, 6, per_frame));
-    return end_call(c);
+    return loss_common(c, (size_t)frames * per_frame, frames, 6, per_frame, est_cv6, gt_jp6, out4, J6_or_null);
 }
 
 int dsac_select_frames(dsac_ctx* c, int frames, int N, const double* probs, const double* losses, int loss_stride, const double* u, int32_t* hyp_idx_or_null,

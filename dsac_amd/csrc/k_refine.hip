@@ -1068,8 +1068,8 @@ hipError_t zero_set_cells(hipStream_t st, int N, const int32_t* sets, int P, int
 }
 
 // --------------------------------------------------------------------------------------------------
-// Replica plan of dRefineHyp (12 replicas) + dRefineObj (6 per selected cell).  One wave scans inlier_map in
-// the reference's x-outer / y-inner order (core/cnn_softam.h:873-882) and keeps every skip-th inlier cell.
+// Replica plan of a batch of lists (FdLists): the head replicas of a list, then 6 per selected cell.  inlier_map is scanned in
+// the reference's x-outer / y-inner order (core/cnn_softam.h:873-882) and every skip-th inlier cell is kept.
 // --------------------------------------------------------------------------------------------------
 // Parallel form of the column-major scan: PLAN_THREADS threads own consecutive segments of the scan order t = x * H + y, count their
 // inlier cells, an LDS prefix sum turns the counts into each segment's starting inCount, and a second walk selects: the k-th inlier
@@ -1095,60 +1095,104 @@ DM_INLINE int plan_segment_prefix(const int32_t* __restrict__ inlier_map, const 
     return s_cnt[tid] - cnt;  // exclusive prefix = inCount before this segment
 }
 
-__global__ __launch_bounds__(PLAN_THREADS) void k_refine_fd_plan(const double* __restrict__ init_pose, const int32_t* __restrict__ inlier_map, FrameDev F,
-                                                                 int skip, float eps_hyp, float eps_obj, int cap, double* __restrict__ rep_poses,
-                                                                 int32_t* __restrict__ rep_px_c, float* __restrict__ rep_value,
-                                                                 int32_t* __restrict__ obj_pixels, int32_t* __restrict__ n_obj, int px_stride) {
-    __shared__ int s_cnt[PLAN_THREADS];
-    const int lane = threadIdx.x;
-    {   // frame f of a batch (blockIdx.x): its start pose, inlier map, coordinate map and slice of the replica arrays (12 + 6*cap replicas per frame)
-        const size_t f = blockIdx.x, R = 12 + 6 * (size_t)cap;
-        init_pose += 6 * f; inlier_map += f * F.P; F.xyz += (long long)f * F.xyz_stride;
-        rep_poses += f * R * 6; rep_px_c += f * R * 2; rep_value += f * R; obj_pixels += f * px_stride; n_obj += f;
-    }
-    double init[6];
+// ---- the replicas of a list, written once for both plan forms -----------------------------------------------------------------------
+// SET = false, soft-argmax (dRefineHyp + dRefineObj): FD_HEAD_POSE head replicas perturb the start pose, and every replica starts from it.
+// SET = true, the DSAC variant (dRefine, below): FD_HEAD_SET head replicas perturb the minimal set; k_refine_fd_init_set writes the start poses later.
+template <bool SET>
+constexpr int fd_head() { return SET ? FD_HEAD_SET : FD_HEAD_POSE; }
+
+// list m of a batch as the plan kernels see it: its minimal set (SET), inlier map and slice of the replica arrays (fd_head + 6*cap replicas per list)
+struct FdList {
+    const int32_t *set4, *inlier_map;
+    double* rep_poses;
+    int32_t* rep_px_c;
+    float* rep_value;
+    int32_t *obj_pixels, *n_obj;
+    double init[6];  // !SET: the start pose
+};
+// also moves F.xyz to the list's frame: the perturbed values are read from the frame's own map
+template <bool SET>
+DM_INLINE FdList fd_list(const FdLists& L, size_t m, FrameDev& F, const double* init_pose, const int32_t* set4, const int32_t* inlier_map, double* rep_poses,
+                         int32_t* rep_px_c, float* rep_value, int32_t* obj_pixels, int32_t* n_obj) {
+    const size_t R = fd_head<SET>() + 6 * (size_t)L.cap;
+    const int f = L.frame_of ? clamp_frame(L.frame_of[m], F) : L.list_is_frame ? (int)m : 0;
+    F.xyz += (long long)f * F.xyz_stride;
+    FdList l = {SET ? set4 + 4 * m : nullptr, inlier_map + m * F.P, rep_poses + m * R * 6, rep_px_c + m * R * 2, rep_value + m * R,
+                obj_pixels + m * (size_t)L.px_stride, n_obj + m, {0, 0, 0, 0, 0, 0}};
+    if (!SET) {
 #pragma unroll
-    for (int i = 0; i < 6; i++) init[i] = init_pose[i];
-    // dRefineHyp: replica 2i = +step on parameter i, 2i+1 = (+step) - 2 step  (double arithmetic, :758-772,798-812)
-    if (lane < 12) {
-        const int i = lane >> 1;
+        for (int i = 0; i < 6; i++) l.init[i] = init_pose[6 * m + i];
+    }
+    return l;
+}
+
+// head replica r < fd_head<SET>()
+template <bool SET>
+DM_INLINE void emit_head_replica(int r, const FdList& l, const FrameDev& F, float eps_hyp, float eps_obj) {
+    if (SET) {  // (point pt, channel c, +/-) of the first three set points
+        const int pt = r / 6, c = (r % 6) >> 1;
+        const int p = min(max(l.set4[pt], 0), F.P - 1);
+        const float vf = F.xyz[(size_t)p * 3 + c] + eps_obj;
+        l.rep_px_c[2 * r] = p; l.rep_px_c[2 * r + 1] = c;
+        l.rep_value[r] = (r & 1) ? vf - 2 * eps_obj : vf;
+    } else {    // dRefineHyp: replica 2i = +step on parameter i, 2i+1 = (+step) - 2 step  (double arithmetic, core/cnn_softam.h:758-772,798-812)
+        const int i = r >> 1;
         const double step = (i < 3) ? (double)eps_hyp : (double)(eps_hyp * 1000);
-        double pose[6];
 #pragma unroll
-        for (int k = 0; k < 6; k++) pose[k] = init[k];
-        double v = init[i] + step;
-        if (lane & 1) v -= 2 * step;
-#pragma unroll
-        for (int k = 0; k < 6; k++) rep_poses[(size_t)lane * 6 + k] = (k == i) ? v : pose[k];
-        rep_px_c[2 * lane] = -1; rep_px_c[2 * lane + 1] = 0; rep_value[lane] = 0.f;
+        for (int k = 0; k < 6; k++) {
+            double v = l.init[k];
+            if (k == i) { v += step; if (r & 1) v -= 2 * step; }
+            l.rep_poses[(size_t)r * 6 + k] = v;
+        }
+        l.rep_px_c[2 * r] = -1; l.rep_px_c[2 * r + 1] = 0; l.rep_value[r] = 0.f;
     }
-    // dRefineObj: column-major scan
+}
+
+// the six replicas of selected inlier cell p, selection number `slot` (dRefineObj)
+template <bool SET>
+DM_INLINE void emit_obj_replicas(int slot, int p, const FdList& l, const FrameDev& F, float eps_obj) {
+    l.obj_pixels[slot] = p;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const float v0 = F.xyz[(size_t)p * 3 + c];
+        const float vf = v0 + eps_obj;
+        const float vb = vf - 2 * eps_obj;
+        const int r = fd_head<SET>() + slot * 6 + c * 2;
+        if (!SET) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) { l.rep_poses[(size_t)r * 6 + k] = l.init[k]; l.rep_poses[(size_t)(r + 1) * 6 + k] = l.init[k]; }
+        }
+        l.rep_px_c[2 * r] = p; l.rep_px_c[2 * r + 1] = c; l.rep_value[r] = vf;
+        l.rep_px_c[2 * (r + 1)] = p; l.rep_px_c[2 * (r + 1) + 1] = c; l.rep_value[r + 1] = vb;
+    }
+}
+
+// one workgroup per list (blockIdx.y)
+template <bool SET>
+__global__ __launch_bounds__(PLAN_THREADS) void k_refine_fd_plan(FdLists L, const double* __restrict__ init_pose, const int32_t* __restrict__ set4,
+                                                                 const int32_t* __restrict__ inlier_map, FrameDev F, int skip, float eps_hyp, float eps_obj,
+                                                                 double* __restrict__ rep_poses, int32_t* __restrict__ rep_px_c, float* __restrict__ rep_value,
+                                                                 int32_t* __restrict__ obj_pixels, int32_t* __restrict__ n_obj) {
+    __shared__ int s_cnt[PLAN_THREADS];
+    const int tid = threadIdx.x;
+    const FdList l = fd_list<SET>(L, blockIdx.y, F, init_pose, set4, inlier_map, rep_poses, rep_px_c, rep_value, obj_pixels, n_obj);
+    if (tid < fd_head<SET>()) emit_head_replica<SET>(tid, l, F, eps_hyp, eps_obj);
+    // column-major scan: x-outer / y-inner order, t = x * H + y  (core/cnn_softam.h:873-882, core/cnn.h:935-945)
     const int P = F.P;
     const int seg = (P + PLAN_THREADS - 1) / PLAN_THREADS;
-    const int t0 = min(P, lane * seg), t1 = min(P, t0 + seg);
+    const int t0 = min(P, tid * seg), t1 = min(P, t0 + seg);
     int total = 0;
-    int inCount = plan_segment_prefix(inlier_map, F, t0, t1, s_cnt, &total);
+    int inCount = plan_segment_prefix(l.inlier_map, F, t0, t1, s_cnt, &total);
     for (int t = t0; t < t1; t++) {
         const int x = t / F.H, y = t - x * F.H, p = y * F.W + x;
-        if (inlier_map[p] == 0) continue;
+        if (l.inlier_map[p] == 0) continue;
         inCount++;
         if (inCount % skip != 0) continue;
         const int slot = inCount / skip - 1;
-        if (slot >= cap) continue;
-        obj_pixels[slot] = p;
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const float v0 = F.xyz[(size_t)p * 3 + c];
-            const float vf = v0 + eps_obj;
-            const float vb = vf - 2 * eps_obj;
-            const int r = 12 + slot * 6 + c * 2;
-#pragma unroll
-            for (int k = 0; k < 6; k++) { rep_poses[(size_t)r * 6 + k] = init[k]; rep_poses[(size_t)(r + 1) * 6 + k] = init[k]; }
-            rep_px_c[2 * r] = p; rep_px_c[2 * r + 1] = c; rep_value[r] = vf;
-            rep_px_c[2 * (r + 1)] = p; rep_px_c[2 * (r + 1) + 1] = c; rep_value[r + 1] = vb;
-        }
+        if (slot >= L.cap) continue;
+        emit_obj_replicas<SET>(slot, p, l, F, eps_obj);
     }
-    if (lane == 0) n_obj[0] = min(total / skip, cap);
+    if (tid == 0) l.n_obj[0] = min(total / skip, L.cap);
 }
 
 // ---- the same plan for large maps: two launches over tiles of 64 columns --------------------------------------------------------
@@ -1183,64 +1227,17 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_refine_fd_count(const int32_t*
     }
 }
 
-// SET: the DSAC variant's replica list (18 set perturbations first, start poses written later by k_refine_fd_init_set)
 template <bool SET>
-DM_INLINE void emit_obj_replicas(int slot, int p, const FrameDev& F, const double init[6], float eps_obj, double* __restrict__ rep_poses,
-                                 int32_t* __restrict__ rep_px_c, float* __restrict__ rep_value, int32_t* __restrict__ obj_pixels) {
-    obj_pixels[slot] = p;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const float v0 = F.xyz[(size_t)p * 3 + c];
-        const float vf = v0 + eps_obj;
-        const float vb = vf - 2 * eps_obj;
-        const int r = (SET ? 18 : 12) + slot * 6 + c * 2;
-        if (!SET) {
-#pragma unroll
-            for (int k = 0; k < 6; k++) { rep_poses[(size_t)r * 6 + k] = init[k]; rep_poses[(size_t)(r + 1) * 6 + k] = init[k]; }
-        }
-        rep_px_c[2 * r] = p; rep_px_c[2 * r + 1] = c; rep_value[r] = vf;
-        rep_px_c[2 * (r + 1)] = p; rep_px_c[2 * (r + 1) + 1] = c; rep_value[r + 1] = vb;
-    }
-}
-
-template <bool SET>
-__global__ __launch_bounds__(PLAN_THREADS) void k_refine_fd_emit(const double* __restrict__ init_pose, const int32_t* __restrict__ inlier_map, FrameDev F,
-                                                                 int skip, float eps_hyp, float eps_obj, int cap, const int32_t* __restrict__ scratch,
-                                                                 double* __restrict__ rep_poses, int32_t* __restrict__ rep_px_c,
-                                                                 float* __restrict__ rep_value, int32_t* __restrict__ obj_pixels,
-                                                                 int32_t* __restrict__ n_obj, const int32_t* __restrict__ set4, int px_stride,
-                                                                 const int32_t* __restrict__ frame_of) {
+__global__ __launch_bounds__(PLAN_THREADS) void k_refine_fd_emit(FdLists L, const double* __restrict__ init_pose, const int32_t* __restrict__ set4,
+                                                                 const int32_t* __restrict__ inlier_map, FrameDev F, int skip, float eps_hyp, float eps_obj,
+                                                                 const int32_t* __restrict__ scratch, double* __restrict__ rep_poses,
+                                                                 int32_t* __restrict__ rep_px_c, float* __restrict__ rep_value,
+                                                                 int32_t* __restrict__ obj_pixels, int32_t* __restrict__ n_obj) {
     const int tid = threadIdx.x, lane = tid & 63, seg = tid >> 6;
     const int x0 = blockIdx.x * 64, x = x0 + lane;
-    double init[6] = {0, 0, 0, 0, 0, 0};
-    if (SET) {  // hypothesis m of a batch (blockIdx.y): its set, inlier map, counts and slice of the replica arrays (18 + 6*cap replicas each)
-        const size_t m = blockIdx.y, R = 18 + 6 * (size_t)cap;
-        set4 += 4 * m; inlier_map += m * F.P; scratch += m * F.W * (PLAN_SEGS + 1); rep_px_c += m * R * 2; rep_value += m * R; obj_pixels += m * cap; n_obj += m;
-        if (frame_of) F.xyz += (long long)clamp_frame(frame_of[m], F) * F.xyz_stride;  // frame batch: hypothesis m reads its own frame's coordinates
-        if (blockIdx.x == 0 && tid < 18) {
-            const int pt = tid / 6, c = (tid % 6) >> 1;
-            const int p = min(max(set4[pt], 0), F.P - 1);
-            const float vf = F.xyz[(size_t)p * 3 + c] + eps_obj;
-            rep_px_c[2 * tid] = p; rep_px_c[2 * tid + 1] = c;
-            rep_value[tid] = (tid & 1) ? vf - 2 * eps_obj : vf;
-        }
-    } else {
-        // frame f of a batch (blockIdx.y): its start pose, inlier map, coordinate map, counts and slice of the replica arrays
-        const size_t f = blockIdx.y, R = 12 + 6 * (size_t)cap;
-        init_pose += 6 * f; inlier_map += f * F.P; F.xyz += (long long)f * F.xyz_stride; scratch += f * F.W * (PLAN_SEGS + 1);
-        rep_poses += f * R * 6; rep_px_c += f * R * 2; rep_value += f * R; obj_pixels += f * (size_t)px_stride; n_obj += f;
-#pragma unroll
-        for (int i = 0; i < 6; i++) init[i] = init_pose[i];
-    }
-    if (!SET && blockIdx.x == 0 && tid < 12) {  // dRefineHyp: replica 2i = +step on parameter i, 2i+1 = (+step) - 2 step (as the one-workgroup form)
-        const int i = tid >> 1;
-        const double step = (i < 3) ? (double)eps_hyp : (double)(eps_hyp * 1000);
-        double v = init[i] + step;
-        if (tid & 1) v -= 2 * step;
-#pragma unroll
-        for (int k = 0; k < 6; k++) rep_poses[(size_t)tid * 6 + k] = (k == i) ? v : init[k];
-        rep_px_c[2 * tid] = -1; rep_px_c[2 * tid + 1] = 0; rep_value[tid] = 0.f;
-    }
+    const FdList l = fd_list<SET>(L, blockIdx.y, F, init_pose, set4, inlier_map, rep_poses, rep_px_c, rep_value, obj_pixels, n_obj);
+    scratch += (size_t)blockIdx.y * F.W * (PLAN_SEGS + 1);
+    if (blockIdx.x == 0 && tid < fd_head<SET>()) emit_head_replica<SET>(tid, l, F, eps_hyp, eps_obj);
     // inliers in the columns before this tile (all threads), and in all columns (for n_obj)
     __shared__ int s_part[PLAN_SEGS], s_tot[PLAN_SEGS], s_col[64];
     int before = 0, total = 0;
@@ -1259,7 +1256,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_refine_fd_emit(const double* _
     before = 0; total = 0;
 #pragma unroll
     for (int k = 0; k < PLAN_SEGS; k++) { before += s_part[k]; total += s_tot[k]; }
-    if (blockIdx.x == 0 && tid == 0) n_obj[0] = min(total / skip, cap);
+    if (blockIdx.x == 0 && tid == 0) l.n_obj[0] = min(total / skip, L.cap);
     if (x >= F.W) return;
     int inCount = before + s_col[lane];
     for (int k = 0; k < seg; k++) inCount += scratch[(size_t)F.W + (size_t)x * PLAN_SEGS + k];
@@ -1267,47 +1264,13 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_refine_fd_emit(const double* _
     const int y0 = min(F.H, seg * rows), y1 = min(F.H, y0 + rows);
     for (int y = y0; y < y1; y++) {
         const int p = y * F.W + x;
-        if (inlier_map[p] == 0) continue;
+        if (l.inlier_map[p] == 0) continue;
         inCount++;
         if (inCount % skip != 0) continue;
         const int slot = inCount / skip - 1;
-        if (slot >= cap) continue;
-        emit_obj_replicas<SET>(slot, p, F, init, eps_obj, rep_poses, rep_px_c, rep_value, obj_pixels);
+        if (slot >= L.cap) continue;
+        emit_obj_replicas<SET>(slot, p, l, F, eps_obj);
     }
-}
-
-size_t refine_fd_plan_scratch_ints(const FrameDev& F) { return F.P > PLAN_TILED_MIN_CELLS ? (size_t)F.W * (PLAN_SEGS + 1) : 0; }
-
-hipError_t refine_fd_plan(hipStream_t st, const double* init_pose, const int32_t* inlier_map, const FrameDev& F, int skip, float eps_hyp,
-                          float eps_obj, int cap, double* rep_poses, int32_t* rep_px_c, float* rep_value, int32_t* obj_pixels, int32_t* n_obj,
-                          int32_t* scratch, int frames, int px_stride) {
-    if (frames < 1) frames = 1;
-    if (px_stride <= 0) px_stride = cap;
-    if (scratch && F.P > PLAN_TILED_MIN_CELLS) {
-        const int tiles = (F.W + 63) / 64;
-        hipLaunchKernelGGL(k_refine_fd_count, dim3(tiles, frames), dim3(PLAN_THREADS), 0, st, inlier_map, F, scratch);
-        hipLaunchKernelGGL(k_refine_fd_emit<false>, dim3(tiles, frames), dim3(PLAN_THREADS), 0, st, init_pose, inlier_map, F, skip, eps_hyp, eps_obj, cap, scratch,
-                           rep_poses, rep_px_c, rep_value, obj_pixels, n_obj, (const int32_t*)nullptr, px_stride, (const int32_t*)nullptr);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(k_refine_fd_plan, dim3(frames), dim3(PLAN_THREADS), 0, st, init_pose, inlier_map, F, skip, eps_hyp, eps_obj, cap, rep_poses, rep_px_c,
-                       rep_value, obj_pixels, n_obj, px_stride);
-    return hipGetLastError();
-}
-
-// launches the replicas: grid = 12 + 6*cap waves, those beyond 12 + 6*n_obj exit immediately
-hipError_t refine_fd_run(hipStream_t st, int cap, const int32_t* n_obj, const double* rep_poses, const int32_t* perm, int steps, int max_inl,
-                         int min_inl, float thr, const int32_t* rep_px_c, const float* rep_value, const FrameDev& F, double* rep_out, int frames) {
-    if (max_inl > RF_MAX_INL) return hipErrorInvalidValue;
-    const int R = 12 + 6 * cap;
-    if (frames > 1) {  // one replica list per frame: list m = b / R refines against frame m, replicas beyond 12 + 6 * n_obj[m] exit at once
-        hipLaunchKernelGGL(k_refine<1>, dim3(R * frames), dim3(64), 0, st, R * frames, n_obj, 12, 6, rep_poses, perm, steps, max_inl, min_inl, thr, rep_px_c, rep_value, F,
-                           rep_out, (int32_t*)nullptr, (int32_t*)nullptr, 0, R, R, (const double*)nullptr, (double*)nullptr, (const int32_t*)nullptr);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(k_refine<1>, dim3(R), dim3(64), 0, st, R, n_obj, 12, 6, rep_poses, perm, steps, max_inl, min_inl, thr, rep_px_c, rep_value, F, rep_out,
-                       (int32_t*)nullptr, (int32_t*)nullptr, 0, 0, 0, (const double*)nullptr, (double*)nullptr, (const int32_t*)nullptr);
-    return hipGetLastError();
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -1317,50 +1280,6 @@ hipError_t refine_fd_run(hipStream_t st, int cap, const int32_t* n_obj, const do
 // replica is P3P of the set read from the replica's perturbed map -- for the inlier replicas that is the unperturbed
 // hypothesis, because processImage removes the set's own cells from the inlier map (:1208-1214).
 // --------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(PLAN_THREADS) void k_refine_fd_plan_set(const int32_t* __restrict__ set4, const int32_t* __restrict__ inlier_map, FrameDev F, int skip,
-                                                           float eps_obj, int cap, int32_t* __restrict__ rep_px_c, float* __restrict__ rep_value,
-                                                           int32_t* __restrict__ obj_pixels, int32_t* __restrict__ n_obj,
-                                                           const int32_t* __restrict__ frame_of) {
-    const int lane = threadIdx.x;
-    const int P = F.P;
-    {   // hypothesis m of a batch (blockIdx.y): its set, inlier map and slice of the replica arrays (18 + 6*cap replicas each)
-        const size_t m = blockIdx.y, R = 18 + 6 * (size_t)cap;
-        set4 += 4 * m; inlier_map += m * P; rep_px_c += m * R * 2; rep_value += m * R; obj_pixels += m * cap; n_obj += m;
-        if (frame_of) F.xyz += (long long)clamp_frame(frame_of[m], F) * F.xyz_stride;  // frame batch: hypothesis m reads its own frame's coordinates
-    }
-    if (lane < 18) {
-        const int pt = lane / 6, c = (lane % 6) >> 1;
-        const int p = min(max(set4[pt], 0), P - 1);
-        const float v0 = F.xyz[(size_t)p * 3 + c];
-        const float vf = v0 + eps_obj;
-        rep_px_c[2 * lane] = p; rep_px_c[2 * lane + 1] = c;
-        rep_value[lane] = (lane & 1) ? vf - 2 * eps_obj : vf;
-    }
-    __shared__ int s_cnt[PLAN_THREADS];
-    const int seg = (P + PLAN_THREADS - 1) / PLAN_THREADS;  // x-outer / y-inner order: t = x * H + y  (cnn.h:935-945)
-    const int t0 = min(P, lane * seg), t1 = min(P, t0 + seg);
-    int total = 0;
-    int inCount = plan_segment_prefix(inlier_map, F, t0, t1, s_cnt, &total);
-    for (int t = t0; t < t1; t++) {
-        const int x = t / F.H, y = t - x * F.H, p = y * F.W + x;
-        if (inlier_map[p] == 0) continue;
-        inCount++;
-        if (inCount % skip != 0) continue;
-        const int slot = inCount / skip - 1;
-        if (slot >= cap) continue;
-        obj_pixels[slot] = p;
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const float v0 = F.xyz[(size_t)p * 3 + c];
-            const float vf = v0 + eps_obj;
-            const int r = 18 + slot * 6 + c * 2;
-            rep_px_c[2 * r] = p; rep_px_c[2 * r + 1] = c; rep_value[r] = vf;
-            rep_px_c[2 * (r + 1)] = p; rep_px_c[2 * (r + 1) + 1] = c; rep_value[r + 1] = vf - 2 * eps_obj;
-        }
-    }
-    if (lane == 0) n_obj[0] = min(total / skip, cap);
-}
-
 // start pose of replica r: P3P (least-squares alignment, as OpenCV's; closed form since round 5) of the set read through the replica's perturbation
 __global__ __launch_bounds__(64) void k_refine_fd_init_set(int cap, const int32_t* __restrict__ n_obj, const int32_t* __restrict__ set4,
                                                            const int32_t* __restrict__ rep_px_c, const float* __restrict__ rep_value, FrameDev F,
@@ -1410,101 +1329,83 @@ __global__ __launch_bounds__(64) void k_refine_fd_init_set(int cap, const int32_
     }
 }
 
-hipError_t refine_fd_plan_set(hipStream_t st, const int32_t* set4, const int32_t* inlier_map, const FrameDev& F, int skip, float eps_obj, int cap,
-                              double* rep_poses, int32_t* rep_px_c, float* rep_value, int32_t* obj_pixels, int32_t* n_obj, int M, int32_t* scratch,
-                              const int32_t* frame_of) {
-    if (M <= 0) return hipSuccess;
+size_t refine_fd_plan_scratch_ints(const FrameDev& F) { return F.P > PLAN_TILED_MIN_CELLS ? (size_t)F.W * (PLAN_SEGS + 1) : 0; }
+
+template <bool SET>
+static void launch_fd_plan(hipStream_t st, const FdLists& L, const double* init_pose, const int32_t* set4, const int32_t* inlier_map, const FrameDev& F, int skip,
+                           float eps_hyp, float eps_obj, const FdReplicas& rep, int32_t* obj_pixels, int32_t* n_obj, int32_t* scratch) {
     if (scratch && F.P > PLAN_TILED_MIN_CELLS) {
-        // large maps: the tiled two-launch plan of the soft-argmax path, one grid row per hypothesis (round 2 scanned each map with one workgroup, column-major
-        // with a 2.5 KB stride: 158 us per 640 x 480 map)
-        const int tiles = (F.W + 63) / 64;
-        hipLaunchKernelGGL(k_refine_fd_count, dim3(tiles, M), dim3(PLAN_THREADS), 0, st, inlier_map, F, scratch);
-        hipLaunchKernelGGL(k_refine_fd_emit<true>, dim3(tiles, M), dim3(PLAN_THREADS), 0, st, (const double*)nullptr, inlier_map, F, skip, 0.f, eps_obj, cap, scratch,
-                           (double*)nullptr, rep_px_c, rep_value, obj_pixels, n_obj, set4, cap, frame_of);
-    } else
-    hipLaunchKernelGGL(k_refine_fd_plan_set, dim3(1, M), dim3(PLAN_THREADS), 0, st, set4, inlier_map, F, skip, eps_obj, cap, rep_px_c, rep_value, obj_pixels, n_obj, frame_of);
-    const int R = 18 + 6 * cap;
-    hipLaunchKernelGGL(k_refine_fd_init_set, dim3((R + 15) / 16, M), dim3(64), 0, st, cap, n_obj, set4, rep_px_c, rep_value, F, rep_poses, frame_of);
+        const dim3 grid((F.W + 63) / 64, L.lists);
+        hipLaunchKernelGGL(k_refine_fd_count, grid, dim3(PLAN_THREADS), 0, st, inlier_map, F, scratch);
+        hipLaunchKernelGGL(k_refine_fd_emit<SET>, grid, dim3(PLAN_THREADS), 0, st, L, init_pose, set4, inlier_map, F, skip, eps_hyp, eps_obj, scratch, rep.poses,
+                           rep.px_c, rep.value, obj_pixels, n_obj);
+        return;
+    }
+    hipLaunchKernelGGL(k_refine_fd_plan<SET>, dim3(1, L.lists), dim3(PLAN_THREADS), 0, st, L, init_pose, set4, inlier_map, F, skip, eps_hyp, eps_obj, rep.poses,
+                       rep.px_c, rep.value, obj_pixels, n_obj);
+}
+
+hipError_t refine_fd_plan(hipStream_t st, const FdLists& L, const double* init_pose, const int32_t* set4, const int32_t* inlier_map, const FrameDev& F, int skip,
+                          float eps_hyp, float eps_obj, const FdReplicas& rep, int32_t* obj_pixels, int32_t* n_obj, int32_t* scratch) {
+    if (L.lists <= 0) return hipSuccess;
+    if (L.head == FD_HEAD_POSE) {
+        launch_fd_plan<false>(st, L, init_pose, set4, inlier_map, F, skip, eps_hyp, eps_obj, rep, obj_pixels, n_obj, scratch);
+        return hipGetLastError();
+    }
+    if (L.head != FD_HEAD_SET || L.list_is_frame) return hipErrorInvalidValue;  // k_refine_fd_init_set finds a list's frame through frame_of alone
+    launch_fd_plan<true>(st, L, init_pose, set4, inlier_map, F, skip, eps_hyp, eps_obj, rep, obj_pixels, n_obj, scratch);
+    hipLaunchKernelGGL(k_refine_fd_init_set, dim3((L.replicas() + 15) / 16, L.lists), dim3(64), 0, st, L.cap, n_obj, set4, rep.px_c, rep.value, F, rep.poses, L.frame_of);
     return hipGetLastError();
 }
 
-hipError_t refine_fd_run_set(hipStream_t st, int cap, const int32_t* n_obj, const double* rep_poses, const int32_t* perm, int steps, int max_inl,
-                             int min_inl, float thr, const int32_t* rep_px_c, const float* rep_value, const FrameDev& F, double* rep_out, int M,
-                             const int32_t* frame_of) {
+// one wave per replica: list m = b / replicas() refines against its frame, the replicas beyond head + 6 * n_obj[m] exit at once
+hipError_t refine_fd_run(hipStream_t st, const FdLists& L, const int32_t* n_obj, const int32_t* perm, int steps, int max_inl, int min_inl, float thr,
+                         const FrameDev& F, const FdReplicas& rep) {
     if (max_inl > RF_MAX_INL) return hipErrorInvalidValue;
-    if (M <= 0) return hipSuccess;
-    const int R = 18 + 6 * cap;
-    const long long B = (long long)R * M;
+    if (L.lists <= 0) return hipSuccess;
+    const int R = L.replicas();
+    const long long B = (long long)R * L.lists;
     if (B > 0x7fffffffll) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_refine<1>, dim3((unsigned)B), dim3(64), 0, st, (int)B, n_obj, 18, 6, rep_poses, perm, steps, max_inl, min_inl, thr, rep_px_c, rep_value, F,
-                       rep_out, (int32_t*)nullptr, (int32_t*)nullptr, 0, R, 0, (const double*)nullptr, (double*)nullptr, frame_of);
+    hipLaunchKernelGGL(k_refine<1>, dim3((unsigned)B), dim3(64), 0, st, (int)B, n_obj, L.head, 6, rep.poses, perm, steps, max_inl, min_inl, thr, rep.px_c, rep.value, F,
+                       rep.out, (int32_t*)nullptr, (int32_t*)nullptr, 0, R, L.list_is_frame ? R : 0, (const double*)nullptr, (double*)nullptr, L.frame_of);
     return hipGetLastError();
 }
 
-__global__ __launch_bounds__(64) void k_refine_fd_finish_set(const double* __restrict__ rep_out, const int32_t* __restrict__ n_obj, int cap, int skip,
-                                                             float eps_obj, double* __restrict__ J_set, double* __restrict__ J_obj) {
-    {
-        const size_t m = blockIdx.y, R = 18 + 6 * (size_t)cap;
-        rep_out += m * R * 6; n_obj += m; J_set += m * 54; J_obj += m * (size_t)cap * 18;
+// central differences of the jp 6-vectors (getRodVecAndTrans(Hypothesis(cv2our(.))), core/cnn_softam.h:721-722): replica pairs 0 .. HP - 1 are the head,
+// then 3 per cell.  !SET: pair i = pose parameter i into the 6 x 6 J_hyp.  SET: pair = 3 pt + c into the 6 x 9 J_set, no skip factor (cnn.h:923).
+template <bool SET>
+__global__ __launch_bounds__(64) void k_refine_fd_finish(const double* __restrict__ rep_out, const int32_t* __restrict__ n_obj, int cap, int skip, float eps_hyp,
+                                                         float eps_obj, double* __restrict__ J_head, double* __restrict__ J_obj) {
+    constexpr int HP = fd_head<SET>() / 2;
+    {   // list m of a batch (blockIdx.y): its replica results and Jacobians
+        const size_t m = blockIdx.y;
+        rep_out += m * (2 * HP + 6 * (size_t)cap) * 6; n_obj += m; J_head += m * 6 * HP; J_obj += m * (size_t)cap * 18;
     }
-    const int pair = blockIdx.x * blockDim.x + threadIdx.x;  // 0..8: set point pt = pair / 3, channel pair % 3; then 3 per cell
-    const int npairs = 9 + 3 * min(n_obj[0], cap);
+    const int pair = blockIdx.x * blockDim.x + threadIdx.x;
+    const int npairs = HP + 3 * min(n_obj[0], cap);
     if (pair >= npairs) return;
     double f6[6], b6[6], cvf[6], cvb[6];
 #pragma unroll
     for (int k = 0; k < 6; k++) { cvf[k] = rep_out[(size_t)(2 * pair) * 6 + k]; cvb[k] = rep_out[(size_t)(2 * pair + 1) * 6 + k]; }
     dm::cv_to_jp6(cvf, f6);
     dm::cv_to_jp6(cvb, b6);
-    if (pair < 9) {
+    if (pair < HP) {
 #pragma unroll
-        for (int k = 0; k < 6; k++) J_set[k * 9 + pair] = (f6[k] - b6[k]) / (double)(2 * eps_obj);  // no skip factor (cnn.h:923)
+        for (int k = 0; k < 6; k++)
+            J_head[k * HP + pair] = (f6[k] - b6[k]) / (SET ? (double)(2 * eps_obj) : k < 3 ? (double)(2 * eps_hyp) : (double)(2 * eps_hyp * 1000));
     } else {
-        const int cell = (pair - 9) / 3, c = (pair - 9) % 3;
+        const int cell = (pair - HP) / 3, c = (pair - HP) % 3;
 #pragma unroll
         for (int k = 0; k < 6; k++) J_obj[((size_t)cell * 6 + k) * 3 + c] = (f6[k] - b6[k]) / (double)(2 * eps_obj) * skip;
     }
 }
 
-hipError_t refine_fd_finish_set(hipStream_t st, const double* rep_out, const int32_t* n_obj, int cap, int skip, float eps_obj, double* J_set, double* J_obj,
-                                int M) {
-    if (M <= 0) return hipSuccess;
-    const int pairs = 9 + 3 * cap;
-    hipLaunchKernelGGL(k_refine_fd_finish_set, dim3((pairs + 63) / 64, M), dim3(64), 0, st, rep_out, n_obj, cap, skip, eps_obj, J_set, J_obj);
-    return hipGetLastError();
-}
-
-// central differences of the jp 6-vectors (getRodVecAndTrans(Hypothesis(cv2our(.))), core/cnn_softam.h:721-722)
-__global__ __launch_bounds__(64) void k_refine_fd_finish(const double* __restrict__ rep_out, const int32_t* __restrict__ n_obj, int cap, int skip,
-                                                         float eps_hyp, float eps_obj, double* __restrict__ J_hyp, double* __restrict__ J_obj) {
-    {   // frame f of a batch (blockIdx.y): its replica results and Jacobians
-        const size_t f = blockIdx.y;
-        rep_out += f * (12 + 6 * (size_t)cap) * 6; n_obj += f; J_hyp += f * 36; J_obj += f * (size_t)cap * 18;
-    }
-    const int pair = blockIdx.x * blockDim.x + threadIdx.x;  // replica pair index: 0..5 hyp, 6.. obj (3 per cell)
-    const int npairs = 6 + 3 * min(n_obj[0], cap);
-    if (pair >= npairs) return;
-    double f6[6], b6[6], cvf[6], cvb[6];
-#pragma unroll
-    for (int k = 0; k < 6; k++) { cvf[k] = rep_out[(size_t)(2 * pair) * 6 + k]; cvb[k] = rep_out[(size_t)(2 * pair + 1) * 6 + k]; }
-    dm::cv_to_jp6(cvf, f6);
-    dm::cv_to_jp6(cvb, b6);
-    if (pair < 6) {
-        const int i = pair;
-#pragma unroll
-        for (int k = 0; k < 3; k++) J_hyp[k * 6 + i] = (f6[k] - b6[k]) / (double)(2 * eps_hyp);
-#pragma unroll
-        for (int k = 3; k < 6; k++) J_hyp[k * 6 + i] = (f6[k] - b6[k]) / (double)(2 * eps_hyp * 1000);
-    } else {
-        const int cell = (pair - 6) / 3, c = (pair - 6) % 3;
-#pragma unroll
-        for (int k = 0; k < 6; k++) J_obj[((size_t)cell * 6 + k) * 3 + c] = (f6[k] - b6[k]) / (double)(2 * eps_obj) * skip;
-    }
-}
-
-hipError_t refine_fd_finish(hipStream_t st, const double* rep_out, const int32_t* n_obj, int cap, int skip, float eps_hyp, float eps_obj,
-                            double* J_hyp, double* J_obj, int frames) {
-    const int pairs = 6 + 3 * cap;
-    hipLaunchKernelGGL(k_refine_fd_finish, dim3((pairs + 63) / 64, frames < 1 ? 1 : frames), dim3(64), 0, st, rep_out, n_obj, cap, skip, eps_hyp, eps_obj, J_hyp, J_obj);
+hipError_t refine_fd_finish(hipStream_t st, const FdLists& L, const double* rep_out, const int32_t* n_obj, int skip, float eps_hyp, float eps_obj, double* J_head,
+                            double* J_obj) {
+    if (L.lists <= 0) return hipSuccess;
+    const dim3 grid((L.head / 2 + 3 * L.cap + 63) / 64, L.lists);
+    if (L.head == FD_HEAD_SET) hipLaunchKernelGGL(k_refine_fd_finish<true>, grid, dim3(64), 0, st, rep_out, n_obj, L.cap, skip, eps_hyp, eps_obj, J_head, J_obj);
+    else hipLaunchKernelGGL(k_refine_fd_finish<false>, grid, dim3(64), 0, st, rep_out, n_obj, L.cap, skip, eps_hyp, eps_obj, J_head, J_obj);
     return hipGetLastError();
 }
 

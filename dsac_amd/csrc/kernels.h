@@ -189,32 +189,37 @@ hipError_t refine_split(hipStream_t st, int B, const double* init_poses, const i
 // loss_gt_jp6 (B x 6) / loss_out4 (B x 4): maxLoss of every refined pose against its ground truth in the same launch (K7's arithmetic, loss_math.h)
 // inlier_maps[h][set cell] = 0 for the 4 cells of every hypothesis' minimal set (core/cnn.h:1208-1214)
 hipError_t zero_set_cells(hipStream_t st, int N, const int32_t* sets, int P, int32_t* inlier_maps);
-// DSAC-variant replica plan (core/cnn.h:854-990 dRefine): 18 replicas perturb the first three points of the minimal set,
-// 6 per selected inlier cell follow; every replica's start pose is P3P of the set read from the perturbed map.
-// scratch: M * refine_fd_plan_scratch_ints(F) int32 (nullptr / small maps: one workgroup per hypothesis scans its map)
-hipError_t refine_fd_plan_set(hipStream_t st, const int32_t* set4, const int32_t* inlier_map, const FrameDev& F, int skip, float eps_obj, int cap,
-                              double* rep_poses, int32_t* rep_px_c, float* rep_value, int32_t* obj_pixels, int32_t* n_obj, int M = 1,
-                              int32_t* scratch = nullptr, const int32_t* frame_of = nullptr);
-// frame_of (M int32, device) with a frame batch: hypothesis m lives in frame frame_of[m] (its minimal set, inlier map and replicas read that frame's map)
-// M hypotheses at once (sets M x 4, inlier maps M x H*W, 18 + 6*cap replicas each): one launch of M * (18 + 6*cap) waves
-hipError_t refine_fd_run_set(hipStream_t st, int cap, const int32_t* n_obj, const double* rep_poses, const int32_t* perm, int steps, int max_inl,
-                             int min_inl, float thr, const int32_t* rep_px_c, const float* rep_value, const FrameDev& F, double* rep_out, int M = 1,
-                             const int32_t* frame_of = nullptr);
-hipError_t refine_fd_finish_set(hipStream_t st, const double* rep_out, const int32_t* n_obj, int cap, int skip, float eps_obj, double* J_set /*M x 6 x 9*/,
-                                double* J_obj, int M = 1);
-// builds the replica list of dRefineHyp/dRefineObj on device, see k_refine.hip
-// scratch: refine_fd_plan_scratch_ints(F) int32 of device memory (0: not needed, small map) -- large maps are planned by two tiled launches
+// ---- K6's finite-difference Jacobians: plan the replica lists, run the replicas through k_refine, central differences ----
+// A batch of replica lists.  head = FD_HEAD_POSE: dRefineHyp + dRefineObj (core/cnn_softam.h), 12 replicas perturb the given start pose, one list per frame.
+// head = FD_HEAD_SET: the DSAC variant (core/cnn.h:854-990 dRefine), 18 replicas perturb the first three points of the minimal set and every replica's start
+// pose is P3P of the set read from the perturbed map, one list per hypothesis.  6 replicas per selected inlier cell follow in both.
+constexpr int FD_HEAD_POSE = 12, FD_HEAD_SET = 18;
+struct FdLists {
+    int head;                 // head replicas per list
+    int lists;                // list m: replicas() entries of the replica arrays, its own inlier map (H*W), n_obj[m], cap x 18 of J_obj
+    int cap;                  // at most cap selected cells per list
+    int px_stride;            // obj_pixels of list m at m * px_stride
+    bool list_is_frame;       // list m reads frame m of the batch (FD_HEAD_POSE only) ...
+    const int32_t* frame_of;  // ... else frame frame_of[m] (lists int32, device), nullptr: the single frame
+    int replicas() const { return head + 6 * cap; }
+};
+struct FdReplicas {  // lists x replicas() each: start poses (x 6), perturbed cell and channel (x 2; cell -1: none), perturbed value, refined poses (x 6)
+    double* poses;
+    int32_t* px_c;
+    float* value;
+    double* out;
+};
+// scratch of the plan per list: int32 of device memory (0: small map, one workgroup per list scans it) -- large maps are planned by two tiled launches
 size_t refine_fd_plan_scratch_ints(const FrameDev& F);
-// frames > 1 (frame batch): one replica list of 12 + 6*cap entries per frame (init_pose frames x 6, inlier_map frames x H*W, obj_pixels frames x px_stride,
-// n_obj frames, scratch frames x refine_fd_plan_scratch_ints); perturbed values are read from the frame's own map
-hipError_t refine_fd_plan(hipStream_t st, const double* init_pose, const int32_t* inlier_map, const FrameDev& F, int skip, float eps_hyp,
-                          float eps_obj, int cap, double* rep_poses, int32_t* rep_px_c, float* rep_value, int32_t* obj_pixels,
-                          int32_t* n_obj, int32_t* scratch = nullptr, int frames = 1, int px_stride = 0);
-// launches 12 + 6*cap replica waves; those beyond 12 + 6*n_obj[0] exit immediately
-hipError_t refine_fd_run(hipStream_t st, int cap, const int32_t* n_obj, const double* rep_poses, const int32_t* perm, int steps, int max_inl,
-                         int min_inl, float thr, const int32_t* rep_px_c, const float* rep_value, const FrameDev& F, double* rep_out, int frames = 1);
-hipError_t refine_fd_finish(hipStream_t st, const double* rep_out, const int32_t* n_obj, int cap, int skip, float eps_hyp, float eps_obj,
-                            double* J_hyp, double* J_obj, int frames = 1);
+// init_pose: lists x 6 (FD_HEAD_POSE), set4: lists x 4 (FD_HEAD_SET), the other one unused; eps_hyp: FD_HEAD_POSE only
+hipError_t refine_fd_plan(hipStream_t st, const FdLists& L, const double* init_pose, const int32_t* set4, const int32_t* inlier_map, const FrameDev& F, int skip,
+                          float eps_hyp, float eps_obj, const FdReplicas& rep, int32_t* obj_pixels, int32_t* n_obj, int32_t* scratch);
+// one launch of lists x replicas() waves; those beyond head + 6 * n_obj[m] of their list exit immediately
+hipError_t refine_fd_run(hipStream_t st, const FdLists& L, const int32_t* n_obj, const int32_t* perm, int steps, int max_inl, int min_inl, float thr,
+                         const FrameDev& F, const FdReplicas& rep);
+// J_head: lists x 6 x 6 (J_hyp; rows 3-5 over 2 eps_hyp * 1000) or lists x 6 x 9 (J_set, over 2 eps_obj); J_obj over 2 eps_obj, scaled by skip
+hipError_t refine_fd_finish(hipStream_t st, const FdLists& L, const double* rep_out, const int32_t* n_obj, int skip, float eps_hyp, float eps_obj, double* J_head,
+                            double* J_obj);
 
 // ---- k_loss.hip ------------------------------------------------------------------------------------
 // gt_stride: 0 = one ground truth (6 doubles) for all estimates, 6 = one per estimate

@@ -131,6 +131,35 @@ def dpnp_substitution_frame(engine, orc, fr, xyz_f, uv, H, W, cam, sets, coef6):
         return dpnp_substitution(e2, orc, fr, sets, coef6)
 
 
+def test_drefine_on_a_batch_of_three_tiled_maps_equals_the_single_frame_calls(engine, synth):
+    """dsac_refine_fd on three 120 x 160 frames (the tiled replica plan, one grid row per frame), every frame with its own coordinates, start pose and
+    inlier map: bit for bit the three single-frame calls.  test_backward_on_a_frame_batch reaches this size with two frames and the same `cap` on both
+    sides; here the single-frame calls take another cap (4096 against 300), so a replica's slot in the launch differs and its result must not."""
+    H, W, F, sub, cap = 120, 160, 3, 0.3, 300
+    frames = [synth.chess_like_frame(H, W, seed=300 + f) for f in range(F)]
+    xyz = np.ascontiguousarray(np.stack([fr["xyz"] for fr in frames]))
+    uv, cam = frames[0]["uv"], frames[0]["cam"]
+    perm = synth.fast_permutations(H * W, 8, seed=3)
+    rng = np.random.default_rng(7)
+    inits = np.stack([fr["gt_pose"] for fr in frames]) + rng.normal(size=(F, 6)) * np.array([0.003, 0.003, 0.003, 3.0, 3.0, 3.0])
+    maps, single = [], []
+    for f in range(F):
+        engine.set_frame(xyz[f], uv, H, W, cam)
+        _, sd, imap = engine.refine(inits[f], perm, want_inlier_map=True)
+        assert sd[0] == 8
+        maps.append(imap)
+        single.append(engine.dRefine(inits[f], perm, imap, sub_sample=sub))
+    maps = np.stack(maps)
+    assert len({m.tobytes() for m in maps}) == F and 0 < max(len(s[1]) for s in single) <= cap
+    engine.set_frames(xyz, uv, H, W, cam)
+    Jh, px, Jo, n = engine.dRefineFrames(inits, perm, maps, sub_sample=sub, cap=cap)
+    for f in range(F):
+        Jh1, px1, Jo1 = single[f]
+        k = len(px1)
+        assert n[f] == k and np.array_equal(px[f][:k], px1), f
+        assert np.array_equal(Jh[f], Jh1) and np.array_equal(Jo[f][:k], Jo1), f
+
+
 def test_score_backward_into_managed_memory(engine, synth):
     """The main pass of K4 adds into grad_xyz with hardware fp64 atomics, which are only defined on ordinary device memory: a MANAGED gradient buffer
     (hipMallocManaged) takes the staged form by itself -- on one frame and, frame by frame, on a batch -- and receives the same gradient (to the fp32

@@ -144,6 +144,29 @@ def test_bad_arguments_are_rejected(engine, frame40):
         with pytest.raises(C.DsacError) as ei:
             call()
         assert ei.value.code == C.DSAC_ERR_INVALID
+    # the finite-difference chain behind four entry points (and the two names of the batched DSAC-variant form) and dsac_loss_batch_frames: refused before
+    # any launch, each under the name of the call that was made
+    lib, ptr, ctx = C.lib, C.ptr, engine._ctx
+    perm, imap, set4 = np.zeros((1, 1600), np.int32), np.zeros(1600, np.int32), np.arange(4, dtype=np.int32)
+    d6, J, px, Jo, n = np.zeros(6), np.zeros((6, 9)), np.zeros(4, np.int32), np.zeros((4, 6, 3)), np.zeros(1, np.int32)
+    one, grad = np.ones(1), np.zeros((1600, 3))
+    chain = {
+        "dsac_refine_fd": lambda sub, eo: lib.dsac_refine_fd(ctx, ptr(d6), ptr(perm), 1, 100, 50, 10.0, ptr(imap), sub, 0.001, eo, ptr(J), ptr(px), ptr(Jo), 4, ptr(n)),
+        "dsac_refine_fd_set": lambda sub, eo: lib.dsac_refine_fd_set(ctx, ptr(set4), ptr(perm), 1, 100, 50, 10.0, ptr(imap), sub, eo, ptr(J), ptr(px), ptr(Jo), 4, ptr(n)),
+        "dsac_refine_fd_sets": lambda sub, eo: lib.dsac_refine_fd_sets(ctx, 1, ptr(set4), ptr(perm), 1, 100, 50, 10.0, ptr(imap), sub, eo, ptr(J), ptr(px), ptr(Jo), 4,
+                                                                       ptr(n)),
+        "dsac_refine_fd_sets_frames": lambda sub, eo: lib.dsac_refine_fd_sets_frames(ctx, 1, ptr(set4), ptr(n), ptr(perm), 1, 100, 50, 10.0, ptr(imap), sub, eo, ptr(J),
+                                                                                     ptr(px), ptr(Jo), 4, ptr(n)),
+        "dsac_backward_path1": lambda sub, eo: lib.dsac_backward_path1(ctx, 1, ptr(d6), ptr(set4), ptr(one), ptr(d6), ptr(d6), ptr(d6), ptr(perm), 1, 100, 50, 10.0,
+                                                                       ptr(imap), sub, 0.001, eo, 1.0, None, ptr(grad), ptr(one), None, None),
+    }
+    for name, call in chain.items():
+        for sub, eo in ((2.0, 2.0), (0.01, 0.0), (0.01, -1.0)):  # sub_sample > 1; eps_obj <= 0
+            assert call(sub, eo) == C.DSAC_ERR_INVALID, (name, sub, eo)
+            assert lib.dsac_last_error(ctx).decode().startswith(name + ": "), (name, lib.dsac_last_error(ctx))
+    for per_frame in (0, -3):
+        assert lib.dsac_loss_batch_frames(ctx, 1, per_frame, ptr(d6), ptr(d6), ptr(np.zeros(4)), None) == C.DSAC_ERR_INVALID
+        assert lib.dsac_last_error(ctx).decode().startswith("dsac_loss_batch_frames: ")
     # quirk transpose needs a square map
     engine.set_frame(np.zeros((6, 3), np.float32), None, 2, 3, fr["cam"])
     with pytest.raises(C.DsacError):
