@@ -48,6 +48,8 @@ EXPORTS = [
     "dsac_get_option", "dsac_k2_range_census",
     "dsac_reproject_f16", "dsac_process_images_begin_f16",
     "dsac_score_backward_f16", "dsac_soft_score_derr_f16",
+    "dsac_reproject_bf16", "dsac_process_images_begin_bf16",
+    "dsac_score_backward_bf16", "dsac_soft_score_derr_bf16",
 ]
 
 # enum dsac_k2_form (dsac_get_option "k2_form_last") and the DSAC_K2_WHY_* bits ("k2_form_why_last")
@@ -87,6 +89,7 @@ def _load():
     lib.dsac_sample.argtypes = [vp, i32, u64, vp, f32, i32, vp, vp, vp]
     lib.dsac_reproject.argtypes = [vp, i32, vp, f32, vp, f32, f32, vp]
     lib.dsac_reproject_f16.argtypes = [vp, i32, vp, f32, vp, f32, f32, vp]
+    lib.dsac_reproject_bf16.argtypes = [vp, i32, vp, f32, vp, f32, f32, vp]
     lib.dsac_sample_ahead.argtypes = [vp, i32, i32, u64, vp, f32, i32, vp, vp, vp]
     lib.dsac_score_sampled.argtypes = [vp, i32, f32, f32, f32, f64, vp, vp, vp, vp, vp, vp]
     lib.dsac_score_hypotheses.argtypes = [vp, i32, u64, vp, f32, i32, f32, f32, f32, f64, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -94,6 +97,7 @@ def _load():
     lib.dsac_dpnp.argtypes = [vp, i32, vp, f32, vp]
     lib.dsac_score_backward.argtypes = [vp, i32, vp, vp, vp, vp, u32, vp]
     lib.dsac_score_backward_f16.argtypes = [vp, i32, vp, vp, vp, vp, u32, vp]
+    lib.dsac_score_backward_bf16.argtypes = [vp, i32, vp, vp, vp, vp, u32, vp]
     lib.dsac_soft_score_backward.argtypes = [vp, i32, vp, vp, vp, f32, f32, f32, vp, u32, vp]
     lib.dsac_refine.argtypes = [vp, i32, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
     lib.dsac_refine_fd.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, f32, f32, f32, vp, vp, vp, i32, vp]
@@ -130,9 +134,11 @@ def _load():
     lib.dsac_select_frames.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.dsac_soft_score_derr.argtypes = [vp, i32, vp, vp, f32, f32, f32, vp]
     lib.dsac_soft_score_derr_f16.argtypes = [vp, i32, vp, vp, f32, f32, f32, vp]
+    lib.dsac_soft_score_derr_bf16.argtypes = [vp, i32, vp, vp, f32, f32, f32, vp]
     lib.dsac_softmax_frames.argtypes = [vp, i32, i32, vp, f64, vp, vp, vp, vp]
     lib.dsac_process_images_begin.argtypes = [vp, i32, u64, f32, i32, f32, f32, f32, vp, vp, vp, vp, vp]
     lib.dsac_process_images_begin_f16.argtypes = [vp, i32, u64, f32, i32, f32, f32, f32, vp, vp, vp, vp, vp]
+    lib.dsac_process_images_begin_bf16.argtypes = [vp, i32, u64, f32, i32, f32, f32, f32, vp, vp, vp, vp, vp]
     lib.dsac_process_images_finish.argtypes = [vp, i32, vp, f64, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.dsac_refstream_init.argtypes = [vp, u32, i32]
     lib.dsac_refstream_discard.argtypes = [vp, i32, C.c_ulonglong]

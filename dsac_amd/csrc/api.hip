@@ -210,9 +210,9 @@ int out_arg(dsac_ctx* c, T* p, size_t count, T** out, bool preload = false) {
     return DSAC_OK;
 }
 
-// The error images of a K2 call as an output argument: floats, or IEEE binary16 (dk::K2_ELEM_F16) carried as 16-bit words.
+// The error images of a K2 call as an output argument: floats, or IEEE binary16 / bfloat16 (dk::K2_ELEM_F16 / dk::K2_ELEM_BF16) carried as 16-bit words.
 int err_out_arg(dsac_ctx* c, void* p, int elem, size_t count, void** out) {
-    if (elem == dk::K2_ELEM_F16) {
+    if (elem != dk::K2_ELEM_F32) {
         uint16_t* d = nullptr;
         const int rc = out_arg(c, static_cast<uint16_t*>(p), count, &d);
         *out = d;
@@ -268,8 +268,9 @@ struct ProfScope {
 // the cv poses (NULL only in dsac_score_sampled: nothing to split, the fp32 form on K1's records) and F, the frame the launch READS (the slot's own frame in
 // dsac_score_sampled, the current one everywhere else): the records fold its fx, fy and split exponent.  Records that are wanted are built on `st` right in
 // front of the launch and handed to it; records that are not wanted are neither.
-//   err, elem: the error images and their element type -- dk::K2_ELEM_F32 (float) or dk::K2_ELEM_F16 (IEEE binary16: dsac_reproject_f16 /
-//   dsac_process_images_begin_f16, which have checked k2_f16_check before anything was enqueued; only the auto policy's exact vector build stores halves)
+//   err, elem: the error images and their element type -- dk::K2_ELEM_F32 (float), dk::K2_ELEM_F16 (IEEE binary16: dsac_reproject_f16 /
+//   dsac_process_images_begin_f16) or dk::K2_ELEM_BF16 (bfloat16: the _bf16 twins); the 16-bit calls have checked k2_f16_check before anything was enqueued;
+//   only the auto policy's exact vector build stores 16-bit elements)
 //   gated: the launch sits between the context's k2_wait / k2_record events (dsac_set_k2_events)
 //   fallback_stop: the stop event of the launch when profiling attaches no pair to it (the deferred score tails start behind it); *done receives the event
 //   that completes with K2 -- the pair's stop event, else fallback_stop
@@ -396,23 +397,25 @@ int k2_soft_part(dsac_ctx* c, int N, bool want_err, bool want_soft, float* tau, 
     return DSAC_OK;
 }
 
-// Half error images (dsac_reproject_f16, dsac_process_images_begin_f16) exist for the default arithmetic only: the exact-transform vector build.  Every condition is
-// checked here, before the call enqueues anything, and refused by name -- never a silent launch of another form, and "k2_form_last" keeps its value.
-int k2_f16_check(dsac_ctx* c, const char* who, const void* err16) {
+// 16-bit error images (dsac_reproject_f16 / _bf16, dsac_process_images_begin_f16 / _bf16) exist for the default arithmetic only: the exact-transform vector build.
+// Every condition is checked here, before the call enqueues anything, and refused by name -- never a silent launch of another form, and "k2_form_last" keeps its
+// value.  The conditions are the same for both element types; `elem` only picks the word the message uses beside the call's name.
+int k2_f16_check(dsac_ctx* c, const char* who, int elem, const void* err16) {
     const dk::FrameDev& F = c->F;
+    const char* what = elem == dk::K2_ELEM_BF16 ? "bfloat16" : "half";
     if (!err16) return fail(c, DSAC_ERR_INVALID, "%s: err16 must be non-NULL", who);
-    if (F.P % 8 != 0) return fail(c, DSAC_ERR_INVALID, "%s: half error images need H*W %% 8 == 0, this map has %d x %d = %d cells", who, F.H, F.W, F.P);
+    if (F.P % 8 != 0) return fail(c, DSAC_ERR_INVALID, "%s: %s error images need H*W %% 8 == 0, this map has %d x %d = %d cells", who, what, F.H, F.W, F.P);
     if (reinterpret_cast<uintptr_t>(err16) & 15) return fail(c, DSAC_ERR_INVALID, "%s: err16 (%p) must be on a 16-byte address", who, err16);
     if ((reinterpret_cast<uintptr_t>(F.xyz) & 15) || (reinterpret_cast<uintptr_t>(F.uv) & 15))
-        return fail(c, DSAC_ERR_INVALID, "%s: half error images need the frame's xyz (%p) and uv (%p) on 16-byte addresses", who, (const void*)F.xyz, (const void*)F.uv);
+        return fail(c, DSAC_ERR_INVALID, "%s: %s error images need the frame's xyz (%p) and uv (%p) on 16-byte addresses", who, what, (const void*)F.xyz, (const void*)F.uv);
     if (!dk::pose_split_available(F))
-        return fail(c, DSAC_ERR_INVALID, "%s: half error images need a focal length <= 1024 px (the exact-transform form), got fx = %g, fy = %g", who, F.fx, F.fy);
-    if (c->k2.variant != -1) return fail(c, DSAC_ERR_INVALID, "%s: half error images need k2_variant -1 (the auto policy's tiles), it is %d", who, c->k2.variant);
+        return fail(c, DSAC_ERR_INVALID, "%s: %s error images need a focal length <= 1024 px (the exact-transform form), got fx = %g, fy = %g", who, what, F.fx, F.fy);
+    if (c->k2.variant != -1) return fail(c, DSAC_ERR_INVALID, "%s: %s error images need k2_variant -1 (the auto policy's tiles), it is %d", who, what, c->k2.variant);
     const int ex_bits = dk::K2_FLAG_EXACT | dk::K2_FLAG_EXACT_ANY;
     if (c->k2.flags & ~ex_bits)
-        return fail(c, DSAC_ERR_INVALID, "%s: half error images exist for the exact-transform form only: k2_flags 0x%x sets bits other than 28 / 29", who, c->k2.flags);
+        return fail(c, DSAC_ERR_INVALID, "%s: %s error images exist for the exact-transform form only: k2_flags 0x%x sets bits other than 28 / 29", who, what, c->k2.flags);
     if (!c->k2.exact_auto && !(c->k2.flags & ex_bits))
-        return fail(c, DSAC_ERR_INVALID, "%s: half error images need the exact-transform form: k2_exact_auto is 0 and neither k2_flags bit 28 nor 29 is set", who);
+        return fail(c, DSAC_ERR_INVALID, "%s: %s error images need the exact-transform form: k2_exact_auto is 0 and neither k2_flags bit 28 nor 29 is set", who, what);
     return DSAC_OK;
 }
 
@@ -919,7 +922,7 @@ int dsac_sample_refstream_frames(dsac_ctx* c, int hyps_per_frame, float thr, lon
     return end_call(c);
 }
 
-// dsac_reproject and dsac_reproject_f16: one body, the element type of the error images (dk::K2_ELEM_*) travels to the K2 stage
+// dsac_reproject, dsac_reproject_f16 and dsac_reproject_bf16: one body, the element type of the error images (dk::K2_ELEM_*) travels to the K2 stage
 static int reproject_call(dsac_ctx* c, const char* who, int N, const double* poses, float clampv, void* err_or_null, int elem, float tau, float beta,
                           double* soft_or_null) {
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "%s: ctx is NULL", who);
@@ -929,7 +932,7 @@ static int reproject_call(dsac_ctx* c, const char* who, int N, const double* pos
     if (c->F.frames > 1 && (N % c->F.frames != 0 || Nf % dk::K2_NF_MULTIPLE != 0))
         return fail(c, DSAC_ERR_INVALID, "%s: with a frame batch N must be frames x (a multiple of %d), got %d for %d frames", who, dk::K2_NF_MULTIPLE, N, c->F.frames);
     if (N < 0 || !poses) return fail(c, DSAC_ERR_INVALID, "%s: N >= 0 and poses must be non-NULL", who);
-    if (elem == dk::K2_ELEM_F16) ARG_TRY(k2_f16_check(c, who, err_or_null));  // before anything is enqueued
+    if (elem != dk::K2_ELEM_F32) ARG_TRY(k2_f16_check(c, who, elem, err_or_null));  // before anything is enqueued
     if (N == 0 || (!err_or_null && !soft_or_null)) return DSAC_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c);
@@ -956,6 +959,10 @@ int dsac_reproject(dsac_ctx* c, int N, const double* poses, float clampv, float*
 
 int dsac_reproject_f16(dsac_ctx* c, int N, const double* poses, float clampv, uint16_t* err16, float tau, float beta, double* soft_or_null) {
     return reproject_call(c, "dsac_reproject_f16", N, poses, clampv, err16, dk::K2_ELEM_F16, tau, beta, soft_or_null);
+}
+
+int dsac_reproject_bf16(dsac_ctx* c, int N, const double* poses, float clampv, uint16_t* err16, float tau, float beta, double* soft_or_null) {
+    return reproject_call(c, "dsac_reproject_bf16", N, poses, clampv, err16, dk::K2_ELEM_BF16, tau, beta, soft_or_null);
 }
 
 static int softmax_common(dsac_ctx* c, const char* who, int frames, int N, const double* scores, double scale, double* w, double* entropy_or_null,
@@ -1201,7 +1208,7 @@ int dsac_set_option(dsac_ctx* c, const char* key, int value) {
     else if (k == "k2_diag") c->k2.diag = value;
     else if (k == "k2_exact_auto") c->k2.exact_auto = value != 0;
     else if (k == "k2_f16_store") {
-        if (value != 0 && value != 1) return fail(c, DSAC_ERR_INVALID, "dsac_set_option: k2_f16_store is 0 (8-byte stores) or 1 (16-byte stores after a lane exchange)");
+        if (value != 0 && value != 1) return fail(c, DSAC_ERR_INVALID, "dsac_set_option: k2_f16_store (both 16-bit builds, binary16 and bfloat16) is 0 (8-byte stores) or 1 (16-byte stores after a lane exchange)");
         c->k2.f16_store = value;
     }
     else if (k == "k6_walk_exact") c->k6_walk_exact = value != 0;
@@ -1358,15 +1365,17 @@ int dsac_profile_read(dsac_ctx* c, int which, double* ms_total, int* launches, i
     return DSAC_OK;
 }
 
-// What dsac_score_backward_f16 needs beyond the float call, checked before anything is staged or enqueued.  Half gradient images are read by the matrix-core form
+// What dsac_score_backward_f16 and dsac_score_backward_bf16 need beyond the float call (elem: dk::K4_ELEM_*; the conditions are the same but for the forms
+// bfloat16 is not built for, the messages name the element type), checked before anything is staged or enqueued.  Half gradient images are read by the matrix-core form
 // only, and whether a call gets that form is backward_plan's decision alone: the check asks the plan itself, frame by frame (the single-frame plan of every frame
 // of a batch, on that frame's own xyz / uv and its slice of d_err16 -- a host d_err16 is held to the alignment its staged copy will have anyway), and refuses
 // where it answers with the VALU form.  The conditions spelled out below only put a name to the plan's answer for dsac_last_error; they decide nothing.
-static int k4_f16_check(dsac_ctx* c, const char* who, int N, const uint16_t* d_err16, unsigned flags) {
+static int k4_f16_check(dsac_ctx* c, const char* who, int elem, int N, const uint16_t* d_err16, unsigned flags) {
     const dk::FrameDev& F = c->F;
+    const char* what = elem == dk::K4_ELEM_BF16 ? "bfloat16" : "half";
     if (flags & (DSAC_BWD_PARITY_FP64 | DSAC_BWD_QUIRK_ROT_WRITEBACK))
-        return fail(c, DSAC_ERR_INVALID, "%s: half gradient images exist for the fp32 matrix-core form only: DSAC_BWD_PARITY_FP64 / DSAC_BWD_QUIRK_ROT_WRITEBACK read floats "
-                                         "(dsac_score_backward)", who);
+        return fail(c, DSAC_ERR_INVALID, "%s: %s gradient images exist for the fp32 matrix-core form only: DSAC_BWD_PARITY_FP64 / DSAC_BWD_QUIRK_ROT_WRITEBACK read floats "
+                                         "(dsac_score_backward)", who, what);
     const int frames = F.frames > 1 ? F.frames : 1;
     const int n1 = N / frames;
     for (int f = 0; f < frames; f++) {
@@ -1376,21 +1385,28 @@ static int k4_f16_check(dsac_ctx* c, const char* who, int N, const uint16_t* d_e
         if (Fd.uv) Fd.uv = F.uv + (size_t)f * F.uv_stride;
         Fd.xyz_stride = Fd.uv_stride = 0;
         const uint16_t* d = d_err16 + (size_t)f * n1 * F.P;
-        if (dk::backward_plan(n1, Fd, d, c->k4_variant, 0, dk::K4_ELEM_F16).variant > 0) continue;
-        if (F.P % 4 != 0) return fail(c, DSAC_ERR_INVALID, "%s: half gradient images need H*W %% 4 == 0, this map has %d x %d = %d cells", who, F.H, F.W, F.P);
-        if (!F.uv && F.W % 4 != 0) return fail(c, DSAC_ERR_INVALID, "%s: half gradient images on the implicit pixel grid need W %% 4 == 0, W is %d", who, F.W);
+        const int form = dk::backward_plan(n1, Fd, d, c->k4_variant, 0, elem).variant;
+        if (form > 0) {
+            // bfloat16 is built for the forms without scratch only (dk::k4_form_has_bf16): the 5- and 6-chunk and the high-occupancy knobs are refused by name
+            if (elem == dk::K4_ELEM_BF16 && !dk::k4_form_has_bf16(form))
+                return fail(c, DSAC_ERR_INVALID, "%s: k4_variant %d names form %d, which is not built for bfloat16 gradient images (forms 1, 2 and 5 are: the others need "
+                                                 "scratch in every element type)", who, c->k4_variant, form);
+            continue;
+        }
+        if (F.P % 4 != 0) return fail(c, DSAC_ERR_INVALID, "%s: %s gradient images need H*W %% 4 == 0, this map has %d x %d = %d cells", who, what, F.H, F.W, F.P);
+        if (!F.uv && F.W % 4 != 0) return fail(c, DSAC_ERR_INVALID, "%s: %s gradient images on the implicit pixel grid need W %% 4 == 0, W is %d", who, what, F.W);
         if ((reinterpret_cast<uintptr_t>(Fd.xyz) & 15) || (reinterpret_cast<uintptr_t>(Fd.uv) & 15))
-            return fail(c, DSAC_ERR_INVALID, "%s: half gradient images need every frame's xyz and uv on 16-byte addresses (frame %d: %p, %p)", who, f, (const void*)Fd.xyz,
+            return fail(c, DSAC_ERR_INVALID, "%s: %s gradient images need every frame's xyz and uv on 16-byte addresses (frame %d: %p, %p)", who, what, f, (const void*)Fd.xyz,
                         (const void*)Fd.uv);
         if (reinterpret_cast<uintptr_t>(d) & 7) return fail(c, DSAC_ERR_INVALID, "%s: d_err16 (%p) must be on an 8-byte address", who, (const void*)d_err16);
         if (c->k4_variant >= 0 && (c->k4_variant % 1000) % 10 == 0)
-            return fail(c, DSAC_ERR_INVALID, "%s: k4_variant %d names the VALU form, which reads no half gradient images", who, c->k4_variant);
-        return fail(c, DSAC_ERR_INVALID, "%s: the matrix-core form, the only one that reads half gradient images, is not available for this frame and k4_variant %d", who, c->k4_variant);
+            return fail(c, DSAC_ERR_INVALID, "%s: k4_variant %d names the VALU form, which reads no %s gradient images", who, c->k4_variant, what);
+        return fail(c, DSAC_ERR_INVALID, "%s: the matrix-core form, the only one that reads %s gradient images, is not available for this frame and k4_variant %d", who, what, c->k4_variant);
     }
     return DSAC_OK;
 }
 
-// d_err: N x P floats (elem == dk::K4_ELEM_F32) or IEEE binary16 carried as 16-bit words (dk::K4_ELEM_F16: dsac_score_backward_f16), NULL with g
+// d_err: N x P floats (elem == dk::K4_ELEM_F32) or IEEE binary16 / bfloat16 carried as 16-bit words (dk::K4_ELEM_F16: dsac_score_backward_f16, dk::K4_ELEM_BF16: dsac_score_backward_bf16), NULL with g
 static int score_backward_common(dsac_ctx* c, const char* who, int N, const double* poses, const int32_t* sets, const void* d_err, int elem,
                                  const double* g, float clampv, float tau, float beta, const double* dpnp_or_null, unsigned flags,
                                  double* grad_xyz) {
@@ -1413,8 +1429,8 @@ static int score_backward_common(dsac_ctx* c, const char* who, int N, const doub
         return fail(c, DSAC_ERR_INVALID, "%s: DSAC_BWD_QUIRK_ROT_WRITEBACK needs DSAC_BWD_PARITY_FP64 (the write-back is a sequential recurrence)", who);
     if (parity && (!d_err || (long long)(frames > 1 ? Nf : N) * c->F.P > (1ll << 26)))
         return fail(c, DSAC_ERR_INVALID, "%s: DSAC_BWD_PARITY_FP64 takes a d_err volume with N*H*W <= 2^26 (reference-sized maps)", who);
-    const bool f16 = elem == dk::K4_ELEM_F16;
-    if (f16 && N > 0) ARG_TRY(k4_f16_check(c, who, N, static_cast<const uint16_t*>(d_err), flags));
+    const bool f16 = elem != dk::K4_ELEM_F32;  // either 16-bit element type
+    if (f16 && N > 0) ARG_TRY(k4_f16_check(c, who, elem, N, static_cast<const uint16_t*>(d_err), flags));
     if (N == 0) return DSAC_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c);
@@ -1425,7 +1441,7 @@ static int score_backward_common(dsac_ctx* c, const char* who, int N, const doub
     double* d_grad;
     ARG_TRY(in_arg(c, poses, (size_t)N * 6, &d_poses));
     ARG_TRY(in_arg(c, sets, (size_t)N * 4, &d_sets));
-    if (f16) {  // host halves are staged at 2 bytes per element
+    if (f16) {  // host halves / bfloat16 are staged at 2 bytes per element
         const uint16_t* d16;
         ARG_TRY(in_arg(c, static_cast<const uint16_t*>(d_err), (size_t)N * P, &d16));
         d_derr = d16;
@@ -1546,6 +1562,12 @@ int dsac_score_backward_f16(dsac_ctx* c, int N, const double* poses, const int32
                             unsigned flags, double* grad_xyz) {
     if (c && !d_err16) return fail(c, DSAC_ERR_INVALID, "dsac_score_backward_f16: d_err16 is NULL");
     return score_backward_common(c, "dsac_score_backward_f16", N, poses, sets, d_err16, dk::K4_ELEM_F16, nullptr, 100.0f, 0.f, 0.f, dpnp_or_null, flags, grad_xyz);
+}
+
+int dsac_score_backward_bf16(dsac_ctx* c, int N, const double* poses, const int32_t* sets, const uint16_t* d_err16, const double* dpnp_or_null,
+                             unsigned flags, double* grad_xyz) {
+    if (c && !d_err16) return fail(c, DSAC_ERR_INVALID, "dsac_score_backward_bf16: d_err16 is NULL");
+    return score_backward_common(c, "dsac_score_backward_bf16", N, poses, sets, d_err16, dk::K4_ELEM_BF16, nullptr, 100.0f, 0.f, 0.f, dpnp_or_null, flags, grad_xyz);
 }
 
 int dsac_soft_score_backward(dsac_ctx* c, int N, const double* poses, const int32_t* sets, const double* g, float clampv, float tau, float beta,
@@ -1902,11 +1924,12 @@ int dsac_select_frames(dsac_ctx* c, int frames, int N, const double* probs, cons
 
 // d_err[h][p] = g[h] * d soft[h] / d err[h][p] = g[h] * (-beta) * s (1 - s),  s = sigmoid(beta (tau - err[h][p])); zero where the residual sits on the clamp
 // (the score no longer depends on it there -- what K4's in-kernel form does, k_backward.hip).  Four cells per lane (one float4, or four halves in 8 bytes:
-// dsac_soft_score_derr_f16 -- widened on the load, the same fp32 arithmetic, rounded to nearest even on the store), the row index from the launch's y.
+// dsac_soft_score_derr_f16, or four bfloat16: dsac_soft_score_derr_bf16 -- widened on the load, the same fp32 arithmetic, rounded to nearest even on the store), the row index from the launch's y.
 extern "C++" {  // templates: the element type of the images
 namespace {
 typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-template <typename V4, typename E>  // V4: four cells as one vector -- float4 of E = float, or four E = _Float16 in 8 bytes
+typedef __bf16 bf4_t __attribute__((ext_vector_type(4)));
+template <typename V4, typename E>  // V4: four cells as one vector -- float4 of E = float, or four E = _Float16 / __bf16 in 8 bytes
 __global__ __launch_bounds__(256) void k_soft_derr(int P4, const V4* __restrict__ err, const double* __restrict__ g, float clampv, float tau, float beta,
                                                    V4* __restrict__ d_err) {
     const size_t h = blockIdx.y;
@@ -1923,11 +1946,13 @@ __global__ __launch_bounds__(256) void k_soft_derr(int P4, const V4* __restrict_
             const float s = 1.f / (1.f + __expf(-beta * (tau - in[k])));
             out[k] = in[k] >= clampv ? 0.f : gh * s * (1.f - s);
         }
-        if constexpr (std::is_same<E, _Float16>::value) {
+        if constexpr (sizeof(E) == 2) {
             // The half store rounds the fp32 result, the float kernel's float, to nearest even (v_cvt_f16_f32; subnormal results kept).  Left to itself the compiler
             // folds the last multiply into the conversion (v_fma_mixlo_f16: the exact product rounded to half ONCE), which is one half ulp off the float call's
             // rounded float on about 1 cell in 20 000.  There is no builtin for "convert, do not fuse"; the empty statement pins the float in a register first.
             // tests/test_gpu_k4_f16.py::test_soft_score_derr_in_half compares the bits of every cell and fails if a compiler fuses the two again.
+            // The pin covers both 16-bit types: the bfloat16 store likewise takes the float kernel's float and rounds it once (v_cvt_pk_bf16_f32;
+            // tests/test_gpu_k4_bf16.py::test_soft_score_derr_in_bfloat16).
 #pragma unroll
             for (int k = 0; k < 4; k++) asm volatile("" : "+v"(out[k]));
         }
@@ -1936,14 +1961,14 @@ __global__ __launch_bounds__(256) void k_soft_derr(int P4, const V4* __restrict_
     }
 }
 
-// shared by dsac_soft_score_derr (V4 = float4, 16-byte vectors) and dsac_soft_score_derr_f16 (V4 = four halves, 8-byte vectors); T: the C ABI's element type
+// shared by dsac_soft_score_derr (V4 = float4, 16-byte vectors), dsac_soft_score_derr_f16 and dsac_soft_score_derr_bf16 (V4 = four halves / bfloat16, 8-byte vectors); T: the C ABI's element type
 template <typename V4, typename E, typename T>
 int soft_derr_call(dsac_ctx* c, const char* who, int N, const double* g, const T* err, float clampv, float tau, float beta, T* d_err) {
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "%s: ctx is NULL", who);
     if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "%s: no frame set (the maps are H*W wide)", who);
     if (N < 0 || !g || !err || !d_err || !(beta > 0.f)) return fail(c, DSAC_ERR_INVALID, "%s: NULL argument, negative count or beta <= 0", who);
     if (c->F.P % 4 != 0) return fail(c, DSAC_ERR_INVALID, "%s: H*W must be a multiple of 4", who);
-    if (std::is_same<E, _Float16>::value && ((reinterpret_cast<uintptr_t>(err) | reinterpret_cast<uintptr_t>(d_err)) % sizeof(V4)) != 0)  // the half call: before anything is staged
+    if (sizeof(E) == 2 && ((reinterpret_cast<uintptr_t>(err) | reinterpret_cast<uintptr_t>(d_err)) % sizeof(V4)) != 0)  // the 16-bit calls: before anything is staged
         return fail(c, DSAC_ERR_INVALID, "%s: err16 (%p) / d_err16 (%p) must be on 8-byte addresses", who, (const void*)err, (const void*)d_err);
     if (N == 0) return DSAC_OK;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1976,6 +2001,10 @@ int dsac_soft_score_derr(dsac_ctx* c, int N, const double* g, const float* err, 
 
 int dsac_soft_score_derr_f16(dsac_ctx* c, int N, const double* g, const uint16_t* err16, float clampv, float tau, float beta, uint16_t* d_err16) {
     return soft_derr_call<half4_t, _Float16>(c, "dsac_soft_score_derr_f16", N, g, err16, clampv, tau, beta, d_err16);
+}
+
+int dsac_soft_score_derr_bf16(dsac_ctx* c, int N, const double* g, const uint16_t* err16, float clampv, float tau, float beta, uint16_t* d_err16) {
+    return soft_derr_call<bf4_t, __bf16>(c, "dsac_soft_score_derr_bf16", N, g, err16, clampv, tau, beta, d_err16);
 }
 
 // ---- shared by dsac_process_images and the begin / finish pair -------------------------------------------------------------------------------
@@ -2134,7 +2163,7 @@ int dsac_process_images(dsac_ctx* c, int hyps_per_frame, uint64_t seed, float th
 // core/cnn_softam.h:1066-1078 is  getDiffMap x N -> forward(diffMaps) -> softMax : begin leaves the error images of every frame in HBM, the caller's
 // score model (the reference's score CNN; any device code on the context's stream) turns them into frames x hyps_per_frame scores, finish continues
 // with K3 -> K6 -> K7.  The deferral modes of dsac_process_images apply to the pair (the tails start in finish).
-// dsac_process_images_begin and dsac_process_images_begin_f16: one body, the element type of the error images (dk::K2_ELEM_*) travels to the K2 stage
+// dsac_process_images_begin, dsac_process_images_begin_f16 and dsac_process_images_begin_bf16: one body, the element type of the error images (dk::K2_ELEM_*) travels to the K2 stage
 static int pi_begin_call(dsac_ctx* c, const char* who, int hyps_per_frame, uint64_t seed, float thr, int max_tries, float clampv, float tau, float beta, double* poses,
                          int32_t* sets_out, uint8_t* ok, void* err, int elem, double* soft_or_null) {
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "%s: ctx is NULL", who);
@@ -2147,7 +2176,7 @@ static int pi_begin_call(dsac_ctx* c, const char* who, int hyps_per_frame, uint6
     if (!poses || !sets_out || !ok || (!err && !soft_or_null))
         return fail(c, DSAC_ERR_INVALID, "%s: poses / sets_out / ok and at least one of err / soft must be non-NULL", who);
     if (max_tries <= 0 || c->F.P < 4) return fail(c, DSAC_ERR_INVALID, "%s: max_tries > 0 and a frame of at least 4 cells needed", who);
-    if (elem == dk::K2_ELEM_F16) ARG_TRY(k2_f16_check(c, who, err));  // before anything is enqueued
+    if (elem != dk::K2_ELEM_F32) ARG_TRY(k2_f16_check(c, who, elem, err));  // before anything is enqueued
     if (c->pi_refstream) ARG_TRY(pi_refstream_check(c, (std::string(who) + " (pi_refstream)").c_str(), hyps_per_frame));  // before anything is enqueued
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c, /*keep_tail=*/c->pi_defer_tail != 0);
@@ -2186,6 +2215,12 @@ int dsac_process_images_begin(dsac_ctx* c, int hyps_per_frame, uint64_t seed, fl
 int dsac_process_images_begin_f16(dsac_ctx* c, int hyps_per_frame, uint64_t seed, float thr, int max_tries, float clampv, float tau, float beta, double* poses,
                                   int32_t* sets_out, uint8_t* ok, uint16_t* err16, double* soft_or_null) {
     return pi_begin_call(c, "dsac_process_images_begin_f16", hyps_per_frame, seed, thr, max_tries, clampv, tau, beta, poses, sets_out, ok, err16, dk::K2_ELEM_F16,
+                         soft_or_null);
+}
+
+int dsac_process_images_begin_bf16(dsac_ctx* c, int hyps_per_frame, uint64_t seed, float thr, int max_tries, float clampv, float tau, float beta, double* poses,
+                                   int32_t* sets_out, uint8_t* ok, uint16_t* err16, double* soft_or_null) {
+    return pi_begin_call(c, "dsac_process_images_begin_bf16", hyps_per_frame, seed, thr, max_tries, clampv, tau, beta, poses, sets_out, ok, err16, dk::K2_ELEM_BF16,
                          soft_or_null);
 }
 

@@ -349,7 +349,11 @@ DM_INLINE float row16_sum_f(float v) {  // sum over the 16 lanes of a DPP row, r
 // ET: element type of d_err -- float, or _Float16 (dsac_score_backward_f16: IEEE binary16 gradient images; the non-SOFTMODE builds only).  The half build is
 // the float build with an 8-byte load of a lane's 4 pixels instead of a 16-byte one and one widening conversion per (hypothesis, pixel) pair -- exact,
 // subnormal halves included --, so that under the same launch plan it returns the float build's result on the widened values bit for bit.
+// ET = __bf16 (dsac_score_backward_bf16: bfloat16 gradient images): the same 8-byte load, kept as two dwords; a bfloat16 is the upper half of the float of the
+// same value, so the widening is one shift (low element) or one mask (high element) per pair -- exact for every pattern, subnormals, infinities and NaN included.
+// The landing-register and software-pipeline layout is the half build's.
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+typedef unsigned k4_u2 __attribute__((ext_vector_type(2)));
 template <int CH, bool SOFTMODE, bool UV, int MINW, typename ET = float>
 __global__ __launch_bounds__(K4_THREADS, MINW) void k_score_backward_mfma(const float* __restrict__ rec, const float* __restrict__ xyz,
                                                                     const float* __restrict__ uv, const ET* __restrict__ d_err,
@@ -473,9 +477,10 @@ __global__ __launch_bounds__(K4_THREADS, MINW) void k_score_backward_mfma(const 
             for (int pp = 0; pp < 2; pp++) gx[ch][pp] = gy[ch][pp] = gz[ch][pp] = zero2;
 
         // d_err of the first group (one dwordx4 per chunk: 4 consecutive pixels of hypothesis c; the half build: one dwordx2, half the landing registers)
-        constexpr bool F16 = sizeof(ET) == 2;
-        using W4 = typename std::conditional<F16, h4, f4>::type;
-        const W4 zw = {0, 0, 0, 0};
+        constexpr bool BF16 = std::is_same<ET, __bf16>::value;
+        constexpr bool F16 = sizeof(ET) == 2 && !BF16;
+        using W4 = typename std::conditional<BF16, k4_u2, typename std::conditional<F16, h4, f4>::type>::type;
+        const W4 zw = W4{};
         W4 wn[CH];
         // Every lane loads, from a clamped address (ragged hypothesis end -> the tile's last row, pixels beyond the map -> the last 4): a load under a
         // lane mask is a branch around the instruction, hipcc's wait-count pass then no longer knows how many loads are in flight and waits vmcnt(0) at
@@ -557,6 +562,10 @@ __global__ __launch_bounds__(K4_THREADS, MINW) void k_score_backward_mfma(const 
                         const float gb = c2.y * (-beta);
                         w = (sg * f2{gb, gb}) * (f2{1.f, 1.f} - sg);
                     } else {
+                        if constexpr (BF16) {
+                            const unsigned d = pp ? wv[ch].y : wv[ch].x;  // two bfloat16: v_lshlrev_b32 16, v_and_b32 0xffff0000, exact
+                            w = f2{__uint_as_float(d << 16), __uint_as_float(d & 0xffff0000u)};
+                        } else
                         w = pp ? f2{(float)wv[ch].z, (float)wv[ch].w} : f2{(float)wv[ch].x, (float)wv[ch].y};  // half build: v_cvt_f32_f16, exact
                         if (K4_ABLATE & 16) w = f2{c2.y, c2.z} + ex;
                     }
@@ -716,7 +725,7 @@ K4Plan backward_plan(int N, const FrameDev& F, const void* d_err, int variant, i
     pl.glayers = 1;
     pl.elem = elem;
     // a lane reads its 4 pixels of d_err as one vector: 16 bytes of floats, 8 bytes of halves -- everything else of the plan is the same for both
-    const uintptr_t derr_mask = elem == K4_ELEM_F16 ? 7 : 15;
+    const uintptr_t derr_mask = elem != K4_ELEM_F32 ? 7 : 15;
     const bool batch = Nf > 0 && F.frames > 1;
     // a frame's hypotheses as ONE tile up to 256, beyond that (round 6) as several equal tiles of the same launch: the largest multiple of 16 up to 256 that
     // divides the count (384 -> 192, 512 -> 256, 1024 -> 256); the tiles of a frame add into its gradient with fp64 atomics like the tiles of one big frame
@@ -797,8 +806,9 @@ hipError_t score_backward(hipStream_t st, int N, const float* staged_bwd, const 
     if (N <= 0) return hipSuccess;
     const int HT = plan.HT, NT = plan.NT;
     const bool soft = d_err_any == nullptr;
-    const bool f16 = plan.elem == K4_ELEM_F16;
-    if (f16 && (soft || plan.variant <= 0)) return hipErrorInvalidValue;  // half gradient images: the matrix-core form only, nothing takes another form silently
+    const bool bf16 = plan.elem == K4_ELEM_BF16;
+    const bool f16 = plan.elem == K4_ELEM_F16 || bf16;  // either 16-bit element type
+    if (f16 && (soft || plan.variant <= 0)) return hipErrorInvalidValue;  // 16-bit gradient images: the matrix-core form only, nothing takes another form silently
     const float* d_err = f16 ? nullptr : static_cast<const float*>(d_err_any);  // the VALU form below reads floats
     const float LOG2E = 1.4426950408889634f;
     const float kA = beta * LOG2E, kB = -beta * tau * LOG2E;
@@ -824,22 +834,29 @@ hipError_t score_backward(hipStream_t st, int N, const float* staged_bwd, const 
                            grad_part, G12_part, N, F.P, F.W, PT, NT, G, F.fx, F.cx, F.cy, clampv, kA, kB, beta, HT, k_poses, k_direct, flags,   \
                            plan.Nf, F.xyz_stride, F.uv_stride);                                                                                  \
     } while (0)
-#define DSAC_K4M_CH(C_, W_)                                                                              \
+    // the bfloat16 builds exist for the forms that need no scratch (k4_form_has_bf16: 2, 3 and 4 chunks at two waves per SIMD); the entry point has refused
+    // the others by name, a launch that gets here all the same is an error
+#define DSAC_K4M_BF(C_, W_) do { if (UV) DSAC_K4M(C_, false, true, W_, __bf16); else DSAC_K4M(C_, false, false, W_, __bf16); } while (0)
+#define DSAC_K4M_NOBF(C_, W_) return hipErrorNotSupported
+#define DSAC_K4M_CH(C_, W_, BF_)                                                                         \
     do {                                                                                                 \
         if (soft) { if (UV) DSAC_K4M(C_, true, true, W_, float); else DSAC_K4M(C_, true, false, W_, float); }          \
+        else if (bf16) { BF_(C_, W_); }                                                                  \
         else if (f16) { if (UV) DSAC_K4M(C_, false, true, W_, _Float16); else DSAC_K4M(C_, false, false, W_, _Float16); } \
         else { if (UV) DSAC_K4M(C_, false, true, W_, float); else DSAC_K4M(C_, false, false, W_, float); }             \
     } while (0)
-        if (plan.variant == 6) DSAC_K4M_CH(2, 4);
-        else if (plan.variant == 7) DSAC_K4M_CH(3, 3);
+        if (plan.variant == 6) DSAC_K4M_CH(2, 4, DSAC_K4M_NOBF);
+        else if (plan.variant == 7) DSAC_K4M_CH(3, 3, DSAC_K4M_NOBF);
         else switch (CH) {
-            case 2: DSAC_K4M_CH(2, 2); break;
-            case 3: DSAC_K4M_CH(3, 2); break;
-            case 4: DSAC_K4M_CH(4, 2); break;
-            case 5: DSAC_K4M_CH(5, 2); break;
-            default: DSAC_K4M_CH(6, 2); break;
+            case 2: DSAC_K4M_CH(2, 2, DSAC_K4M_BF); break;
+            case 3: DSAC_K4M_CH(3, 2, DSAC_K4M_BF); break;
+            case 4: DSAC_K4M_CH(4, 2, DSAC_K4M_BF); break;
+            case 5: DSAC_K4M_CH(5, 2, DSAC_K4M_NOBF); break;
+            default: DSAC_K4M_CH(6, 2, DSAC_K4M_NOBF); break;
         }
 #undef DSAC_K4M_CH
+#undef DSAC_K4M_BF
+#undef DSAC_K4M_NOBF
 #undef DSAC_K4M
         return hipGetLastError();
     }

@@ -546,6 +546,11 @@ DM_INLINE bool hp_chunk_ex(const ExOps& A, const h8 (&B8)[4], const f2 (&ppix)[4
 typedef unsigned u4v __attribute__((ext_vector_type(4)));
 typedef _Float16 h2v __attribute__((ext_vector_type(2)));
 DM_INLINE unsigned pk_h2(float a, float b) { return __builtin_bit_cast(unsigned, __builtin_convertvector(f2{a, b}, h2v)); }
+// two floats as two bfloat16 in a dword, each rounded to nearest even (v_cvt_pk_bf16_f32 on gfx950; NaN stays NaN): the error images of dsac_reproject_bf16
+typedef __bf16 b2v __attribute__((ext_vector_type(2)));
+DM_INLINE unsigned pk_b2(float a, float b) { return __builtin_bit_cast(unsigned, __builtin_convertvector(f2{a, b}, b2v)); }
+// the packer of the 16-bit stores by element type
+template <bool BF> DM_INLINE unsigned pk_e2(float a, float b) { if constexpr (BF) return pk_b2(a, b); else return pk_h2(a, b); }
 // The lanes of quarter 3 (the translation) run the same code on the constant SPLIT_T_COORD = 2^15 + 1, whose pieces are the powers of two
 // (2^10, 2^3, 2^11, 0, 0, 0, 1, 0) that the translation pieces of k_pose_prep_split are scaled against -- no select between coordinates and constants.
 constexpr float SPLIT_T_COORD = 32769.0f;
@@ -760,13 +765,15 @@ typedef f4 f4_a4 __attribute__((aligned(4)));
 //   LAYOUT 2: lanes c and c ^ 1 hold cells 8k .. 8k + 3 and 8k + 4 .. 8k + 7 of the same four rows (both exist or neither).  The even lane takes rows 0 and 1 of
 //             all eight cells, the odd lane rows 2 and 3: every dword of a stored row is the lane's own or its neighbour's (quad_perm [1, 0, 3, 2]), one select
 //             each; two 16-byte stores per lane and chunk
+// BF: the values are rounded to bfloat16 instead (k_reproject_st<.., EXF = 5 / 6>, dsac_reproject_bf16) -- only the packing of two floats into a dword differs; the
+// lane exchange and the stores move packed dwords and are the same code
 typedef unsigned u2v __attribute__((ext_vector_type(2)));
-template <int LAYOUT>
+template <int LAYOUT, bool BF = false>
 DM_INLINE void store_rows_h16(_Float16* base, const f4 (&ev)[4], int P, int p0, int g, int c, bool full, int rows) {
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0xffffffffu, 0x00020000);
     unsigned pk[4][2];
 #pragma unroll
-    for (int r = 0; r < 4; r++) { pk[r][0] = pk_h2(ev[r].x, ev[r].y); pk[r][1] = pk_h2(ev[r].z, ev[r].w); }
+    for (int r = 0; r < 4; r++) { pk[r][0] = pk_e2<BF>(ev[r].x, ev[r].y); pk[r][1] = pk_e2<BF>(ev[r].z, ev[r].w); }
     if constexpr (LAYOUT == 1) {
         const unsigned loff = ((unsigned)(4 * g) * (unsigned)P + (unsigned)p0) * 2u;
         if (full) {
@@ -810,7 +817,9 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* 
     // EXF = 3 / 4: EXF = 2 with the error images stored as IEEE binary16 (dsac_reproject_f16; `err` then points to halves).  Everything up to ev[r] and the sigmoid
     // sums is EXF = 2's code; only the store differs: 3 = four 8-byte stores per lane and chunk, 4 = lanes c and c ^ 1 trade rows, two 16-byte stores of 8 cells each.
     // The element type rides in EXF and not in a parameter of its own so that the float kernels keep their names (the Makefile's ISA-mix targets select by name)
-    constexpr int H16 = EXF >= 3 ? EXF - 2 : 0;
+    // EXF = 5 / 6: the same two store layouts with the values rounded to bfloat16 (dsac_reproject_bf16): 5 = layout 1, 6 = layout 2
+    constexpr bool BF16 = EXF >= 5;
+    constexpr int H16 = EXF >= 5 ? EXF - 4 : EXF >= 3 ? EXF - 2 : 0;
     static_assert(H16 == 0 || (ERR && ANY == 0 && !LO), "half error images: the vector build of the exact form, with an error image to store");
     const int b = blockIdx.x;
     int ht, pt;
@@ -1053,7 +1062,7 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* 
                 }
             }
             if constexpr (H16 != 0) {
-                if (valid[ch]) store_rows_h16<H16>(reinterpret_cast<_Float16*>(err) + (size_t)(h0 + 16 * gi) * P, ev, P, p0[ch], g, c, nh == HT, nh - hyp0);
+                if (valid[ch]) store_rows_h16<H16, BF16>(reinterpret_cast<_Float16*>(err) + (size_t)(h0 + 16 * gi) * P, ev, P, p0[ch], g, c, nh == HT, nh - hyp0);
             }
             if (H16 == 0 && ERR && valid[ch] && fast_stores) {
                 // buffer store: the address is a wave-uniform row base in a scalar resource (the tile's first hypothesis of this group) + a scalar row offset +
@@ -1276,6 +1285,15 @@ static hipError_t launch_reproject_ps(hipStream_t st, int N, const float* staged
     return hipGetLastError();
 }
 
+// The store layout of a bfloat16 build (EX = 5: 8-byte stores, 6: 16-byte stores after the lane exchange) for one instantiation.  Two builds of the small tile
+// at its 168-register budget (implicit grid, W % 64 != 0) spill 12 bytes per lane in one layout and nothing in the other -- error images only in layout 1, err + soft
+// in layout 2, as their binary16 twins do --; the bfloat16 call takes the other layout there, whatever "k2_f16_store" says: the stored values do not depend on
+// the layout, and no bfloat16 build needs scratch.  Every other EX is returned as it is (the float and binary16 kernels keep their instantiations)
+template <int NG, int CHW, int MINW, int EX>
+constexpr int k2_bf16_exf(bool soft, bool uv, bool g64) {
+    if (EX >= 5 && NG == 4 && CHW == 1 && MINW == 3 && !uv && !g64) return soft ? 5 : 6;
+    return EX;
+}
 template <int NG, int CHW, int WAVES, bool PW, int MINW = 1, bool LO = false, int EX = 0, int ANY = 0>
 static hipError_t launch_reproject_st(hipStream_t st, int N, const float* staged, const FrameDev& F, float clampv, float* err, float kA, float kB,
                                       float* soft_part, int* tiles_used, int Nf, int kflags, hipEvent_t evA, hipEvent_t evB, const float* staged_lo = nullptr,
@@ -1290,7 +1308,7 @@ static hipError_t launch_reproject_st(hipStream_t st, int N, const float* staged
     const bool ERR = err != nullptr, SOFT = soft_part != nullptr, UV = F.uv != nullptr;
     const bool G64 = !UV && (F.W & 63) == 0;
 #define DSAC_K2S(E, S, U, G)                                                                                                               \
-    hipExtLaunchKernelGGL((k_reproject_st<NG, CHW, WAVES, PW, E, S, U, G, MINW, LO, EX, ANY>), dim3(grid), dim3(WAVES * 64), 0, st, evA, evB, 0, staged, F.xyz, F.uv, err, \
+    hipExtLaunchKernelGGL((k_reproject_st<NG, CHW, WAVES, PW, E, S, U, G, MINW, LO, k2_bf16_exf<NG, CHW, MINW, EX>(S, U, G), ANY>), dim3(grid), dim3(WAVES * 64), 0, st, evA, evB, 0, staged, F.xyz, F.uv, err, \
                           soft_part, N, F.P, F.W, PT, F.cx, F.cy, clampv, kA, kB, kflags, Nf, F.xyz_stride, F.uv_stride, staged_lo, split)
     if (ERR && SOFT) { if (UV) DSAC_K2S(true, true, true, false); else if (G64) DSAC_K2S(true, true, false, true); else DSAC_K2S(true, true, false, false); }
     else if (ERR) { if (UV) DSAC_K2S(true, false, true, false); else if (G64) DSAC_K2S(true, false, false, true); else DSAC_K2S(true, false, false, false); }
@@ -1607,9 +1625,9 @@ hipError_t reproject(hipStream_t st, int N, const float* staged, const FrameDev&
     } else if (opts.variant >= 0 && !ex_variant) why |= K2_WHY_FORCED;
     if (!pose_split_available(F)) why |= K2_WHY_FOCAL;
     if (!opts.poses64) why |= K2_WHY_NO_POSES;  // dsac_score_sampled without the cv poses: nothing to split
-    // half error images (dsac_reproject_f16 / dsac_process_images_begin_f16): the auto policy's exact vector build and nothing else -- the entry points have refused
+    // 16-bit error images (dsac_reproject_f16 / _bf16, dsac_process_images_begin_f16 / _bf16): the auto policy's exact vector build and nothing else -- the entry points have refused
     // every other request by name; a launch that gets here all the same is an error, never another form and never a float store into a half buffer
-    if (opts.err_elem == K2_ELEM_F16 && !(err && vec && F.P % 8 == 0 && split_ok && opts.variant < 0 && k2_wants_exact(opts) &&
+    if (opts.err_elem != K2_ELEM_F32 && !(err && vec && F.P % 8 == 0 && split_ok && opts.variant < 0 && k2_wants_exact(opts) &&
                                           !(opts.flags & ~(K2_FLAG_EXACT | K2_FLAG_EXACT_ANY))))
         return hipErrorNotSupported;
     auto report = [&](int form) { if (opts.report) { opts.report[0] = form; opts.report[1] = (form == K2_FORM_EXACT_VEC || form == K2_FORM_EXACT_ANY) ? 0 : why; } };
@@ -1677,6 +1695,11 @@ hipError_t reproject(hipStream_t st, int N, const float* staged, const FrameDev&
                 if (opts.err_elem == K2_ELEM_F16) {
                     if (opts.f16_store == 0) return F.P <= 16384 ? DSAC_EX(4, 1, 3, 3) : DSAC_EX(4, 4, 2, 3);
                     return F.P <= 16384 ? DSAC_EX(4, 1, 3, 4) : DSAC_EX(4, 4, 2, 4);
+                }
+                // bfloat16 error images: EXF = 5 / 6, the same tiles and the same two layouts
+                if (opts.err_elem == K2_ELEM_BF16) {
+                    if (opts.f16_store == 0) return F.P <= 16384 ? DSAC_EX(4, 1, 3, 5) : DSAC_EX(4, 4, 2, 5);
+                    return F.P <= 16384 ? DSAC_EX(4, 1, 3, 6) : DSAC_EX(4, 4, 2, 6);
                 }
                 if (F.P <= 16384) return DSAC_EX(4, 1, 3, 2);
                 return DSAC_EX(4, 4, 2, 2);

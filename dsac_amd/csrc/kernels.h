@@ -47,11 +47,11 @@ struct K2Opts {
     const void* split = nullptr;      // per call: the split fp16 records (pose_prep_split), for flags bit 28
     const double* poses64 = nullptr;  // per call: the cv poses (N x 6 doubles) the staged records were made from -- the precise form (flags bit 25) works from these
     int* report = nullptr;            // per call: int[2] that receives the arithmetic form of the launch (K2_FORM_*) and why it is not the exact one (K2_WHY_*)
-    int err_elem = 0;                 // per call: element type of `err` (K2_ELEM_*); K2_ELEM_F16: `err` points to N x P IEEE binary16 (the exact vector build only, P % 8 == 0)
-    int f16_store = 1;                // "k2_f16_store": store layout of the half build: 0 = four 8-byte stores per lane and chunk, 1 (default: 882 against 892 us at the
+    int err_elem = 0;                 // per call: element type of `err` (K2_ELEM_*); K2_ELEM_F16 / K2_ELEM_BF16: `err` points to N x P IEEE binary16 / bfloat16 (the exact vector build only, P % 8 == 0)
+    int f16_store = 1;                // "k2_f16_store": store layout of both 16-bit builds (binary16 and bfloat16): 0 = four 8-byte stores per lane and chunk, 1 (default: 882 against 892 us at the
                                       // bench shape, profiles/k2_f16_ab.txt) = two 16-byte stores after a lane exchange
 };
-enum { K2_ELEM_F32 = 0, K2_ELEM_F16 = 1 };
+enum { K2_ELEM_F32 = 0, K2_ELEM_F16 = 1, K2_ELEM_BF16 = 2 };
 constexpr int K2_FLAG_RECLO = 1 << 27;    // k2_flags: pose records in two pieces -- the low parts through fp16 matrix-core instructions chained onto the fp32 ones
 constexpr int K2_FLAG_STORE_ONLY = 1 << 1;  // k2_flags: store schedule only (measurement)
 constexpr int K2_FLAG_EXACT = 1 << 28;    // k2_flags: exact transform -- split fp16 records through the fp16 matrix core, the camera-frame point rounded to float once (round 6)
@@ -134,9 +134,12 @@ struct K4Plan {
     bool fused = false;   // round 4: no backward_prep launch -- the main pass derives its records from the poses, the finish kernel dR/drod; G12_part [hyp][row][12]
     bool direct = false;  // ... and (one hypothesis tile) the main pass adds its gradient straight into grad_xyz: no grad_part, no gradient reduction launch
     int Nf = 0;           // frame batch: hypotheses per frame (= HT), 0 = one frame
-    int elem = 0;         // element type of d_err (K4_ELEM_*); K4_ELEM_F16: N x P IEEE binary16, the matrix-core form only (variant > 0, not the soft mode)
+    int elem = 0;         // element type of d_err (K4_ELEM_*); K4_ELEM_F16 / K4_ELEM_BF16: N x P IEEE binary16 / bfloat16, the matrix-core form only (variant > 0, not the soft mode)
 };
-enum { K4_ELEM_F32 = 0, K4_ELEM_F16 = 1 };
+enum { K4_ELEM_F32 = 0, K4_ELEM_F16 = 1, K4_ELEM_BF16 = 2 };
+// the bfloat16 build of the matrix-core form exists where it needs no scratch: forms 1, 2 and 5 (2, 4 and 3 chunks at two waves per SIMD -- what the auto plan
+// picks, and the 3-chunk knob).  The 5- and 6-chunk forms (3, 4) and the high-occupancy forms (6, 7) spill in every element type and are not built in bfloat16
+inline bool k4_form_has_bf16(int form) { return form == 1 || form == 2 || form == 5; }
 // Nf > 0 (frame batch): N = frames x Nf hypotheses, one hypothesis tile per frame (Nf a multiple of 16, <= 256), gradient per frame (grad_xyz frames x P x 3);
 // plan.variant == 0 then means: not available for a batch
 // elem: what d_err points to (K4_ELEM_*).  The half plan is the float plan -- same variant, tiles, rows, fused / direct -- with d_err on an 8-byte address
@@ -145,7 +148,7 @@ K4Plan backward_plan(int N, const FrameDev& F, const void* d_err, int variant, i
 bool backward_variant_known(int variant);  // -1 (auto), 0 .. 5, or a form + 10 * tile code + 100 * workgroups per CU (see backward_plan)
 constexpr int BWD_DRDH = 54;  // per hypothesis: dR/drod (27) and Omega_i = (dR/drod_i) R^T (27)
 hipError_t backward_prep(hipStream_t st, int N, const double* poses, const FrameDev& F, float* staged_bwd, double* dRdH /*N x BWD_DRDH*/);
-// K4 main pass.  d_err (N x P floats, or halves with plan.elem == K4_ELEM_F16) or nullptr with g (N doubles) for the soft-inlier score.
+// K4 main pass.  d_err (N x P floats, or 16-bit elements with plan.elem == K4_ELEM_F16 / K4_ELEM_BF16) or nullptr with g (N doubles) for the soft-inlier score.
 //   grad_part : [hyp_tiles][P*3] floats       G12_part : [partial rows][N][12] floats
 // poses (cv, N x 6) / grad_xyz (P x 3 fp64, accumulated into) / flags: used when plan.fused / plan.direct (staged_bwd and grad_part may then be nullptr)
 hipError_t score_backward(hipStream_t st, int N, const float* staged_bwd, const FrameDev& F, const void* d_err, const double* g,

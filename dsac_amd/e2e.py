@@ -240,7 +240,8 @@ class ScoredFrameBatch:
 
     err_dtype=torch.float16: K2 writes the error images in half precision (dsac_process_images_begin_f16: half the bytes) and the score model runs on
     them under torch.autocast; its gradient images stay in half precision and go to K4 as they are (dsac_score_backward_f16: no conversion pass, the float
-    call's result on the same values).  Default float32."""
+    call's result on the same values).  err_dtype=torch.bfloat16: the same seam in bfloat16 (dsac_process_images_begin_bf16, autocast in bfloat16,
+    dsac_score_backward_bf16) -- float's exponent range, so the small gradient images neither underflow nor need a gradient scaler.  Default float32."""
 
     def __init__(self, device=0, frames=8, hyps=256, ref_steps=8, inlier_count=100, thr=10.0, sub_sample=0.01, cam=(525.0, 525.0, 320.0, 240.0), score_net=None,
                  H=CNN_OBJ_PATCHSIZE, W=CNN_OBJ_PATCHSIZE, engine=None, err_dtype=torch.float32):
@@ -267,7 +268,8 @@ class ScoredFrameBatch:
         eng.set_frames(xyz, uv, self.H, self.W, self.cam, uv_per_frame=uv_per_frame, borrow=True)
         eng.processImagesBegin(N, self.err, seed=seed, thr=self.thr, out=(self.poses, self.sets, self.ok))
         self._err_in = self.err.detach().requires_grad_(True)  # same storage: the score CNN reads what K2 wrote
-        with torch.autocast("cuda", dtype=torch.float16, enabled=self.err_dtype == torch.float16):
+        half = self.err_dtype in (torch.float16, torch.bfloat16)
+        with torch.autocast("cuda", dtype=self.err_dtype if half else torch.float16, enabled=half):
             self._scores = self.score_net(self._err_in)
         self.scores = self._scores.detach().double().contiguous()
         eng.processImagesFinish(N, self.scores, perm, self.poses, gt_jp6=gt_jp6, scale=1.0, thr=self.thr, max_inl=self.inlier_count, out=self.res)
@@ -285,7 +287,7 @@ class ScoredFrameBatch:
                                            int(perm.shape[0]), int(self.inlier_count), 50, float(int(self.thr)), ptr(r["inlierMaps"]), float(self.sub_sample), 0.001, 2.0, 1.0,
                                            ptr(self.dpnp), ptr(self.grad_xyz), ptr(self.g), None, None))
         self._scores.backward(gradient=self.g.to(self._scores.dtype).clamp_(-CLAMP_E2E, CLAMP_E2E))
-        d = self._err_in.grad.reshape(F * N, H, W)  # float32, or float16 from a half-precision model: K4 reads either (Engine.dScore picks the call)
+        d = self._err_in.grad.reshape(F * N, H, W)  # float32, or float16 / bfloat16 from such a model: K4 reads each as it is (Engine.dScore picks the call)
         # reference-exact seam: gradient images read back transposed (lua_calls.h:329-335) together with dScore's x*cols*3 + y*3 columns -- both or neither
         d_err = (d.transpose(1, 2) if quirk_transpose else d).reshape(F * N, P).contiguous()
         eng.dScore(self.poses, self.sets, d_err, dpnp=self.dpnp, quirk_transpose=quirk_transpose, grad=self.grad_xyz)

@@ -38,6 +38,29 @@ def _is_f16(a):
     return str(getattr(a, "dtype", "")) in ("float16", "torch.float16")
 
 
+_INT16 = ("uint16", "int16", "torch.uint16", "torch.int16")
+
+
+def _seam_elem(a, elem=None, what="err"):
+    """Element type of an image array at the score-model seam: "f32", "f16" or "bf16".  Arrays and tensors with a floating dtype decide by it (float32,
+    float16, torch.bfloat16); elem may repeat that type and must not contradict it.  numpy has no bfloat16: a 16-bit integer array holds bit patterns of the
+    type elem names ("bf16", or "f16"), and without the keyword such an array is refused, never guessed.  A raw address or None is floats unless elem says
+    otherwise."""
+    dt = str(getattr(a, "dtype", ""))
+    if elem not in (None, "f32", "f16", "bf16"):
+        raise ValueError("dsac_amd: elem is None (decide by the dtype of %s), \"f32\", \"f16\" or \"bf16\", got %r" % (what, elem))
+    if a is None or isinstance(a, int):
+        return elem or "f32"
+    if dt in _INT16:
+        if elem in ("f16", "bf16"):
+            return elem
+        raise ValueError("dsac_amd: %s is %s: say elem=\"bf16\" (or \"f16\") for the type whose bit patterns it holds" % (what, dt))
+    own = "bf16" if dt == "torch.bfloat16" else "f16" if _is_f16(a) else "f32"
+    if elem is not None and elem != own:
+        raise ValueError("dsac_amd: elem=%r contradicts the dtype of %s (%s)" % (elem, what, dt))
+    return own
+
+
 class Engine:
     """One DSAC engine context = one GPU stream.  Not thread-safe (one per host thread)."""
 
@@ -219,17 +242,18 @@ class Engine:
 
     # ---- the score-CNN seam of the batched fast path (dsac_process_images_begin / _finish) ---------------------------------------------
     def processImagesBegin(self, hyps_per_frame, err, seed=1305, thr=10.0, max_tries=1 << 20, clamp=CNN_OBJ_MAXINPUT, tau=10.0, beta=0.5, soft=None, out=None,
-                           refstream=None):
+                           refstream=None, elem=None):
         """First half of processImage for every frame set with set_frame / set_frames (cnn_softam.h:1010-1069): K1 sample + P3P, K2 -> the F*N error
         images in `err` (F*N x H*W float32, where the reference's score CNN reads them: lua_calls.h:98-104); soft (F*N float64, optional) receives the
         soft-inlier sums as well.  out = (poses F*N x 6, sets F*N x 4, ok F*N) preallocated or None; returns it.  refstream: as processImages.
-        A float16 `err` (numpy or torch) takes dsac_process_images_begin_f16: the same values rounded to half, everything else bit for bit."""
+        A float16 `err` (numpy or torch) takes dsac_process_images_begin_f16: the same values rounded to half, everything else bit for bit.  A torch.bfloat16
+        `err` takes dsac_process_images_begin_bf16; a numpy uint16 array or a raw address does with elem="bf16" (numpy has no bfloat16) and is refused without."""
         F, N = getattr(self, "frames", 1), int(hyps_per_frame)
         if out is None:
             out = (np.zeros((F * N, 6)), np.zeros((F * N, 4), np.int32), np.zeros(F * N, np.uint8))
         poses, sets_out, ok = out
         self._pi_refstream(refstream)
-        begin = lib.dsac_process_images_begin_f16 if _is_f16(err) else lib.dsac_process_images_begin
+        begin = {"f32": lib.dsac_process_images_begin, "f16": lib.dsac_process_images_begin_f16, "bf16": lib.dsac_process_images_begin_bf16}[_seam_elem(err, elem)]
         check(self._ctx, begin(self._ctx, N, int(seed) & 0xFFFFFFFFFFFFFFFF, float(thr), int(max_tries), float(clamp), float(tau), float(beta),
                        ptr(poses), ptr(sets_out), ptr(ok), ptr(err), ptr(soft)))
         return out
@@ -272,7 +296,8 @@ class Engine:
         lua_calls.h:89-105).  score_fn runs on the engine's stream when the engine was made on torch's current stream (Engine(stream=...)); its result
         may be any floating torch tensor on the device.  perm / gt_jp6: device tensors or host arrays (host arrays are uploaded).  Returns the dict of
         processImages with torch device tensors (plus "diffMaps").  refstream: as processImages.  err_dtype=torch.float16: the error images are
-        allocated, written by K2 and handed to score_fn in half precision (a given `err` decides by its own dtype); default float32."""
+        allocated, written by K2 and handed to score_fn in half precision (a given `err` decides by its own dtype); default float32;
+        torch.bfloat16 likewise (dsac_process_images_begin_bf16)."""
         import torch
         F, N = getattr(self, "frames", 1), int(hyps_per_frame)
         dev = torch.device("cuda", self.device)
@@ -388,13 +413,16 @@ class Engine:
         self.set_option("pi_refstream", 1 if refstream else 0)
 
     # ---- K2 ---------------------------------------------------------------------------------------
-    def reproject(self, poses, N=None, clamp=CNN_OBJ_MAXINPUT, err=None, soft=None, tau=10.0, beta=0.5):
+    def reproject(self, poses, N=None, clamp=CNN_OBJ_MAXINPUT, err=None, soft=None, tau=10.0, beta=0.5, elem=None):
         """err[h] = getDiffMap(pose_h) (cnn_softam.h:319-362) and/or soft[h] = sum_p sigmoid(beta*(tau - err)).  A float16 `err` (numpy or torch) takes
-        dsac_reproject_f16: the float call's values rounded to half, soft bit for bit; a float32 `err` is the float call."""
+        dsac_reproject_f16: the float call's values rounded to half, soft bit for bit; a float32 `err` is the float call.  A torch.bfloat16 `err` takes
+        dsac_reproject_bf16 (rounded to bfloat16); a numpy uint16 array or a raw address does with elem="bf16" and is refused without the keyword.  elem: None
+        (by the dtype of `err`), or "f32" / "f16" / "bf16" -- it names the type of a 16-bit integer array or a raw address and may repeat, never contradict, a
+        floating dtype; the same holds for processImagesBegin, dScore and softScoreDErr."""
         poses = _np(poses, np.float64)
         if N is None:
             N = int(poses.shape[0])
-        reproject = lib.dsac_reproject_f16 if _is_f16(err) else lib.dsac_reproject
+        reproject = {"f32": lib.dsac_reproject, "f16": lib.dsac_reproject_f16, "bf16": lib.dsac_reproject_bf16}[_seam_elem(err, elem)]
         check(self._ctx, reproject(self._ctx, int(N), ptr(poses), float(clamp), ptr(err), float(tau), float(beta), ptr(soft)))
         return err, soft
 
@@ -459,17 +487,19 @@ class Engine:
         return J
 
     # ---- K4 ---------------------------------------------------------------------------------------
-    def dScore(self, poses, sets, d_err, dpnp=None, quirk_transpose=False, grad=None, parity_fp64=False, quirk_rot_writeback=False):
+    def dScore(self, poses, sets, d_err, dpnp=None, quirk_transpose=False, grad=None, parity_fp64=False, quirk_rot_writeback=False, elem=None):
         """dScore part (iii) (cnn_softam.h:609-645) summed over hypotheses (train_ransac_softam.cpp:382-383).
         grad (H*W x 3 float64) is accumulated into and returned.  parity_fp64: the fp64 parity mode (the reference's evaluation order, one lane
         per hypothesis; reference-sized maps), quirk_rot_writeback: with it, quirk 7 (cnn_softam.h:506-508).
         A float16 `d_err` (numpy or torch) takes dsac_score_backward_f16: K4 reads the halves as they are (no converted copy) and returns the float call's
-        result on the widened values; the fp64 parity mode does not read halves.  Everything else is the float call."""
+        result on the widened values; the fp64 parity mode does not read halves.  A torch.bfloat16 `d_err` takes dsac_score_backward_bf16 on the
+        same terms; a numpy uint16 array or a raw address does with elem="bf16" and is refused without the keyword.  Everything else is the float call."""
         poses = _np(poses, np.float64)
         sets = _np(sets, np.int32)
-        half = _is_f16(d_err)
+        et = _seam_elem(d_err, elem, "d_err")
+        half = et != "f32"  # either 16-bit type: the array goes to K4 as it is
         if half and (parity_fp64 or quirk_rot_writeback):
-            raise ValueError("dsac_amd: parity_fp64 / quirk_rot_writeback read float32 gradient images, d_err is float16")
+            raise ValueError("dsac_amd: parity_fp64 / quirk_rot_writeback read float32 gradient images, d_err is %s" % ("float16" if et == "f16" else "bfloat16"))
         if not half:
             d_err = _np(d_err, np.float32)
         N = int(sets.shape[0])
@@ -477,16 +507,18 @@ class Engine:
             grad = np.zeros((getattr(self, "frames", 1) * self.P, 3))  # frame batch: one P x 3 gradient per frame
         flags = (capi.DSAC_BWD_QUIRK_TRANSPOSE if quirk_transpose else 0) | (capi.DSAC_BWD_PARITY_FP64 if (parity_fp64 or quirk_rot_writeback) else 0) | \
                 (capi.DSAC_BWD_QUIRK_ROT_WRITEBACK if quirk_rot_writeback else 0)
-        backward = lib.dsac_score_backward_f16 if half else lib.dsac_score_backward
+        backward = {"f32": lib.dsac_score_backward, "f16": lib.dsac_score_backward_f16, "bf16": lib.dsac_score_backward_bf16}[et]
         check(self._ctx, backward(self._ctx, N, ptr(poses), ptr(sets), ptr(d_err), ptr(_np(dpnp, np.float64) if dpnp is not None else None), flags, ptr(grad)))
         return grad
 
-    def softScoreDErr(self, g, err, d_err, tau=10.0, beta=0.5, clamp=CNN_OBJ_MAXINPUT):
+    def softScoreDErr(self, g, err, d_err, tau=10.0, beta=0.5, clamp=CNN_OBJ_MAXINPUT, elem=None):
         """The soft-inlier score's gradient images (dsac_soft_score_derr): d_err[h] = g[h] * d soft[h] / d err[h], 0 where err sits on the clamp.  err and
-        d_err are N x H*W of one dtype, float32 or float16 (numpy or torch): halves take dsac_soft_score_derr_f16 (fp32 arithmetic, rounded on the store)."""
-        if _is_f16(err) != _is_f16(d_err):
+        d_err are N x H*W of one dtype, float32 or float16 (numpy or torch): halves take dsac_soft_score_derr_f16 (fp32 arithmetic, rounded on the store).
+        torch.bfloat16 tensors take dsac_soft_score_derr_bf16; numpy uint16 arrays or raw addresses do with elem="bf16", which then speaks for both images."""
+        et = _seam_elem(err, elem)
+        if et != _seam_elem(d_err, elem, "d_err"):
             raise ValueError("dsac_amd: err and d_err must have the same dtype")
-        derr = lib.dsac_soft_score_derr_f16 if _is_f16(err) else lib.dsac_soft_score_derr
+        derr = {"f32": lib.dsac_soft_score_derr, "f16": lib.dsac_soft_score_derr_f16, "bf16": lib.dsac_soft_score_derr_bf16}[et]
         g = _np(g, np.float64)
         check(self._ctx, derr(self._ctx, int(g.shape[0]), ptr(g), ptr(err), float(clamp), float(tau), float(beta), ptr(d_err)))
         return d_err

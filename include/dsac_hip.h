@@ -324,12 +324,25 @@ DSAC_API int dsac_reproject(dsac_ctx* ctx, int N, const double* poses, float cla
  *   no "k2_flags" bit other than 28 / 29 is set;  "k2_exact_auto" is 1 or bit 28 / 29 is set.
  * After a successful call "k2_form_last" is DSAC_K2_FORM_EXACT_VEC and "k2_form_why_last" 0.  Chunks with far coordinates take the in-kernel fp32 path as in
  * the float build; their values too are the float build's, rounded.
- *   "k2_f16_store" (dsac_set_option)  the store layout of the half build: 0 = four 8-byte stores per lane and 64-cell chunk, 1 (default) = neighbouring lanes trade
+ *   "k2_f16_store" (dsac_set_option)  the store layout of both 16-bit builds (binary16 and bfloat16, dsac_reproject_bf16): 0 = four 8-byte stores per lane and 64-cell chunk, 1 (default) = neighbouring lanes trade
  *                 rows so that each issues two 16-byte stores of 8 cells (A/B: scripts/k2_f16_ab.py, profiles/k2_f16_ab.txt); the values do not depend on it.
  * The backward half of the seam in half precision is dsac_score_backward_f16 (K4 reads a half-precision score model's gradient images as they are).
  * Not part of this: the any-map build and the fp32 / precise / two-piece forms in half; dsac_score_hypotheses*, dsac_process_images and the pipelined pair
- * in half; bf16. */
+ * in half.  (bfloat16: dsac_reproject_bf16 below.) */
 DSAC_API int dsac_reproject_f16(dsac_ctx* ctx, int N, const double* poses, float clamp, uint16_t* err16, float tau, float beta, double* soft_or_null);
+/* The same call with the error images in BFLOAT16, the type a PyTorch model on this hardware trains in: err16 [N][H*W] bfloat16 bit patterns (the upper 16
+ * bits of a float) carried as uint16_t, a host or a device pointer, non-NULL.  Each stored value is the float the float call would have stored, rounded to
+ * bfloat16 to nearest even (v_cvt_pk_bf16_f32) -- at most 0.25 px of rounding at the 100 px clamp, 0.031 px near a 10 px threshold, what a bf16 model's first
+ * layer does anyway.  soft is the float call's bit for bit (the sigmoid is taken before the rounding); frame batches, the K2 gate events and the profile
+ * hooks apply as they do to dsac_reproject_f16, and K2 stores the same bytes as the half build: only the packing of two floats into a dword differs.
+ * Every condition and refusal of dsac_reproject_f16 carries over unchanged (DSAC_ERR_INVALID, nothing launched, "k2_form_last" keeps its value,
+ * dsac_last_error names this call and the condition); after a successful call "k2_form_last" is DSAC_K2_FORM_EXACT_VEC.  "k2_f16_store" selects the store
+ * layout here as well, with one exception: on a map of up to 16 384 cells on the implicit pixel grid with W % 64 != 0, error images alone take the 16-byte layout
+ * and err + soft the 8-byte layout whatever the option says -- the other build of either would need 12 bytes of scratch per lane; the values do not depend on it.  The backward twin is dsac_score_backward_bf16; bfloat16 keeps float's exponent range, so the gradient images on the way back -- far below
+ * binary16's smallest normal -- neither underflow nor need a gradient scaler.
+ * Not part of this: the any-map build and the fp32 / precise / two-piece forms in bfloat16; dsac_score_hypotheses*, dsac_process_images and the pipelined
+ * pair in bfloat16; the C++ host shim (dsac_amd/host: its ScoreModel takes const float* and has no binary16 either). */
+DSAC_API int dsac_reproject_bf16(dsac_ctx* ctx, int N, const double* poses, float clamp, uint16_t* err16, float tau, float beta, double* soft_or_null);
 
 /* ---- K3: softmax / entropy / soft-argmax pose --------------------------------------------------- */
 /* Replaces softMax core/cnn_softam.h:535-553, entropy :80-88 and the weighted pose average :1082-1094.
@@ -402,9 +415,21 @@ DSAC_API int dsac_score_backward(dsac_ctx* ctx, int N, const double* poses, cons
  *   d_err16 is NULL or off an 8-byte address;  DSAC_BWD_PARITY_FP64 (and with it DSAC_BWD_QUIRK_ROT_WRITEBACK) is set;  H*W % 4 != 0;  a frame's xyz or uv
  *   is off a 16-byte address;  the implicit pixel grid has W % 4 != 0;  "k4_variant" names the VALU form (0, 1000, or either plus a multiple of 10);
  * and wherever dsac_score_backward refuses (fx != fy, ...).  Nothing takes another form silently.
- * Not part of this: the VALU and fp64 parity forms in half; bf16. */
+ * Not part of this: the VALU and fp64 parity forms in half.  (bfloat16: dsac_score_backward_bf16 below.) */
 DSAC_API int dsac_score_backward_f16(dsac_ctx* ctx, int N, const double* poses, const int32_t* sets, const uint16_t* d_err16, const double* dpnp_or_null,
                             unsigned flags, double* grad_xyz);
+/* The same call on BFLOAT16 gradient images, the backward twin of dsac_reproject_bf16: d_err16 [N][H*W] bfloat16 bit patterns carried as uint16_t, a host or a
+ * device pointer (host arrays are staged at 2 bytes per element), non-NULL.  The matrix-core form loads a lane's four cells as 8 bytes and widens them in
+ * registers by one shift or mask each -- exact for every pattern -- on the launch plan the float call would take: the result is the float call's on the widened
+ * values, with grad_xyz zeroed beforehand bit for bit (on other contents within the last bit of a cell), dsac_last_pose_gradients bit for bit.  Unlike
+ * binary16, bfloat16 holds gradient values of 1e-8 and below (g[h] (-beta) s (1 - s) with a small g): nothing underflows, nothing needs scaling.
+ * The refusals are dsac_score_backward_f16's, condition by condition (8-byte address, DSAC_BWD_PARITY_FP64 / DSAC_BWD_QUIRK_ROT_WRITEBACK, H*W % 4, 16-byte xyz
+ * and uv, implicit grid with W % 4, a VALU "k4_variant"): DSAC_ERR_INVALID, nothing staged or enqueued, dsac_last_error names this call.  One more:
+ * a "k4_variant" whose form is 3, 4 (5 or 6 chunks), 6 or 7 (the high-occupancy builds) -- experiment knobs whose builds need scratch in every element type --
+ * is refused in the same way; bfloat16 is built for forms 1, 2 (what the automatic plan picks) and 5, none of which needs scratch.
+ * Not part of this: the VALU and fp64 parity forms in bfloat16. */
+DSAC_API int dsac_score_backward_bf16(dsac_ctx* ctx, int N, const double* poses, const int32_t* sets, const uint16_t* d_err16, const double* dpnp_or_null,
+                             unsigned flags, double* grad_xyz);
 /* The backward calls need fx == fy: the reference's Jacobians use the single focal length camMat(0,0) for both axes
  * (core/cnn_softam.h:406,466); a camera with two focal lengths is rejected with DSAC_ERR_INVALID rather than differentiated
  * inconsistently with the forward kernels.  Quirk 7 of the reference (dProjectdHyp writes the re-derived rotation back into the
@@ -428,8 +453,12 @@ DSAC_API int dsac_soft_score_derr(dsac_ctx* ctx, int N, const double* g, const f
  * err16 / d_err16 N x H*W IEEE binary16 on 8-byte addresses, 4 | H*W (else DSAC_ERR_INVALID, before anything is staged).  The input is widened to float,
  * the arithmetic is dsac_soft_score_derr's in fp32, the result is rounded to nearest even on the store (small gradients land in the half subnormals). */
 DSAC_API int dsac_soft_score_derr_f16(dsac_ctx* ctx, int N, const double* g, const uint16_t* err16, float clamp, float tau, float beta, uint16_t* d_err16);
+/* The same on bfloat16 images (dsac_process_images_begin_bf16 -> this -> dsac_score_backward_bf16): err16 / d_err16 N x H*W bfloat16 bit patterns on 8-byte
+ * addresses, 4 | H*W (else DSAC_ERR_INVALID, before anything is staged).  The input is widened to float, the arithmetic is dsac_soft_score_derr's in fp32, the
+ * result is rounded ONCE, to nearest even, on the store; a gradient of 1e-10 keeps its value to 2^-9 relative where the half call returns 0. */
+DSAC_API int dsac_soft_score_derr_bf16(dsac_ctx* ctx, int N, const double* g, const uint16_t* err16, float clamp, float tau, float beta, uint16_t* d_err16);
 
-/* The per-hypothesis 1 x 6 pose gradients of the most recent dsac_score_backward / dsac_score_backward_f16 / dsac_soft_score_backward call on
+/* The per-hypothesis 1 x 6 pose gradients of the most recent dsac_score_backward / dsac_score_backward_f16 / dsac_score_backward_bf16 / dsac_soft_score_backward call on
  * this context: G6[h] = sum over cells of d_err[h][p] * dProjectdHyp(p) (the accumulation of core/cnn_softam.h:631-632
  * before its product with dPNP; columns = jp Rodrigues vector, translation in mm).  N must not exceed that call's N. */
 DSAC_API int dsac_last_pose_gradients(dsac_ctx* ctx, int N, double* G6);
@@ -583,6 +612,12 @@ DSAC_API int dsac_process_images_finish(dsac_ctx* ctx, int hyps_per_frame, const
  * they are, no conversion pass in between. */
 DSAC_API int dsac_process_images_begin_f16(dsac_ctx* ctx, int hyps_per_frame, uint64_t seed, float thr, int max_tries, float clamp, float tau, float beta,
                                   double* poses, int32_t* sets_out, uint8_t* ok, uint16_t* err16, double* soft_or_null);
+/* dsac_process_images_begin with the error images in bfloat16: err16 [frames * hyps_per_frame][H*W] bfloat16 bit patterns, non-NULL, each value the float call's
+ * rounded to nearest even; poses, sets_out, ok and soft are the float call's bit for bit, "pi_refstream", "pi_defer_tail" and "seed_stride" apply as they do
+ * there, and dsac_process_images_finish follows it unchanged.  The conditions, the refusal (checked before K1 is enqueued) and "k2_f16_store" are those of
+ * dsac_reproject_bf16.  The backward half is dsac_score_backward_bf16. */
+DSAC_API int dsac_process_images_begin_bf16(dsac_ctx* ctx, int hyps_per_frame, uint64_t seed, float thr, int max_tries, float clamp, float tau, float beta,
+                                   double* poses, int32_t* sets_out, uint8_t* ok, uint16_t* err16, double* soft_or_null);
 /* The same dependency for ANOTHER stream: `hip_stream` (a hipStream_t of the context's device) waits for the deferred tail that is in flight -- and
  * thereby for the dsac_process_images call it belongs to and everything the context's stream held before that call (the tail starts behind that call's
  * K3); the context's own stream is not held up, nothing is inserted into it, and the tail stays pending for it.  This is how a consumer of the tail's
