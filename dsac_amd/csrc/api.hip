@@ -56,6 +56,10 @@ struct dsac_ctx {
     bool have_frame = false;
     dk::FrameDev F{};
     DevBuf frame_xyz, frame_uv;
+    // one camera per frame (dsac_set_frames_cams): the host copy (frames x fx, fy, cx, cy: form decisions, the fx == fy check, the frame-by-frame paths) and the
+    // device table the kernels read; F.cams_h / F.cams point at them while the current frames carry per-frame cameras, else both are NULL
+    std::vector<float> cams_h;
+    DevBuf cams_d;
 
     // scratch, one buffer per role so that calls can be chained without aliasing
     DevBuf rs_states, rs_scratch, rs_small, k6_scratch;  // the reference's random streams (dsac_refstream_init) and the scratch of a sampling window
@@ -282,11 +286,11 @@ int k2_stage(dsac_ctx* c, hipStream_t st, int N, int Nf, const float* staged, co
     const bool lo = poses && (c->k2.flags & dk::K2_FLAG_RECLO);                            // "k2_flags" bit 27: the low parts of the staged records
     if (split) {
         HIP_TRY(c, c->staged_split.reserve(dk::pose_split_bytes(N)));
-        HIP_TRY(c, dk::pose_prep_split(st, N, poses, F, c->staged_split.as<char>()));
+        HIP_TRY(c, dk::pose_prep_split(st, N, poses, F, c->staged_split.as<char>(), Nf));
     }
     if (lo) {
         HIP_TRY(c, c->staged_lo.reserve((size_t)N * dk::POSE_STRIDE * sizeof(float)));
-        HIP_TRY(c, dk::pose_prep_lo(st, N, poses, F, c->staged_lo.as<float>()));
+        HIP_TRY(c, dk::pose_prep_lo(st, N, poses, F, c->staged_lo.as<float>(), Nf));
     }
     ProfScope ps(c, 0, true);
     dk::K2Opts o = c->k2;
@@ -397,6 +401,45 @@ int k2_soft_part(dsac_ctx* c, int N, bool want_err, bool want_soft, float* tau, 
     return DSAC_OK;
 }
 
+// K2 on frames with one camera each (dsac_set_frames_cams) is the exact-transform form and nothing else: what the auto policy launches, on the vector or the
+// any-map build.  Every scoring call asks here before it enqueues anything -- K1 included -- and is refused by name, "k2_form_last" keeps its value.  No-op
+// for the shared camera.
+int k2_cams_check(dsac_ctx* c, const char* who) {
+    const dk::FrameDev& F = c->F;
+    if (!F.cams) return DSAC_OK;
+    for (int f = 0; f < (F.frames > 1 ? F.frames : 1); f++)
+        if (std::max(F.cams_h[4 * f], F.cams_h[4 * f + 1]) > 1024.f)
+            return fail(c, DSAC_ERR_INVALID, "%s: per-frame cameras need every focal length <= 1024 px (the exact-transform form), frame %d has fx = %g, fy = %g", who, f,
+                        (double)F.cams_h[4 * f], (double)F.cams_h[4 * f + 1]);
+    if (c->k2.variant != -1) return fail(c, DSAC_ERR_INVALID, "%s: per-frame cameras need k2_variant -1 (the auto policy's exact-transform form), it is %d", who, c->k2.variant);
+    const int ex_bits = dk::K2_FLAG_EXACT | dk::K2_FLAG_EXACT_ANY;
+    if (c->k2.flags & ~ex_bits)
+        return fail(c, DSAC_ERR_INVALID, "%s: per-frame cameras exist for the exact-transform form only: k2_flags 0x%x sets bits other than 28 / 29", who, c->k2.flags);
+    if (!c->k2.exact_auto && !(c->k2.flags & ex_bits))
+        return fail(c, DSAC_ERR_INVALID, "%s: per-frame cameras need the exact-transform form: k2_exact_auto is 0 and neither k2_flags bit 28 nor 29 is set", who);
+    return DSAC_OK;
+}
+// The backward calls use one focal length for both axes (dProjectdObj / dProjectdHyp, core/cnn_softam.h:406,466): with per-frame cameras that holds row by row
+int cams_fxfy_check(dsac_ctx* c, const char* who) {
+    const dk::FrameDev& F = c->F;
+    if (!F.cams) return DSAC_OK;
+    for (int f = 0; f < (F.frames > 1 ? F.frames : 1); f++)
+        if (F.cams_h[4 * f] != F.cams_h[4 * f + 1])
+            return fail(c, DSAC_ERR_INVALID, "%s: needs fx == fy in every frame's camera, frame %d has %g, %g: dProjectdObj / dProjectdHyp use a single focal length", who, f,
+                        (double)F.cams_h[4 * f], (double)F.cams_h[4 * f + 1]);
+    return DSAC_OK;
+}
+// frame f of the current batch as a single frame: its maps, its camera
+dk::FrameDev frame_view(const dk::FrameDev& F, int f) {
+    dk::FrameDev Fd = F;
+    Fd.frames = 1;
+    Fd.xyz = F.xyz + (size_t)f * F.xyz_stride;
+    if (Fd.uv) Fd.uv = F.uv + (size_t)f * F.uv_stride;
+    Fd.xyz_stride = Fd.uv_stride = 0;
+    dk::frame_cam(Fd, f);
+    return Fd;
+}
+
 // 16-bit error images (dsac_reproject_f16 / _bf16, dsac_process_images_begin_f16 / _bf16) exist for the default arithmetic only: the exact-transform vector build.
 // Every condition is checked here, before the call enqueues anything, and refused by name -- never a silent launch of another form, and "k2_form_last" keeps its
 // value.  The conditions are the same for both element types; `elem` only picks the word the message uses beside the call's name.
@@ -484,6 +527,13 @@ __global__ __launch_bounds__(256) void k_gather_rows(V* __restrict__ dst, const 
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < vecs; i += (size_t)gridDim.x * blockDim.x) d[i] = s[i];
 }
 
+// The camera table of dsac_set_frames_cams reaches the device as a kernel argument, 64 rows per launch: the rows are captured when the launch is enqueued, so
+// the caller's array and the context's host copy may change right after, and nothing waits for the device
+struct CamRows { float4 r[64]; };
+__global__ __launch_bounds__(64) void k_store_cams(float4* __restrict__ dst, int n, CamRows rows) {
+    if ((int)threadIdx.x < n) dst[threadIdx.x] = rows.r[threadIdx.x];
+}
+
 __global__ void k_quantise_int16(float* xyz, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -555,7 +605,7 @@ void dsac_destroy(dsac_ctx* c) {
         if (c->tail[k]) (void)hipStreamSynchronize(c->tail[k]);
     if (c->aux) (void)hipStreamSynchronize(c->aux);
     if (c->aux2) (void)hipStreamSynchronize(c->aux2);
-    c->frame_xyz.release(); c->frame_uv.release();
+    c->frame_xyz.release(); c->frame_uv.release(); c->cams_d.release();
     c->staged.release(); c->staged_lo.release(); c->staged_split.release(); c->rs_states.release(); c->rs_scratch.release(); c->rs_small.release(); c->k6_scratch.release(); c->soft_part.release(); c->bwd_staged.release(); c->dRdH.release();
     c->grad_part.release(); c->g12_part.release(); c->g6.release();
     for (auto& s : c->slots) s.release();
@@ -623,8 +673,9 @@ int dsac_device_info(dsac_ctx* c, int* cus, int* clock_khz, uint64_t* mem_bytes,
     return DSAC_OK;
 }
 
+// cams: NULL = the shared camera fx .. cy (dsac_set_frame, dsac_set_frames); else the checked host rows of dsac_set_frames_cams (frames x 4), fx .. cy = row 0
 static int set_frames_common(dsac_ctx* c, int frames, const float* xyz, const float* uv, bool uv_per_frame, int H, int W, float fx, float fy, float cx,
-                             float cy, unsigned flags) {
+                             float cy, unsigned flags, const float* cams = nullptr) {
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_set_frame: ctx is NULL");
     if (!xyz || H <= 0 || W <= 0 || frames <= 0) return fail(c, DSAC_ERR_INVALID, "dsac_set_frame: need xyz, frames > 0 and H, W > 0 (got H=%d W=%d)", H, W);
     if ((long long)H * W * frames > (1ll << 30)) return fail(c, DSAC_ERR_INVALID, "dsac_set_frame: frames*H*W too large");
@@ -637,6 +688,8 @@ static int set_frames_common(dsac_ctx* c, int frames, const float* xyz, const fl
     if (!borrow && (c->slot_pending[0] || c->slot_pending[1]))
         return fail(c, DSAC_ERR_INVALID, "dsac_set_frame: a pipelined slot is sampled but not yet scored; the library's own frame copy cannot be replaced "
                                          "underneath it (use DSAC_FRAME_BORROW frames with the pipelined calls)");
+    // what the call will commit to c->F: nothing of the context's frame is touched before every step that can fail has succeeded
+    const float *new_xyz = nullptr, *new_uv = nullptr;
     if (borrow) {
         if (!is_device_ptr(xyz, c) || (uv && !is_device_ptr(uv, c))) return fail(c, DSAC_ERR_INVALID, "dsac_set_frame: DSAC_FRAME_BORROW needs device pointers");
         if (flags & DSAC_FRAME_QUANTISE_INT16) {  // the caller's own device buffer, rounded to the int16 grid in place (core/cnn_softam.h:265)
@@ -644,8 +697,8 @@ static int set_frames_common(dsac_ctx* c, int frames, const float* xyz, const fl
             hipLaunchKernelGGL(k_quantise_int16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, const_cast<float*>(xyz), n);
             HIP_TRY(c, hipGetLastError());
         }
-        c->F.xyz = xyz;
-        c->F.uv = uv;
+        new_xyz = xyz;
+        new_uv = uv;
     } else {
         join_tail(c);  // ... and so may a deferred refinement tail
         // K1 of an earlier pipelined slot (auxiliary stream) may still be reading the library's copy: order the overwrite behind it
@@ -653,13 +706,11 @@ static int set_frames_common(dsac_ctx* c, int frames, const float* xyz, const fl
             if (c->aux && c->slot_N[k] > 0) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->slot_ready[k], 0));
         HIP_TRY(c, c->frame_xyz.reserve(P * 3 * sizeof(float)));
         HIP_TRY(c, hipMemcpyAsync(c->frame_xyz.p, xyz, P * 3 * sizeof(float), hipMemcpyDefault, c->stream));
-        c->F.xyz = c->frame_xyz.as<float>();
+        new_xyz = c->frame_xyz.as<float>();
         if (uv) {
             HIP_TRY(c, c->frame_uv.reserve(Puv * 2 * sizeof(float)));
             HIP_TRY(c, hipMemcpyAsync(c->frame_uv.p, uv, Puv * 2 * sizeof(float), hipMemcpyDefault, c->stream));
-            c->F.uv = c->frame_uv.as<float>();
-        } else {
-            c->F.uv = nullptr;
+            new_uv = c->frame_uv.as<float>();
         }
         if (flags & DSAC_FRAME_QUANTISE_INT16) {
             const size_t n = P * 3;
@@ -669,6 +720,36 @@ static int set_frames_common(dsac_ctx* c, int frames, const float* xyz, const fl
         if (!is_device_ptr(xyz) || (uv && !is_device_ptr(uv))) HIP_TRY(c, hipStreamSynchronize(c->stream));  // host source may be freed after return
         if (c->frame_ready) HIP_TRY(c, hipEventRecord(c->frame_ready, c->stream));  // the auxiliary stream's K1 waits for the copy
     }
+    if (cams) {
+        // The table is library memory like the non-borrowed frame copy: work enqueued earlier -- a deferred refinement tail included -- may still read the
+        // previous rows, so the overwrite is ordered behind it, for a borrowed frame as well.  A table that has to grow is uploaded into a new buffer, which
+        // replaces the old one (hipFree waits for the device) only once the upload has been enqueued: a failed allocation or launch leaves the context as it was
+        join_tail(c);
+        const size_t bytes = (size_t)frames * sizeof(float4);
+        DevBuf grown;
+        if (bytes > c->cams_d.cap) HIP_TRY(c, grown.reserve(bytes));
+        float4* table = grown.p ? grown.as<float4>() : c->cams_d.as<float4>();
+        for (int f0 = 0; f0 < frames; f0 += 64) {
+            const int n = std::min(64, frames - f0);
+            CamRows rows;
+            for (int i = 0; i < 64; i++) {
+                const float* r = cams + 4 * (size_t)(f0 + std::min(i, n - 1));
+                rows.r[i] = make_float4(r[0], r[1], r[2], r[3]);
+            }
+            hipLaunchKernelGGL(k_store_cams, dim3(1), dim3(64), 0, c->stream, table + f0, n, rows);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) { grown.release(); return fail(c, DSAC_ERR_HIP, "dsac_set_frames_cams: the upload of the camera table failed: %s", hipGetErrorString(e)); }
+        }
+        if (grown.p) { c->cams_d.release(); c->cams_d = grown; }
+        c->cams_h.assign(cams, cams + (size_t)frames * 4);
+        c->F.cams = c->cams_d.as<float4>();
+        c->F.cams_h = c->cams_h.data();
+    } else {
+        c->F.cams = nullptr;
+        c->F.cams_h = nullptr;
+    }
+    c->F.xyz = new_xyz;
+    c->F.uv = new_uv;
     c->F.H = H; c->F.W = W; c->F.P = (int)P1;
     c->F.fx = fx; c->F.fy = fy; c->F.cx = cx; c->F.cy = cy;
     c->F.frames = frames;
@@ -772,6 +853,20 @@ int dsac_set_frame(dsac_ctx* c, const float* xyz, const float* uv, int H, int W,
 int dsac_set_frames(dsac_ctx* c, int frames, const float* xyz, const float* uv_or_null, int uv_per_frame, int H, int W, float fx, float fy, float cx,
                     float cy, unsigned flags) {
     return set_frames_common(c, frames, xyz, uv_or_null, uv_per_frame != 0, H, W, fx, fy, cx, cy, flags);
+}
+
+int dsac_set_frames_cams(dsac_ctx* c, int frames, const float* xyz, const float* uv_or_null, int uv_per_frame, int H, int W, const float* cams, unsigned flags) {
+    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_set_frames_cams: ctx is NULL");
+    if (frames <= 0) return fail(c, DSAC_ERR_INVALID, "dsac_set_frames_cams: frames must be > 0 (got %d)", frames);
+    if (!cams) return fail(c, DSAC_ERR_INVALID, "dsac_set_frames_cams: cams is NULL (frames x 4 floats on the host: fx, fy, cx, cy of every frame)");
+    // a host array, read before the call returns (the real query: \"device_args\" promises device pointers for the data arguments, not for this one)
+    if (is_device_ptr(cams)) return fail(c, DSAC_ERR_INVALID, "dsac_set_frames_cams: cams is a device pointer; the table is a host array (frames x 4 floats)");
+    for (int f = 0; f < frames; f++) {
+        const float fx = cams[4 * f], fy = cams[4 * f + 1];
+        if (!(fx != 0.f) || !(fy != 0.f) || !std::isfinite(fx) || !std::isfinite(fy))
+            return fail(c, DSAC_ERR_INVALID, "dsac_set_frames_cams: zero or non-finite focal length in row %d (fx = %g, fy = %g)", f, (double)fx, (double)fy);
+    }
+    return set_frames_common(c, frames, xyz, uv_or_null, uv_per_frame != 0, H, W, cams[0], cams[1], cams[2], cams[3], flags, cams);
 }
 
 int dsac_sample(dsac_ctx* c, int N, uint64_t seed, const int32_t* sets_or_null, float thr, int max_tries, double* poses, int32_t* sets_out,
@@ -932,6 +1027,7 @@ static int reproject_call(dsac_ctx* c, const char* who, int N, const double* pos
     if (c->F.frames > 1 && (N % c->F.frames != 0 || Nf % dk::K2_NF_MULTIPLE != 0))
         return fail(c, DSAC_ERR_INVALID, "%s: with a frame batch N must be frames x (a multiple of %d), got %d for %d frames", who, dk::K2_NF_MULTIPLE, N, c->F.frames);
     if (N < 0 || !poses) return fail(c, DSAC_ERR_INVALID, "%s: N >= 0 and poses must be non-NULL", who);
+    ARG_TRY(k2_cams_check(c, who));
     if (elem != dk::K2_ELEM_F32) ARG_TRY(k2_f16_check(c, who, elem, err_or_null));  // before anything is enqueued
     if (N == 0 || (!err_or_null && !soft_or_null)) return DSAC_OK;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -944,7 +1040,7 @@ static int reproject_call(dsac_ctx* c, const char* who, int N, const double* pos
     ARG_TRY(err_out_arg(c, err_or_null, elem, (size_t)N * P, &d_err));
     ARG_TRY(out_arg(c, soft_or_null, (size_t)N, &d_soft));
     HIP_TRY(c, c->staged.reserve((size_t)N * dk::POSE_STRIDE * sizeof(float)));
-    HIP_TRY(c, dk::pose_prep(c->stream, N, d_poses, c->F, c->staged.as<float>()));
+    HIP_TRY(c, dk::pose_prep(c->stream, N, d_poses, c->F, c->staged.as<float>(), Nf));
     float* d_part = nullptr;
     ARG_TRY(k2_soft_part(c, N, d_err != nullptr, d_soft != nullptr, &tau, &beta, &d_part));
     int used = 0;
@@ -1007,6 +1103,7 @@ static int score_hypotheses_common(dsac_ctx* c, int N, int Nf, uint64_t seed, co
     const int frames = Nf > 0 ? N / Nf : 1;
     if (!sets_or_null && max_tries <= 0) return fail(c, DSAC_ERR_INVALID, "dsac_score_hypotheses: max_tries must be > 0");
     if (!sets_or_null && c->F.P < 4) return fail(c, DSAC_ERR_INVALID, "dsac_score_hypotheses: frame has fewer than 4 cells");
+    ARG_TRY(k2_cams_check(c, Nf > 0 ? "dsac_score_hypotheses_frames" : "dsac_score_hypotheses"));
     HIP_TRY(c, hipSetDevice(c->device));
     // "pi_defer_tail" = 2 on a frame batch with device-resident arguments: the score tail (reduction of the per-tile sums + K3: two small launches that
     // leave the chip idle while they run in order) goes to the tail stream, K1 of the NEXT call follows K2 of this one without a gap -- the contract of
@@ -1115,6 +1212,9 @@ int dsac_sample_ahead(dsac_ctx* c, int slot, int N, uint64_t seed, const int32_t
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_sample_ahead: ctx is NULL");
     if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "dsac_sample_ahead: no frame set");
     if (slot < 0 || slot > 1 || N <= 0 || !poses || !sets_out || !ok) return fail(c, DSAC_ERR_INVALID, "dsac_sample_ahead: slot in {0,1}, N > 0, non-NULL outputs");
+    if (c->F.cams)
+        return fail(c, DSAC_ERR_INVALID, "dsac_sample_ahead: the current frames carry per-frame cameras (dsac_set_frames_cams): a slot keeps its frame across later set "
+                                         "calls, the library's camera table does not (dsac_score_hypotheses_frames / dsac_process_images take such a batch)");
     int Nf = 0;  // frame batch: N = frames x hypotheses per frame, frame f draws from the stream of seed + f
     if (c->F.frames > 1) {
         if (sets_or_null || N % c->F.frames != 0 || (N / c->F.frames) % 128 != 0)
@@ -1306,6 +1406,7 @@ int dsac_get_option(dsac_ctx* c, const char* key, int* value) {
     else if (k == "seed_stride") *value = c->seed_stride;
     else if (k == "pi_defer_tail") *value = c->pi_defer_tail;
     else if (k == "k1_cus") *value = c->k1_cus;
+    else if (k == "frame_cams") *value = (c->have_frame && c->F.cams) ? 1 : 0;  // read-only: the current frames carry one camera each (dsac_set_frames_cams)
     else return fail(c, DSAC_ERR_INVALID, "dsac_get_option: unknown key '%s'", key);
     return DSAC_OK;
 }
@@ -1314,6 +1415,10 @@ int dsac_k2_range_census(dsac_ctx* c, int N, const double* poses, long long* far
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_k2_range_census: ctx is NULL");
     if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "dsac_k2_range_census: no frame set");
     if (N < 0 || (N > 0 && !poses) || !far_chunks || !oor_poses) return fail(c, DSAC_ERR_INVALID, "dsac_k2_range_census: N >= 0 and non-NULL poses / outputs");
+    // per-frame cameras: the records of hypothesis h fold the camera of frame h / (N / frames), as the scoring calls split them
+    const int census_frames = c->F.frames > 1 ? c->F.frames : 1;
+    if (c->F.cams && N % census_frames != 0)
+        return fail(c, DSAC_ERR_INVALID, "dsac_k2_range_census: with per-frame cameras N must be frames x (hypotheses per frame), got %d for %d frames", N, census_frames);
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c);
     const double* d_poses;
@@ -1321,7 +1426,7 @@ int dsac_k2_range_census(dsac_ctx* c, int N, const double* poses, long long* far
     DevBuf& cnt = next_slot(c);
     HIP_TRY(c, cnt.reserve(2 * sizeof(unsigned long long)));
     HIP_TRY(c, hipMemsetAsync(cnt.p, 0, 2 * sizeof(unsigned long long), c->stream));
-    HIP_TRY(c, dk::k2_range_census(c->stream, N, d_poses, c->F, cnt.as<unsigned long long>()));
+    HIP_TRY(c, dk::k2_range_census(c->stream, N, d_poses, c->F, cnt.as<unsigned long long>(), census_frames > 1 ? N / census_frames : 0));
     unsigned long long h[2] = {0, 0};
     HIP_TRY(c, hipMemcpyAsync(h, cnt.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1379,11 +1484,7 @@ static int k4_f16_check(dsac_ctx* c, const char* who, int elem, int N, const uin
     const int frames = F.frames > 1 ? F.frames : 1;
     const int n1 = N / frames;
     for (int f = 0; f < frames; f++) {
-        dk::FrameDev Fd = F;
-        Fd.frames = 1;
-        Fd.xyz = F.xyz + (size_t)f * F.xyz_stride;
-        if (Fd.uv) Fd.uv = F.uv + (size_t)f * F.uv_stride;
-        Fd.xyz_stride = Fd.uv_stride = 0;
+        const dk::FrameDev Fd = frame_view(F, f);
         const uint16_t* d = d_err16 + (size_t)f * n1 * F.P;
         const int form = dk::backward_plan(n1, Fd, d, c->k4_variant, 0, elem).variant;
         if (form > 0) {
@@ -1419,6 +1520,7 @@ static int score_backward_common(dsac_ctx* c, const char* who, int N, const doub
         return fail(c, DSAC_ERR_INVALID, "%s: with a frame batch N must be frames x (hypotheses per frame), got %d for %d frames", who, N, frames);
     // the reference's jp-convention Jacobians use one focal length, f = camMat(0,0), for both axes (core/cnn_softam.h:406,466);
     // a camera with fx != fy would make this backward inconsistent with the forward kernels, which honour both
+    ARG_TRY(cams_fxfy_check(c, who));  // per-frame cameras: row by row, with the frame index
     if (c->F.fx != c->F.fy) return fail(c, DSAC_ERR_INVALID, "%s: needs fx == fy (got %g, %g): dProjectdObj / dProjectdHyp use a single focal length", who,
                                         (double)c->F.fx, (double)c->F.fy);
     if (N < 0 || !poses || !sets || !grad_xyz || (!d_err && !g)) return fail(c, DSAC_ERR_INVALID, "%s: NULL argument", who);
@@ -1464,14 +1566,6 @@ static int score_backward_common(dsac_ctx* c, const char* who, int N, const doub
         HIP_TRY(c, dk::dpnp(c->stream, N, d_sets, c->F, 0.1f, s.as<double>(), Nf));
         d_dpnp = s.as<double>();
     }
-    auto frame_view = [&](int f) {  // frame f of a batch as a single frame
-        dk::FrameDev Fd = c->F;
-        Fd.frames = 1;
-        Fd.xyz = c->F.xyz + (size_t)f * c->F.xyz_stride;
-        if (Fd.uv) Fd.uv = c->F.uv + (size_t)f * c->F.uv_stride;
-        Fd.xyz_stride = Fd.uv_stride = 0;
-        return Fd;
-    };
     if (parity) {
         // fp64 parity mode: the reference's evaluation order, optional rotation write-back (quirk 7); a batch frame by frame (the scratch reused in stream order)
         const int n1 = frames > 1 ? Nf : N;
@@ -1480,7 +1574,7 @@ static int score_backward_common(dsac_ctx* c, const char* who, int N, const doub
         HIP_TRY(c, c->g6.reserve((size_t)N * 6 * sizeof(double)));
         for (int f = 0; f < frames; f++) {
             const size_t h0 = (size_t)f * n1;
-            HIP_TRY(c, dk::score_backward_parity(c->stream, n1, d_poses + h0 * 6, frames > 1 ? frame_view(f) : c->F, static_cast<const float*>(derr_row(h0)), d_dpnp + h0 * 72, d_sets + h0 * 4, flags,
+            HIP_TRY(c, dk::score_backward_parity(c->stream, n1, d_poses + h0 * 6, frames > 1 ? frame_view(c->F, f) : c->F, static_cast<const float*>(derr_row(h0)), d_dpnp + h0 * 72, d_sets + h0 * 4, flags,
                                                  jac.as<double>(), d_grad + (size_t)f * P * 3, c->g6.as<double>() + h0 * 6));
         }
         c->g6_n = N;
@@ -1527,7 +1621,7 @@ static int score_backward_common(dsac_ctx* c, const char* who, int N, const doub
         // a frame batch on a map the matrix-core form cannot read as vectors (H*W or W not a multiple of 4, unaligned buffers), or with a hypothesis count
         // per frame that is not a multiple of 16 up to 256: frame by frame through the single-frame forms, the scratch buffers reused in stream order -- F times the launches, the same numbers as F single-frame calls
         for (int f = 0; f < frames; f++) {
-            const dk::FrameDev Fd = frame_view(f);
+            const dk::FrameDev Fd = frame_view(c->F, f);
             const dk::K4Plan pf = dk::backward_plan(Nf, Fd, derr_row((size_t)f * Nf), plain ? c->k4_variant : staged_variant, 0, elem);
             if (pf.Nf < 0 || (f16 && pf.variant <= 0)) return fail(c, DSAC_ERR_INVALID, "%s: no kernel form for this map (k4_variant %d)", who, c->k4_variant);
             ARG_TRY(run(Nf, Fd, pf, (size_t)f * Nf, (size_t)f * P, 0));
@@ -1796,6 +1890,7 @@ int dsac_backward_path1(dsac_ctx* c, int N, const double* poses, const int32_t* 
     if (!poses || !sets || !w || !avg_cv6 || !ref_cv6 || !gt_jp6 || !perm || !inlier_map || !grad_xyz || !g || steps < 0)
         return fail(c, DSAC_ERR_INVALID, "dsac_backward_path1: NULL argument or bad count");
     if (max_inl < 1 || max_inl > 256) return fail(c, DSAC_ERR_INVALID, "dsac_backward_path1: need 1 <= max_inl <= 256");
+    ARG_TRY(cams_fxfy_check(c, "dsac_backward_path1"));  // per-frame cameras: a backward call like the score backward, one focal length per frame
     FdStage fd;
     ARG_TRY(fd_stage_check(c, "dsac_backward_path1", sub_sample, &eps_hyp, eps_obj, &fd));
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2082,6 +2177,7 @@ int dsac_process_images(dsac_ctx* c, int hyps_per_frame, uint64_t seed, float th
     if ((out4_or_null != nullptr) != (gt_jp6_or_null != nullptr)) return fail(c, DSAC_ERR_INVALID, "dsac_process_images: out4 and gt_jp6 go together");
     if (max_inl < 1 || max_inl > 256 || min_inl < 0) return fail(c, DSAC_ERR_INVALID, "dsac_process_images: need 1 <= max_inl <= 256 (got %d), min_inl >= 0", max_inl);
     if (max_tries <= 0 || c->F.P < 4) return fail(c, DSAC_ERR_INVALID, "dsac_process_images: max_tries > 0 and a frame of at least 4 cells needed");
+    ARG_TRY(k2_cams_check(c, "dsac_process_images"));
     if (c->pi_refstream) ARG_TRY(pi_refstream_check(c, "dsac_process_images (pi_refstream)", hyps_per_frame));  // before anything is enqueued
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c, /*keep_tail=*/c->pi_defer_tail != 0);
@@ -2176,6 +2272,7 @@ static int pi_begin_call(dsac_ctx* c, const char* who, int hyps_per_frame, uint6
     if (!poses || !sets_out || !ok || (!err && !soft_or_null))
         return fail(c, DSAC_ERR_INVALID, "%s: poses / sets_out / ok and at least one of err / soft must be non-NULL", who);
     if (max_tries <= 0 || c->F.P < 4) return fail(c, DSAC_ERR_INVALID, "%s: max_tries > 0 and a frame of at least 4 cells needed", who);
+    ARG_TRY(k2_cams_check(c, who));
     if (elem != dk::K2_ELEM_F32) ARG_TRY(k2_f16_check(c, who, elem, err));  // before anything is enqueued
     if (c->pi_refstream) ARG_TRY(pi_refstream_check(c, (std::string(who) + " (pi_refstream)").c_str(), hyps_per_frame));  // before anything is enqueued
     HIP_TRY(c, hipSetDevice(c->device));

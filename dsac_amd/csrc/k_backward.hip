@@ -361,7 +361,8 @@ __global__ __launch_bounds__(K4_THREADS, MINW) void k_score_backward_mfma(const 
                                                                     float* __restrict__ G12_part, int N, int P, int W, int PT, int NT, int G,
                                                                     float f, float cx, float cy, float clampv, float kA, float kB, float beta, int HT,
                                                                     const double* __restrict__ poses, double* __restrict__ grad_direct, unsigned gflags,
-                                                                    int frame_Nf, long long xyz_stride, long long uv_stride) {
+                                                                    int frame_Nf, long long xyz_stride, long long uv_stride,
+                                                                    const float4* __restrict__ cams) {
     // Round 4 (the fused stage): poses != nullptr -> the workgroup derives its hypothesis records from the cv poses itself (no k_backward_prep launch,
     // no record image in HBM) and writes G12_part hypothesis-major ([hyp][row][12]: the finish kernel reads a hypothesis' rows as one contiguous run);
     // grad_direct != nullptr (one hypothesis tile, N <= 256) -> the workgroups add their gradient straight into the caller's fp64 grad_xyz with atomics
@@ -378,6 +379,10 @@ __global__ __launch_bounds__(K4_THREADS, MINW) void k_score_backward_mfma(const 
         xyz += (long long)fr * xyz_stride;
         if (UV) uv += (long long)fr * uv_stride;
         if (grad_direct) grad_direct += (size_t)fr * P * 3;
+        if (cams) {  // one camera per frame (rows with fx == fy: the entry point has checked): the tile's focal length and principal point, a scalar load
+            const float4 k = cams[fr];
+            f = k.x; cx = k.z; cy = k.w;
+        }
     }
 
     // LDS: MFMA B operands in lane order (x row, negated y row, z row of 16 hypotheses), the per-hypothesis coefficients of the
@@ -832,7 +837,7 @@ hipError_t score_backward(hipStream_t st, int N, const float* staged_bwd, const 
         hipLaunchKernelGGL((k_score_backward_mfma<C_, S_, U_, W_, E_>), dim3(grid), dim3(K4_THREADS), lds, st, staged_bwd, F.xyz, F.uv,         \
                            static_cast<const E_*>(d_err_any), g,                                                                               \
                            grad_part, G12_part, N, F.P, F.W, PT, NT, G, F.fx, F.cx, F.cy, clampv, kA, kB, beta, HT, k_poses, k_direct, flags,   \
-                           plan.Nf, F.xyz_stride, F.uv_stride);                                                                                  \
+                           plan.Nf, F.xyz_stride, F.uv_stride, F.cams);                                                                          \
     } while (0)
     // the bfloat16 builds exist for the forms that need no scratch (k4_form_has_bf16: 2, 3 and 4 chunks at two waves per SIMD); the entry point has refused
     // the others by name, a launch that gets here all the same is an error
@@ -905,14 +910,18 @@ __global__ __launch_bounds__(256) void k_support_scatter(int N, int W, int pixel
                                                          const double* __restrict__ dRdH, const double* __restrict__ dpnp,
                                                          const int32_t* __restrict__ sets, int P, unsigned flags, double* __restrict__ grad_xyz,
                                                          double* __restrict__ G6_out, const float* __restrict__ rec_e, float f_e,
-                                                         const double* __restrict__ poses, int Nf) {
+                                                         const double* __restrict__ poses, int Nf, const float4* __restrict__ cams) {
     // poses != nullptr (round 4, the fused stage): G12_part is hypothesis-major ([hyp][row][12]: a wave reads 48 contiguous bytes per lane, the
     // whole hypothesis one contiguous run), the E-based sums apply, and dR/drod, Omega and t' are derived here from the cv pose -- every lane of the
     // hypothesis' wave redundantly, under the partial-row loads -- instead of being read from k_backward_prep's output
     const int h = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (h >= N) return;
-    if (Nf > 0) grad_xyz += (size_t)(h / Nf) * P * 3;  // frame batch: the support cells of hypothesis h lie in frame h / Nf
+    if (Nf > 0) {  // frame batch: the support cells of hypothesis h lie in frame h / Nf
+        const int fr = __builtin_amdgcn_readfirstlane(h / Nf);  // one hypothesis per wave
+        grad_xyz += (size_t)fr * P * 3;
+        if (cams) f_e = cams[fr].x;  // ... and the main pass scaled its sums by that frame's focal length
+    }
     // the first 8 x 64 partial rows (all 512 of the persistent main pass) are requested at once, before the pose-only fp64 work below, which then runs
     // under their latency; rows beyond them (the VALU form's per-tile rows) follow in a plain loop
     constexpr int PRE = 8;
@@ -1040,7 +1049,7 @@ hipError_t score_backward_finish(hipStream_t st, int N, const FrameDev& F, const
     // hyp_tiles == 0: the main pass has added its gradient into grad_xyz itself (K4Plan.direct)
     if (hyp_tiles > 0) hipLaunchKernelGGL(k_grad_reduce, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, F.P, F.W, F.H, hyp_tiles, grad_part, flags, grad_xyz);
     hipLaunchKernelGGL(k_support_scatter, dim3((N + 3) / 4), dim3(256), 0, st, N, F.W, pixel_tiles, G12_part, dRdH, dpnp, sets, F.P, flags, grad_xyz,
-                       G6_scratch, rec_if_e_based, F.fx, poses_if_fused, F.frames > 1 ? Nf : 0);
+                       G6_scratch, rec_if_e_based, F.fx, poses_if_fused, F.frames > 1 ? Nf : 0, F.cams);
     return hipGetLastError();
 }
 

@@ -25,9 +25,23 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
 // --------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_pose_prep(int N, const double* __restrict__ poses, float fx, float fy, float* __restrict__ staged) {
+// Per-frame cameras (FrameDev::cams) in the record kernels: hypothesis h of a batch folds the focal lengths of its own frame h / Nf (Nf <= 0: one frame, row 0),
+// and the split records that frame's own exponent -- what the single-frame call under that camera folds, bit for bit.
+DM_INLINE void pose_focal(const float4* __restrict__ cams, int h, int Nf, float& fx, float& fy) {
+    if (!cams) return;
+    const float4 k = cams[Nf > 0 ? h / Nf : 0];
+    fx = k.x; fy = k.y;
+}
+DM_INLINE int split_exponent_of(float fx, float fy) {  // pose_split_exponent's loop; a power of two up to 2^31 is exact as a float, as ldexp's double is
+    int e = 0;
+    while (e < 31 && (float)(1u << e) < fmaxf(fx, fy)) e++;
+    return e;
+}
+__global__ __launch_bounds__(256) void k_pose_prep(int N, const double* __restrict__ poses, float fx, float fy, float* __restrict__ staged,
+                                                   const float4* __restrict__ cams, int Nf) {
     const int h = blockIdx.x * blockDim.x + threadIdx.x;
     if (h >= N) return;
+    pose_focal(cams, h, Nf, fx, fy);
     double r[3] = {poses[6 * h], poses[6 * h + 1], poses[6 * h + 2]};
     double R[9];
     dm::rodrigues_v2m<false>(r, R, nullptr);
@@ -41,9 +55,11 @@ __global__ __launch_bounds__(256) void k_pose_prep(int N, const double* __restri
 
 // What the float records leave behind: lo = (float)(A - (double)(float)A) for the twelve entries of k_pose_prep's record (the same fp64 arithmetic, so
 // the pair is consistent with the records K1 stages itself).  k2_flags bit 27.
-__global__ __launch_bounds__(256) void k_pose_prep_lo(int N, const double* __restrict__ poses, float fx, float fy, float* __restrict__ staged_lo) {
+__global__ __launch_bounds__(256) void k_pose_prep_lo(int N, const double* __restrict__ poses, float fx, float fy, float* __restrict__ staged_lo,
+                                                      const float4* __restrict__ cams, int Nf) {
     const int h = blockIdx.x * blockDim.x + threadIdx.x;
     if (h >= N) return;
+    pose_focal(cams, h, Nf, fx, fy);
     double r[3] = {poses[6 * h], poses[6 * h + 1], poses[6 * h + 2]};
     double R[9];
     dm::rodrigues_v2m<false>(r, R, nullptr);
@@ -55,9 +71,9 @@ __global__ __launch_bounds__(256) void k_pose_prep_lo(int N, const double* __res
     for (int k = 0; k < 12; k++) o[k] = (float)(A[k] - (double)(float)A[k]);
 }
 
-hipError_t pose_prep_lo(hipStream_t st, int N, const double* poses, const FrameDev& F, float* staged_lo) {
+hipError_t pose_prep_lo(hipStream_t st, int N, const double* poses, const FrameDev& F, float* staged_lo, int Nf) {
     if (N <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_pose_prep_lo, dim3((N + 255) / 256), dim3(256), 0, st, N, poses, F.fx, F.fy, staged_lo);
+    hipLaunchKernelGGL(k_pose_prep_lo, dim3((N + 255) / 256), dim3(256), 0, st, N, poses, F.fx, F.fy, staged_lo, F.cams, Nf);
     return hipGetLastError();
 }
 
@@ -122,10 +138,15 @@ DM_INLINE bool split_row_bad(const double (&a)[4], int E) {
     bad |= split_piece_bad(rem, E + 6); bad |= split_piece_bad(rem, E - 5); bad |= split_piece_bad(rem, E - 16); bad |= split_piece_bad(rem, E - 27);
     return bad;
 }
-__global__ __launch_bounds__(256) void k_pose_prep_split(int N, const double* __restrict__ poses, float fx, float fy, int ex, h8* __restrict__ cross, h4* __restrict__ hi) {
+__global__ __launch_bounds__(256) void k_pose_prep_split(int N, const double* __restrict__ poses, float fx, float fy, int ex, h8* __restrict__ cross, h4* __restrict__ hi,
+                                                         const float4* __restrict__ cams, int Nf) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;  // one thread per (hypothesis, row)
     const int h = i / 3, r = i - 3 * h;
     if (h >= N) return;
+    if (cams) {
+        pose_focal(cams, h, Nf, fx, fy);
+        ex = split_exponent_of(fx, fy);
+    }
     double rv[3] = {poses[6 * h], poses[6 * h + 1], poses[6 * h + 2]};
     double R[9];
     dm::rodrigues_v2m<false>(rv, R, nullptr);
@@ -154,22 +175,27 @@ __global__ __launch_bounds__(256) void k_pose_prep_split(int N, const double* __
 
 size_t pose_split_bytes(int N) { return (size_t)N * (SPLIT_CROSS_BYTES + SPLIT_HI_BYTES); }
 bool pose_split_available(const FrameDev& F) { return pose_split_exponent(F) <= SPLIT_MAX_EX; }
-int pose_split_exponent(const FrameDev& F) {  // ceil(log2(max focal length)), at least 0; > SPLIT_MAX_EX = 10: the exact form is not available
+// ceil(log2(max focal length)), at least 0; > SPLIT_MAX_EX = 10: the exact form is not available.  With per-frame cameras: the largest over the frames (what
+// decides whether the form is available); the records of frame f fold that frame's own exponent (k_pose_prep_split)
+int pose_split_exponent(const FrameDev& F) {
+    float fm = fmaxf(F.fx, F.fy);
+    if (F.cams_h)
+        for (int f = 0; f < (F.frames > 1 ? F.frames : 1); f++) fm = fmaxf(fm, fmaxf(F.cams_h[4 * f], F.cams_h[4 * f + 1]));
     int e = 0;
-    while (ldexp(1.0, e) < (double)fmaxf(F.fx, F.fy)) e++;
+    while (ldexp(1.0, e) < (double)fm) e++;
     return e;
 }
-hipError_t pose_prep_split(hipStream_t st, int N, const double* poses, const FrameDev& F, void* split) {
+hipError_t pose_prep_split(hipStream_t st, int N, const double* poses, const FrameDev& F, void* split, int Nf) {
     if (N <= 0) return hipSuccess;
     h8* cross = reinterpret_cast<h8*>(split);
     h4* hi = reinterpret_cast<h4*>(reinterpret_cast<char*>(split) + (size_t)N * SPLIT_CROSS_BYTES);
-    hipLaunchKernelGGL(k_pose_prep_split, dim3((3 * N + 255) / 256), dim3(256), 0, st, N, poses, F.fx, F.fy, pose_split_exponent(F), cross, hi);
+    hipLaunchKernelGGL(k_pose_prep_split, dim3((3 * N + 255) / 256), dim3(256), 0, st, N, poses, F.fx, F.fy, pose_split_exponent(F), cross, hi, F.cams, Nf);
     return hipGetLastError();
 }
 
-hipError_t pose_prep(hipStream_t st, int N, const double* poses, const FrameDev& F, float* staged) {
+hipError_t pose_prep(hipStream_t st, int N, const double* poses, const FrameDev& F, float* staged, int Nf) {
     if (N <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_pose_prep, dim3((N + 255) / 256), dim3(256), 0, st, N, poses, F.fx, F.fy, staged);
+    hipLaunchKernelGGL(k_pose_prep, dim3((N + 255) / 256), dim3(256), 0, st, N, poses, F.fx, F.fy, staged, F.cams, Nf);
     return hipGetLastError();
 }
 
@@ -811,7 +837,7 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* 
                                                              float* __restrict__ soft_part, int N, int P, int W, int PT, float cx, float cy,
                                                              float clampv, float kA, float kB, int kflags, int Nf, long long xyz_stride,
                                                              long long uv_stride, const float* __restrict__ staged_lo = nullptr,
-                                                             const void* __restrict__ split = nullptr) {
+                                                             const void* __restrict__ split = nullptr, const float4* __restrict__ cams = nullptr) {
     constexpr int HT = 16 * NG;
     constexpr bool EX = EXF != 0, RSQ = EXF >= 2;  // EXF: 0 = fp32 transform, 1 = exact transform (split fp16 records), 2 = the same with the one-transcendental tail (hp_chunk_ex)
     // EXF = 3 / 4: EXF = 2 with the error images stored as IEEE binary16 (dsac_reproject_f16; `err` then points to halves).  Everything up to ev[r] and the sigmoid
@@ -846,6 +872,12 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* 
         const int frame = h0 / Nf;
         xyz += (long long)frame * xyz_stride;
         if (UV) uv += (long long)frame * uv_stride;
+        // one camera per frame: the tile's principal point (a scalar load, frame is uniform over the workgroup); the focal length is in the records.  The exact
+        // builds only -- per-frame cameras run no other form (api.hip refuses by name), and the fp32 / two-piece builds keep the code they had
+        if (EX && cams) {
+            const float4 k = cams[frame];
+            cx = k.z; cy = k.w;
+        }
     }
     __shared__ float s_soft[(SOFT && !PW) ? WAVES * HT : 1];
     // PW: every wave writes its own partial soft sums (row pt * WAVES + wave of soft_part), no LDS, no barrier
@@ -1309,7 +1341,7 @@ static hipError_t launch_reproject_st(hipStream_t st, int N, const float* staged
     const bool G64 = !UV && (F.W & 63) == 0;
 #define DSAC_K2S(E, S, U, G)                                                                                                               \
     hipExtLaunchKernelGGL((k_reproject_st<NG, CHW, WAVES, PW, E, S, U, G, MINW, LO, k2_bf16_exf<NG, CHW, MINW, EX>(S, U, G), ANY>), dim3(grid), dim3(WAVES * 64), 0, st, evA, evB, 0, staged, F.xyz, F.uv, err, \
-                          soft_part, N, F.P, F.W, PT, F.cx, F.cy, clampv, kA, kB, kflags, Nf, F.xyz_stride, F.uv_stride, staged_lo, split)
+                          soft_part, N, F.P, F.W, PT, F.cx, F.cy, clampv, kA, kB, kflags, Nf, F.xyz_stride, F.uv_stride, staged_lo, split, F.cams)
     if (ERR && SOFT) { if (UV) DSAC_K2S(true, true, true, false); else if (G64) DSAC_K2S(true, true, false, true); else DSAC_K2S(true, true, false, false); }
     else if (ERR) { if (UV) DSAC_K2S(true, false, true, false); else if (G64) DSAC_K2S(true, false, false, true); else DSAC_K2S(true, false, false, false); }
     else if (SOFT) {
@@ -1335,7 +1367,7 @@ static hipError_t launch_reproject_any(hipStream_t st, int N, const float* stage
     const bool ERR = err != nullptr, SOFT = soft_part != nullptr, UV = F.uv != nullptr;
 #define DSAC_K2T(E, S, U)                                                                                                                              \
     hipExtLaunchKernelGGL((k_reproject_st<4, 1, 1, true, E, S, U, false, 3, false, 2, 2>), dim3(NTa), dim3(64), 0, st, nullptr, evB, 0, staged, F.xyz, F.uv, err, part, N, \
-                          F.P, F.W, 1, F.cx, F.cy, clampv, kA, kB, kflags | 32, Nf, F.xyz_stride, F.uv_stride, nullptr, split)
+                          F.P, F.W, 1, F.cx, F.cy, clampv, kA, kB, kflags | 32, Nf, F.xyz_stride, F.uv_stride, nullptr, split, F.cams)
     if (ERR && SOFT) { if (UV) DSAC_K2T(true, true, true); else DSAC_K2T(true, true, false); }
     else if (ERR) { if (UV) DSAC_K2T(true, false, true); else DSAC_K2T(true, false, false); }
     else if (SOFT) { if (UV) DSAC_K2T(false, true, true); else DSAC_K2T(false, true, false); }
@@ -1529,7 +1561,7 @@ static hipError_t launch_reproject_prec(hipStream_t st, int N, const double* pos
 // hypothesis t as k_pose_prep_split does and notes a clamped piece or a non-finite entry.
 // --------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_k2_census(int N, const double* __restrict__ poses, float fx, float fy, int ex, const float* __restrict__ xyz, int P, int frames,
-                                                   long long xyz_stride, unsigned long long* __restrict__ out) {
+                                                   long long xyz_stride, unsigned long long* __restrict__ out, const float4* __restrict__ cams, int Nf) {
     const int t = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
     const int CR = (P + 63) >> 6;
     const int w = t >> 6;  // wave-uniform
@@ -1542,6 +1574,10 @@ __global__ __launch_bounds__(256) void k_k2_census(int N, const double* __restri
         if (__any(o) && lane == 0) atomicAdd(out, 1ull);
     }
     if (t < N) {
+        if (cams) {  // as k_pose_prep_split: the focal lengths and the exponent of the hypothesis' own frame
+            pose_focal(cams, t, Nf, fx, fy);
+            ex = split_exponent_of(fx, fy);
+        }
         double rv[3] = {poses[6 * t], poses[6 * t + 1], poses[6 * t + 2]};
         double R[9];
         dm::rodrigues_v2m<false>(rv, R, nullptr);
@@ -1556,12 +1592,12 @@ __global__ __launch_bounds__(256) void k_k2_census(int N, const double* __restri
         if (bad) atomicAdd(out + 1, 1ull);
     }
 }
-hipError_t k2_range_census(hipStream_t st, int N, const double* poses, const FrameDev& F, unsigned long long* out2) {
+hipError_t k2_range_census(hipStream_t st, int N, const double* poses, const FrameDev& F, unsigned long long* out2, int Nf) {
     const int frames = F.frames > 1 ? F.frames : 1;
     const long long waves = (long long)frames * ((F.P + 63) / 64);
     const long long threads = waves * 64 > N ? waves * 64 : N;
     if (threads <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_k2_census, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, N, poses, F.fx, F.fy, pose_split_exponent(F), F.xyz, F.P, frames, F.xyz_stride, out2);
+    hipLaunchKernelGGL(k_k2_census, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, N, poses, F.fx, F.fy, pose_split_exponent(F), F.xyz, F.P, frames, F.xyz_stride, out2, F.cams, Nf);
     return hipGetLastError();
 }
 

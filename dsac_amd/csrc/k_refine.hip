@@ -411,13 +411,9 @@ __global__ __launch_bounds__(64 * S) void k_refine(int B, const int32_t* __restr
     // a latency chain on one wave: whatever shares its SIMD (K5 beside the replicas in dsac_backward_path1, K1 / K2 beside a deferred tail) issues after it
     __builtin_amdgcn_s_setprio(3);
     if (frame_of_group) {  // DSAC variant on a frame batch: replica list m = b / group belongs to hypothesis m, which lives in frame frame_of_group[m]
-        const int f = clamp_frame(frame_of_group[group > 0 ? b / group : 0], F);
-        F.xyz += (long long)f * F.xyz_stride;
-        if (F.uv) F.uv += (long long)f * F.uv_stride;
+        select_frame(F, uniform_frame(clamp_frame(frame_of_group[group > 0 ? b / group : 0], F)));
     } else if (per_frame > 0) {  // frame batch: one wave per (frame, problem) -- the per-image refinement of test_ransac_softam.cpp:97-157 for F images at once
-        const int f = b / per_frame;
-        F.xyz += (long long)f * F.xyz_stride;
-        if (F.uv) F.uv += (long long)f * F.uv_stride;
+        select_frame(F, b / per_frame);
     }
     // replica lists shorter than the launch: `group` replicas per list (0: one list), list m holds live_base + live_mul * n_live[m]
     if (n_live) {
@@ -640,12 +636,13 @@ __global__ __launch_bounds__(256) void k_refine_permute(int steps, int P256, Fra
     const int P = F.P;
     const size_t o = ((size_t)f * steps + step) * P256 + i;
     float m = 0.f, dd = 0.f;
+    select_frame(F, f);  // the frame's cells, positions and -- for the bound D over |u - cx| + |v - cy| -- its own principal point
     if (i < P) {
         const int p = min(max(perm[(size_t)step * P + i], 0), P - 1);
-        const float* xyz = F.xyz + (long long)f * F.xyz_stride;
+        const float* xyz = F.xyz;
         float2 w;
         if (F.uv) {
-            const float* uv = F.uv + (long long)f * F.uv_stride;
+            const float* uv = F.uv;
             w = make_float2(uv[(size_t)p * 2], uv[(size_t)p * 2 + 1]);
         } else {
             const int y = p / F.W;
@@ -657,7 +654,7 @@ __global__ __launch_bounds__(256) void k_refine_permute(int steps, int P256, Fra
         if (step == 0) {  // the bounds over the frame's cells themselves (cell i, not the permuted one): whatever the index lists hold is covered
             m = fabsf(xyz[(size_t)i * 3]) + fabsf(xyz[(size_t)i * 3 + 1]) + fabsf(xyz[(size_t)i * 3 + 2]);
             if (F.uv) {
-                const float* uv = F.uv + (long long)f * F.uv_stride;
+                const float* uv = F.uv;
                 dd = fabsf(uv[(size_t)i * 2] - F.cx) + fabsf(uv[(size_t)i * 2 + 1] - F.cy);
             } else {
                 const int y = i / F.W;
@@ -775,6 +772,7 @@ __global__ __launch_bounds__(64 * SCAN_WAVES) void k_refine_walk(int B, const do
     const int b0 = (int)((blockIdx.x + blockIdx.y) % gridDim.x) * G;
     const int kc = (int)blockIdx.y * SCAN_WAVES + wave;
     const int f = per_frame > 0 ? b0 / per_frame : 0;
+    select_frame(F, f);  // C1, thr1, the principal point and K below are the frame's own (the cells themselves come pre-permuted: F.xyz / F.uv are not read here)
     cells_step += (long long)f * frame_stride;
     uvs_step += (long long)f * frame_stride;
     const int cbase = min(kc, nchunks - 1) * chunk_cells, cend = min(cbase + chunk_cells, P256);
@@ -877,9 +875,10 @@ __global__ __launch_bounds__(64 * SCAN_WAVES) void k_refine_walk(int B, const do
 // by bisection), the selected cells' map counters, lm_pnp.
 __global__ __launch_bounds__(64) void k_refine_lm(int B, double* __restrict__ poses, int32_t* __restrict__ alive, int32_t* __restrict__ steps_done, int max_inl, int min_inl,
                                                   FrameDev F, const int32_t* __restrict__ cnt, int nchunks, int tag, const float* __restrict__ lists,
-                                                  int32_t* __restrict__ inlier_map, int map_stride, double* __restrict__ Rt, float* __restrict__ rec) {
+                                                  int32_t* __restrict__ inlier_map, int map_stride, double* __restrict__ Rt, float* __restrict__ rec, int per_frame) {
     const int b = blockIdx.x;
     if (b >= B || !alive[b]) return;
+    if (per_frame > 0) select_frame(F, b / per_frame);  // the camera of the problem's frame (the cells come from the scan's lists)
     __builtin_amdgcn_s_setprio(3);
     const int lane = threadIdx.x;
     __shared__ float s_X[RF_MAX_INL * 3];
@@ -939,7 +938,7 @@ __global__ __launch_bounds__(64) void k_refine_lm(int B, double* __restrict__ po
 }
 
 __global__ void k_refine_split_init(int B, int Bp, FrameDev F, const double* __restrict__ init_poses, double* __restrict__ out_poses, int32_t* __restrict__ alive,
-                                    int32_t* __restrict__ steps_done, double* __restrict__ Rt, float* __restrict__ rec) {
+                                    int32_t* __restrict__ steps_done, double* __restrict__ Rt, float* __restrict__ rec, int per_frame) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= Bp) return;
     if (b >= B) {  // padding up to a whole group of the scan
@@ -947,6 +946,7 @@ __global__ void k_refine_split_init(int B, int Bp, FrameDev F, const double* __r
         for (int i = 0; i < SCAN_REC; i++) rec[(size_t)b * SCAN_REC + i] = 0.f;
         return;
     }
+    if (per_frame > 0) select_frame(F, b / per_frame);  // one thread per problem: the record folds the focal length of the problem's frame
     const dm::Cam K = make_cam_r(F);
     double pose[6];
     for (int i = 0; i < 6; i++) { pose[i] = init_poses[(size_t)b * 6 + i]; out_poses[(size_t)b * 6 + i] = pose[i]; }
@@ -1013,7 +1013,7 @@ hipError_t refine_split(hipStream_t st, int B, const double* init_poses, const i
     const int P256 = (F.P + 255) / 256 * 256;
     float4* cells = reinterpret_cast<float4*>(p); p += (size_t)frames * max(steps, 1) * P256 * 16;
     float2* uvs = reinterpret_cast<float2*>(p);
-    hipLaunchKernelGGL(k_refine_split_init, dim3(((int)Bp + 63) / 64), dim3(64), 0, st, B, (int)Bp, F, init_poses, out_poses, alive, sd, Rt, rec);
+    hipLaunchKernelGGL(k_refine_split_init, dim3(((int)Bp + 63) / 64), dim3(64), 0, st, B, (int)Bp, F, init_poses, out_poses, alive, sd, Rt, rec, per_frame);
     if (steps <= 0) return hipGetLastError();
     hipError_t e = hipMemsetAsync(cnt, 0, align256(Bp * nchunks * 4) + scan_bounds_bytes(frames), st);  // chunk words carry the step's tag (step + 1): none is current
     if (e != hipSuccess) return e;
@@ -1030,7 +1030,7 @@ hipError_t refine_split(hipStream_t st, int B, const double* init_poses, const i
         else if (G == 2) hipLaunchKernelGGL((k_refine_walk<2>), grid, dim3(64 * SCAN_WAVES), 0, st, WALK_ARGS);
         else hipLaunchKernelGGL((k_refine_walk<1>), grid, dim3(64 * SCAN_WAVES), 0, st, WALK_ARGS);
 #undef WALK_ARGS
-        hipLaunchKernelGGL(k_refine_lm, dim3(B), dim3(64), 0, st, B, out_poses, alive, sd, max_inl, min_inl, F, cnt, nchunks, tag, lists, inlier_map, map_stride, Rt, rec);
+        hipLaunchKernelGGL(k_refine_lm, dim3(B), dim3(64), 0, st, B, out_poses, alive, sd, max_inl, min_inl, F, cnt, nchunks, tag, lists, inlier_map, map_stride, Rt, rec, per_frame);
     }
     return hipGetLastError();
 }
@@ -1110,13 +1110,14 @@ struct FdList {
     int32_t *obj_pixels, *n_obj;
     double init[6];  // !SET: the start pose
 };
-// also moves F.xyz to the list's frame: the perturbed values are read from the frame's own map
+// also selects the list's frame (select_frame: the perturbed values are read from the frame's own map; the plan reads neither uv nor the camera, which the
+// helper moves along -- a dead shift and, with a table, one scalar load per workgroup)
 template <bool SET>
 DM_INLINE FdList fd_list(const FdLists& L, size_t m, FrameDev& F, const double* init_pose, const int32_t* set4, const int32_t* inlier_map, double* rep_poses,
                          int32_t* rep_px_c, float* rep_value, int32_t* obj_pixels, int32_t* n_obj) {
     const size_t R = fd_head<SET>() + 6 * (size_t)L.cap;
     const int f = L.frame_of ? clamp_frame(L.frame_of[m], F) : L.list_is_frame ? (int)m : 0;
-    F.xyz += (long long)f * F.xyz_stride;
+    select_frame(F, f);
     FdList l = {SET ? set4 + 4 * m : nullptr, inlier_map + m * F.P, rep_poses + m * R * 6, rep_px_c + m * R * 2, rep_value + m * R,
                 obj_pixels + m * (size_t)L.px_stride, n_obj + m, {0, 0, 0, 0, 0, 0}};
     if (!SET) {
@@ -1288,9 +1289,7 @@ __global__ __launch_bounds__(64) void k_refine_fd_init_set(int cap, const int32_
         const size_t m = blockIdx.y, R = 18 + 6 * (size_t)cap;
         set4 += 4 * m; rep_px_c += m * R * 2; rep_value += m * R; rep_poses += m * R * 6; n_obj += m;
         if (frame_of) {
-            const long long f = clamp_frame(frame_of[m], F);
-            F.xyz += f * F.xyz_stride;
-            if (F.uv) F.uv += f * F.uv_stride;
+            select_frame(F, uniform_frame(clamp_frame(frame_of[m], F)));
         }
     }
     // four lanes per replica, one per quartic root (side by side, as in K5)

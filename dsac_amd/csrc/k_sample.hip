@@ -133,8 +133,10 @@ __global__ __launch_bounds__(64 * WPB, MINW) void k_sample(int N, uint64_t seed,
     const int hc = done ? 0 : h;
     const int root = lane & (RL - 1);
     const int frame = hc / Nf;           // Nf == N for a single frame
-    F.xyz += (long long)frame * F.xyz_stride;
-    if (F.uv) F.uv += (long long)frame * F.uv_stride;
+    // one hypothesis per wave: the camera row is one scalar load.  The builds with HPW hypotheses per wave (which may sit in two frames: their maps move per
+    // lane) are not launched on a table -- sample() takes HPW = 1 then, the results do not depend on HPW -- and keep the code they had
+    if (HPW == 1) select_frame(F, uniform_frame(frame));
+    else { F.cams = nullptr; select_frame(F, frame); }
     const uint64_t key = dm::hyp_key(seed + (uint64_t)frame * (uint64_t)F.seed_stride, (uint32_t)(hc - frame * Nf));
     const dm::Cam K = make_cam(F);
     for (int base = 0; base < max_tries; base += APR) {
@@ -241,8 +243,7 @@ __global__ __launch_bounds__(64 * WPH) void k_sample_wide(int N, uint64_t seed, 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int h = blockIdx.x;  // grid = N
     const int frame = h / Nf;
-    F.xyz += (long long)frame * F.xyz_stride;
-    if (F.uv) F.uv += (long long)frame * F.uv_stride;
+    select_frame(F, frame);
     const uint64_t key = dm::hyp_key(seed + (uint64_t)frame * (uint64_t)F.seed_stride, (uint32_t)(h - frame * Nf));
     const dm::Cam K = make_cam(F);
     const double thr_hi = (double)thr_int + 0.01;
@@ -358,7 +359,7 @@ __global__ __launch_bounds__(64 * SW) void k_sample_shared(int N, uint64_t seed,
     }
     __syncthreads();
     const int root = lane & 3;
-    const dm::Cam K = make_cam(F);
+    dm::Cam K = make_cam(F);  // the shared camera; with per-frame cameras the target hypothesis' frame sets it in every round
     const float* xyz0 = F.xyz;
     const float* uv0 = F.uv;
     const double thr_hi = (double)thr_int + 0.01;
@@ -388,9 +389,11 @@ __global__ __launch_bounds__(64 * SW) void k_sample_shared(int N, uint64_t seed,
 #pragma unroll
         for (int w = 0; w < SW; w++) if (w == t) bt = base[w];
         const int h = h_first + t;
-        const int frame = h / Nf;
-        F.xyz = xyz0 + (long long)frame * F.xyz_stride;
-        F.uv = uv0 ? uv0 + (long long)frame * F.uv_stride : nullptr;
+        const int frame = uniform_frame(h / Nf);  // t is the wave's target: one hypothesis per wave
+        F.xyz = xyz0;
+        F.uv = uv0;
+        select_frame(F, frame);
+        if (F.cams) K = make_cam(F);
         const uint64_t key = dm::hyp_key(seed + (uint64_t)frame * (uint64_t)F.seed_stride, (uint32_t)(h - frame * Nf));
         const long long att = (long long)bt + 16ll * sl + (lane >> 2);
         const uint32_t attempt = (uint32_t)att;
@@ -453,8 +456,9 @@ __global__ __launch_bounds__(64 * SW) void k_sample_shared(int N, uint64_t seed,
     const int h = h_first + wave;
     if (h < N && !s_acc[wave] && lane == 0) {
         const int frame = h / Nf;
-        F.xyz = xyz0 + (long long)frame * F.xyz_stride;
-        F.uv = uv0 ? uv0 + (long long)frame * F.uv_stride : nullptr;
+        F.xyz = xyz0;
+        F.uv = uv0;
+        select_frame(F, frame);
         const uint64_t key = dm::hyp_key(seed + (uint64_t)frame * (uint64_t)F.seed_stride, (uint32_t)(h - frame * Nf));
         int32_t set4[4];
         draw_set(F, key, (uint32_t)(max_tries - 1), set4);
@@ -501,7 +505,9 @@ hipError_t sample(hipStream_t st, int N, uint64_t seed, const int32_t* sets_in, 
         else hipLaunchKernelGGL(k_eval_sets<false>, dim3((N + 63) / 64), dim3(64), 0, st, N, sets_in, F, thr_int, poses, sets_out, ok, staged);
     } else {
         const int wpb = o.wpb, prio = o.prio;
-        const int H2 = o.hpw > 0 ? o.hpw : 1;  // see the measurement in the kernel's comment
+        int H2 = o.hpw > 0 ? o.hpw : 1;  // see the measurement in the kernel's comment
+        // per-frame cameras: a wave loads ONE camera row, so it holds one hypothesis (the results do not depend on HPW)
+        if (F.cams) H2 = 1;
 #define DSAC_K1(W, G, HN) hipLaunchKernelGGL((k_sample<W, G, HN>), dim3((N + W * G - 1) / (W * G)), dim3(64 * W), 0, st, N, seed, F, thr_int, max_tries, poses, sets_out, ok, staged, prio, Nf > 0 ? Nf : N)
         const int NfK = Nf > 0 ? Nf : N;
         if (o.horn) DSAC_K1(1, 1, true);
@@ -971,6 +977,7 @@ hipError_t refstream_chain(hipStream_t st, RefStreamState* states, int T, int N,
         G.xyz = F.xyz + (long long)f * F.xyz_stride;
         G.uv = F.uv ? F.uv + (long long)f * F.uv_stride : nullptr;
         G.frames = 1;
+        frame_cam(G, f);  // the launches of image f take its camera by value
         return G;
     };
     auto rows = [&](int f) {
@@ -1019,9 +1026,7 @@ hipError_t refstream_unserved(hipStream_t st, int T, const int32_t* first, const
 __global__ __launch_bounds__(128) void k_dpnp(int N, const int32_t* __restrict__ sets, FrameDev F, float eps, double* __restrict__ J, int Nf) {
     const int h = blockIdx.x;
     if (Nf > 0) {  // frame batch: hypothesis h belongs to frame h / Nf
-        const int f = h / Nf;
-        F.xyz += (long long)f * F.xyz_stride;
-        if (F.uv) F.uv += (long long)f * F.uv_stride;
+        select_frame(F, h / Nf);
     }
     const int t = threadIdx.x, lane = t & 63;
     const int s = t >> 2, root = t & 3;

@@ -17,7 +17,31 @@ struct FrameDev {
     int frames = 1;
     long long xyz_stride = 0, uv_stride = 0;
     int seed_stride = 1;  // frame f of a batch draws from the random stream of seed + f * seed_stride (dsac_set_option "seed_stride")
+    // one camera per frame (dsac_set_frames_cams): frames x (fx, fy, cx, cy) in device memory the context owns, nullptr = the shared camera above.
+    // fx .. cy then hold row 0 until a kernel selects its frame (select_frame); cams_h is the context's host copy of the same rows, for the code that
+    // walks a batch frame by frame on the host (frame_cam) -- no kernel reads it
+    const float4* cams = nullptr;
+    const float* cams_h = nullptr;
 };
+
+// The frame selection of every kernel that is handed a whole batch: xyz / uv move to frame `frame`, and with per-frame cameras the frame's row replaces
+// fx .. cy, so that make_cam / make_cam_r and everything behind them see the frame's own camera.  `frame` is wave-uniform at every call site (a workgroup or
+// a wave owns one hypothesis / problem / list); sites where the compiler cannot see that pass it through uniform_frame, which keeps the row a scalar load.
+__device__ __forceinline__ void select_frame(FrameDev& F, long long frame) {
+    F.xyz += frame * F.xyz_stride;
+    if (F.uv) F.uv += frame * F.uv_stride;
+    if (F.cams) {
+        const float4 k = F.cams[frame];
+        F.fx = k.x; F.fy = k.y; F.cx = k.z; F.cy = k.w;
+    }
+}
+__device__ __forceinline__ int uniform_frame(int frame) { return __builtin_amdgcn_readfirstlane(frame); }
+// the same selection on the host, for a FrameDev that stands for frame f alone (the caller has moved xyz / uv): the camera from the host copy, no table
+inline void frame_cam(FrameDev& G, int f) {
+    if (G.cams_h) { G.fx = G.cams_h[4 * f]; G.fy = G.cams_h[4 * f + 1]; G.cx = G.cams_h[4 * f + 2]; G.cy = G.cams_h[4 * f + 3]; }
+    G.cams = nullptr;
+    G.cams_h = nullptr;
+}
 
 // Staged pose record used by K2, 12 floats (48 B, three float4 rows) per hypothesis:
 //   [0..3]  fx*R0 | fx*tx      [4..7] fy*R1 | fy*ty      [8..11] R2 | tz
@@ -25,13 +49,14 @@ constexpr int POSE_STRIDE = 12;
 
 // ---- k_forward.hip ---------------------------------------------------------------------------------
 // fp64 Rodrigues of N cv poses -> staged float records.
-hipError_t pose_prep(hipStream_t st, int N, const double* poses, const FrameDev& F, float* staged);
-hipError_t pose_prep_lo(hipStream_t st, int N, const double* poses, const FrameDev& F, float* staged_lo);  // what the float records leave behind
+// Nf (per-frame cameras): hypotheses per frame, hypothesis h folds the camera of frame h / Nf; 0 = one frame
+hipError_t pose_prep(hipStream_t st, int N, const double* poses, const FrameDev& F, float* staged, int Nf = 0);
+hipError_t pose_prep_lo(hipStream_t st, int N, const double* poses, const FrameDev& F, float* staged_lo, int Nf = 0);  // what the float records leave behind
 // the records of the exact-transform form (k2_flags bit 28): pose_split_bytes(N) bytes; available for focal lengths up to 2^10 (pose_split_exponent <= 10)
 size_t pose_split_bytes(int N);
 int pose_split_exponent(const FrameDev& F);
 bool pose_split_available(const FrameDev& F);
-hipError_t pose_prep_split(hipStream_t st, int N, const double* poses, const FrameDev& F, void* split);
+hipError_t pose_prep_split(hipStream_t st, int N, const double* poses, const FrameDev& F, void* split, int Nf = 0);
 
 // K2.  err (N x P) and/or soft partials.  soft_part must hold reproject_num_pixel_tiles(P) * N floats.
 // Launch knobs of K2; they live in the context (read once from the environment in dsac_create), never in process-wide state.
@@ -77,7 +102,7 @@ hipError_t reproject(hipStream_t st, int N, const float* staged, const FrameDev&
 hipError_t reduce_soft(hipStream_t st, int N, int tiles, const float* soft_part, double* soft);
 // what the exact form degrades on (dsac_k2_range_census): out[0] += 64-cell chunks of the frame(s) with a coordinate outside the split's range (split_B's
 // predicate: those chunks take the fp32 transform), out[1] += hypotheses whose split records clamp a piece or hold a non-finite entry.  One small kernel.
-hipError_t k2_range_census(hipStream_t st, int N, const double* poses, const FrameDev& F, unsigned long long* out2);
+hipError_t k2_range_census(hipStream_t st, int N, const double* poses, const FrameDev& F, unsigned long long* out2, int Nf = 0);
 // K3.
 // frames > 1: one independent softmax per consecutive group of N scores (outputs entropy[frames], avg6[frames][6])
 hipError_t softmax(hipStream_t st, int N, const double* scores, double scale, double* w, double* entropy, const double* poses, double* avg6,

@@ -61,6 +61,18 @@ def _seam_elem(a, elem=None, what="err"):
     return own
 
 
+def frame_cams_arg(cam, frames):
+    """The `cam` argument of Engine.set_frames for a batch of `frames` frames: ((fx, fy, cx, cy), None) for one shared camera (shape (4,)), or
+    (None, table) with table a C-contiguous float32 host array of shape (frames, 4), one camera per frame.  Anything else -- (frames, 3), (frames + 1, 4),
+    a 3-D array -- is a ValueError.  Pure host code: no device, no library call."""
+    a = np.asarray(cam.detach().cpu().numpy() if hasattr(cam, "detach") else cam, dtype=np.float32)
+    if a.shape == (4,):
+        return tuple(float(c) for c in a), None
+    if a.ndim == 2 and a.shape == (int(frames), 4):
+        return None, np.ascontiguousarray(a)
+    raise ValueError("dsac_amd: cam must have shape (4,) (one camera for the batch) or (%d, 4) (fx, fy, cx, cy per frame), got %s" % (int(frames), a.shape))
+
+
 class Engine:
     """One DSAC engine context = one GPU stream.  Not thread-safe (one per host thread)."""
 
@@ -166,13 +178,18 @@ class Engine:
 
     def set_frames(self, xyz, uv=None, H=None, W=None, cam=(525.0, 525.0, 320.0, 240.0), uv_per_frame=False, borrow=False):
         """A batch of frames of the same geometry: xyz F x H*W x 3 float32 (contiguous), uv shared (H*W x 2), per frame (F x H*W x 2)
-        or None.  Only scoreHypothesesFrames works on a batch."""
+        or None.  cam: (fx, fy, cx, cy) shared by the frames, or an F x 4 array (numpy, or anything np.asarray takes) with one camera per frame
+        (dsac_set_frames_cams: every call that accepts a batch then gives the results of F single-frame calls, each under its own camera)."""
         xyz = _np(xyz, np.float32)
         F = int(xyz.shape[0])
         uv = _np(uv, np.float32) if uv is not None else None
-        fx, fy, cx, cy = [float(c) for c in cam]
-        check(self._ctx, lib.dsac_set_frames(self._ctx, F, ptr(xyz), ptr(uv), 1 if uv_per_frame else 0, int(H), int(W), fx, fy, cx, cy,
-                                             capi.DSAC_FRAME_BORROW if borrow else 0))
+        shared, table = frame_cams_arg(cam, F)  # a wrong shape raises here, before the library is called
+        flags = capi.DSAC_FRAME_BORROW if borrow else 0
+        if table is not None:
+            check(self._ctx, lib.dsac_set_frames_cams(self._ctx, F, ptr(xyz), ptr(uv), 1 if uv_per_frame else 0, int(H), int(W), ptr(table), flags))
+        else:
+            fx, fy, cx, cy = shared
+            check(self._ctx, lib.dsac_set_frames(self._ctx, F, ptr(xyz), ptr(uv), 1 if uv_per_frame else 0, int(H), int(W), fx, fy, cx, cy, flags))
         self.H, self.W, self.P, self.frames = int(H), int(W), int(H) * int(W), F
         self._keep = (xyz, uv) if borrow else None
 

@@ -215,7 +215,7 @@ DSAC_API int dsac_gather_rows(dsac_ctx* ctx, void* dst, const void* src, size_t 
 DSAC_API int dsac_set_frame(dsac_ctx* ctx, const float* xyz, const float* uv_or_null, int H, int W, float fx, float fy, float cx, float cy,
                    unsigned flags);
 
-/* Frame batch: `frames` coordinate maps of the same H x W and camera, stored back to back (frame f at xyz + f*H*W*3); uv is one
+/* Frame batch: `frames` coordinate maps of the same H x W and camera (one camera per frame: dsac_set_frames_cams below), stored back to back (frame f at xyz + f*H*W*3); uv is one
  * shared H*W x 2 table (uv_per_frame = 0), one table per frame (uv_per_frame = 1) or NULL (implicit grid).  Independent frames
  * are the unit the path shards over (core/test_ransac_softam.cpp:97-230); batching them lets one launch carry several frames.
  * A batch is accepted by: dsac_score_hypotheses_frames, the pipelined pair dsac_sample_ahead / dsac_score_sampled, dsac_process_images, dsac_refine,
@@ -234,6 +234,32 @@ DSAC_API int dsac_set_frame(dsac_ctx* ctx, const float* xyz, const float* uv_or_
  * dsac_refine_fd_set (one hypothesis: use dsac_refine_fd_sets). */
 DSAC_API int dsac_set_frames(dsac_ctx* ctx, int frames, const float* xyz, const float* uv_or_null, int uv_per_frame, int H, int W, float fx, float fy,
                     float cx, float cy, unsigned flags);
+/* Frame batch with ONE CAMERA PER FRAME: dsac_set_frames in everything but the camera -- the same layout, flags (DSAC_FRAME_BORROW,
+ * DSAC_FRAME_QUANTISE_INT16), "seed_stride", checks and ordering rules.  cams is a HOST array of frames x 4 floats (fx, fy, cx, cy of frame f in row f) that
+ * is read before the call returns, like `rows` of dsac_gather_rows; the caller may free or overwrite it right after.  The context keeps a host copy (form
+ * decisions, the fx == fy check of the backward calls, the paths that walk a batch frame by frame inside a call) and a device table it owns; the upload is
+ * ordered behind everything enqueued earlier, a deferred refinement tail included ("pi_defer_tail"), also for a borrowed frame.  This is for data sets with
+ * one calibration per image, several sensors in one evaluation, and augmentation by rescaling: they keep the batched fast path.
+ * Contract: every call that accepts a batch gives the results of `frames` single-frame calls, frame f under dsac_set_frame(..., cams[f]) with the seed
+ * seed + f * seed_stride -- bit for bit wherever the shared-camera batch is bit for bit against single frames, elsewhere (the score backward: fp32 partial
+ * sums grouped by the launch's workgroup count) within the same bound.  A table of equal rows gives dsac_set_frames' results bit for bit, and the
+ * shared-camera path itself is unchanged.  The kernels select the frame's row where they select its maps (one scalar load per workgroup or wave); the split
+ * records of K2's exact form fold every frame's own exponent ceil(log2 max(fx, fy)), as the single-frame call does.
+ * dsac_get_option("frame_cams") reads 1 while the current frames carry per-frame cameras; dsac_set_frame and dsac_set_frames reset it to 0.
+ * DSAC_ERR_INVALID, by name, with nothing changed in the context: cams NULL, cams a device pointer, a zero or non-finite focal length in any row (and
+ * whatever dsac_set_frames refuses).
+ * Form policy -- nothing takes another form silently; every refusal is DSAC_ERR_INVALID, launches nothing and leaves "k2_form_last" as it was:
+ *   - K2 (every scoring call) is the exact-transform form only, what the auto policy launches: vector or any-map build, float, binary16 or bfloat16 stores.
+ *     Refused: a focal length above 1024 px in any frame, "k2_variant" other than -1, a "k2_flags" bit other than 28 / 29, "k2_exact_auto" 0 without bit 28 / 29.
+ *   - the backward calls (dsac_score_backward and its _f16 / _bf16 twins, dsac_soft_score_backward, dsac_backward_path1) need fx == fy in every row; the
+ *     message names the first frame that differs.
+ *   - dsac_sample_ahead (and with it dsac_score_sampled): a slot keeps its frame across later set calls, the library's table has no such lifetime.
+ *   - dsac_k2_range_census takes N = frames x hypotheses per frame then (hypothesis h is split with the camera of frame h / (N / frames)).
+ *   - calls that refuse any batch keep doing so.
+ * Not part of this: the C++ host shim (dsac_amd/host, FrameBatchOptions) and the driver programs; shard.ShardRunner (its set-frames arguments are prebuilt
+ * for one camera); bench.py; K2's fp32, precise and two-piece forms under per-frame cameras; a device-resident cams array. */
+DSAC_API int dsac_set_frames_cams(dsac_ctx* ctx, int frames, const float* xyz, const float* uv_or_null, int uv_per_frame, int H, int W, const float* cams,
+                         unsigned flags);
 /* dsac_score_hypotheses for every frame of the batch in three launches (K1, K2, K3 over frames x hyps_per_frame hypotheses).
  * Frame f draws from the stream of seed + f, so the result equals `frames` single-frame calls with seeds seed, seed + 1, ...
  * hyps_per_frame must be a multiple of 128.  Outputs are frame-major: poses / sets_out / ok / scores / w [frames][hyps_per_frame],
