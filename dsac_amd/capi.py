@@ -51,6 +51,7 @@ EXPORTS = [
     "dsac_reproject_bf16", "dsac_process_images_begin_bf16",
     "dsac_score_backward_bf16", "dsac_soft_score_derr_bf16",
     "dsac_set_frames_cams",
+    "dsac_set_sampling_weights", "dsac_sampling_table", "dsac_sampling_weights_backward",
 ]
 
 # enum dsac_k2_form (dsac_get_option "k2_form_last") and the DSAC_K2_WHY_* bits ("k2_form_why_last")
@@ -115,6 +116,9 @@ def _load():
     lib.dsac_gather_patches.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp]
     lib.dsac_set_frames.argtypes = [vp, i32, vp, vp, i32, i32, i32, f32, f32, f32, f32, u32]
     lib.dsac_set_frames_cams.argtypes = [vp, i32, vp, vp, i32, i32, i32, vp, u32]
+    lib.dsac_set_sampling_weights.argtypes = [vp, vp]
+    lib.dsac_sampling_table.argtypes = [vp, vp]
+    lib.dsac_sampling_weights_backward.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.dsac_score_hypotheses_frames.argtypes = [vp, i32, u64, f32, i32, f32, f32, f32, f64, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.dsac_set_option.argtypes = [vp, C.c_char_p, i32]
     lib.dsac_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i32)]

@@ -60,6 +60,9 @@ struct dsac_ctx {
     // device table the kernels read; F.cams_h / F.cams point at them while the current frames carry per-frame cameras, else both are NULL
     std::vector<float> cams_h;
     DevBuf cams_d;
+    // guided sampling (dsac_set_sampling_weights): the table (frames x P uint64), the per-frame records (T, n, S, the maximum), the context's copy of the weights
+    // (the gradient reads their values) and the build's per-tile scratch.  k1.guide_cdf / k1.guide_meta point at them while weights are active, else both are NULL
+    DevBuf guide_cdf, guide_coarse, guide_meta, guide_w, guide_scratch;
 
     // scratch, one buffer per role so that calls can be chained without aliasing
     DevBuf rs_states, rs_scratch, rs_small, k6_scratch;  // the reference's random streams (dsac_refstream_init) and the scratch of a sampling window
@@ -404,6 +407,20 @@ int k2_soft_part(dsac_ctx* c, int N, bool want_err, bool want_soft, float* tau, 
 // K2 on frames with one camera each (dsac_set_frames_cams) is the exact-transform form and nothing else: what the auto policy launches, on the vector or the
 // any-map build.  Every scoring call asks here before it enqueues anything -- K1 included -- and is refused by name, "k2_form_last" keeps its value.  No-op
 // for the shared camera.
+// Guided sampling: what a call must refuse while weights are active (dsac_set_sampling_weights), by the caller's name and before anything is enqueued.
+// guide_draw_check: a call that draws from K1's counter stream -- "k1_horn" has no guided build;  guide_refuse: a call whose draw cannot be guided at all
+bool guided(const dsac_ctx* c) { return c->k1.guide_cdf != nullptr; }
+int guide_draw_check(dsac_ctx* c, const char* who) {
+    if (guided(c) && c->k1.horn)
+        return fail(c, DSAC_ERR_INVALID, "%s: sampling weights are active (dsac_set_sampling_weights) and \"k1_horn\" is 1: the Jacobi-sweep alignment has no guided build "
+                                         "(set \"k1_horn\" to 0, or clear the weights)", who);
+    return DSAC_OK;
+}
+int guide_refuse(dsac_ctx* c, const char* who, const char* why) {
+    if (guided(c)) return fail(c, DSAC_ERR_INVALID, "%s: sampling weights are active (dsac_set_sampling_weights): %s (clear them with dsac_set_sampling_weights(ctx, NULL))", who, why);
+    return DSAC_OK;
+}
+
 int k2_cams_check(dsac_ctx* c, const char* who) {
     const dk::FrameDev& F = c->F;
     if (!F.cams) return DSAC_OK;
@@ -606,6 +623,7 @@ void dsac_destroy(dsac_ctx* c) {
     if (c->aux) (void)hipStreamSynchronize(c->aux);
     if (c->aux2) (void)hipStreamSynchronize(c->aux2);
     c->frame_xyz.release(); c->frame_uv.release(); c->cams_d.release();
+    c->guide_cdf.release(); c->guide_coarse.release(); c->guide_meta.release(); c->guide_w.release(); c->guide_scratch.release();
     c->staged.release(); c->staged_lo.release(); c->staged_split.release(); c->rs_states.release(); c->rs_scratch.release(); c->rs_small.release(); c->k6_scratch.release(); c->soft_part.release(); c->bwd_staged.release(); c->dRdH.release();
     c->grad_part.release(); c->g12_part.release(); c->g6.release();
     for (auto& s : c->slots) s.release();
@@ -748,6 +766,8 @@ static int set_frames_common(dsac_ctx* c, int frames, const float* xyz, const fl
         c->F.cams = nullptr;
         c->F.cams_h = nullptr;
     }
+    c->k1.guide_cdf = nullptr;  // the sampling weights belong to the frames they were set for
+    c->k1.guide_meta = nullptr;
     c->F.xyz = new_xyz;
     c->F.uv = new_uv;
     c->F.H = H; c->F.W = W; c->F.P = (int)P1;
@@ -869,6 +889,73 @@ int dsac_set_frames_cams(dsac_ctx* c, int frames, const float* xyz, const float*
     return set_frames_common(c, frames, xyz, uv_or_null, uv_per_frame != 0, H, W, cams[0], cams[1], cams[2], cams[3], flags, cams);
 }
 
+// ---- guided sampling: K1 draws its minimal sets from per-cell weights (include/dsac_hip.h has the contract) ----------------------------------
+int dsac_set_sampling_weights(dsac_ctx* c, const float* weights_or_null) {
+    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_set_sampling_weights: ctx is NULL");
+    if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "dsac_set_sampling_weights: no frame set (the weights belong to the frames currently set)");
+    if (!weights_or_null) {
+        c->k1.guide_cdf = nullptr;
+        c->k1.guide_meta = nullptr;
+        return DSAC_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    // The table is touched on the context's stream only (the build here, K1, the gradient): a build is ordered behind every earlier K1 launch by the stream
+    // itself, and a deferred refinement tail reads none of it.  A host pointer goes through a staging slot like every host argument: the tail is joined then
+    begin_call(c, /*keep_tail=*/is_device_ptr(weights_or_null, c));
+    const int frames = c->F.frames > 1 ? c->F.frames : 1, P = c->F.P;
+    const size_t cells = (size_t)frames * (size_t)P;
+    const float* d_w;
+    ARG_TRY(in_arg(c, weights_or_null, cells, &d_w));
+    // buffers that have to grow are replaced (hipFree waits for the device); a failed allocation leaves the weights cleared, never half a table
+    c->k1.guide_cdf = nullptr;
+    c->k1.guide_meta = nullptr;
+    HIP_TRY(c, c->guide_cdf.reserve(cells * sizeof(uint64_t)));
+    HIP_TRY(c, c->guide_coarse.reserve((size_t)frames * (size_t)dk::guide_coarse_entries(P) * sizeof(uint64_t)));
+    HIP_TRY(c, c->guide_w.reserve(cells * sizeof(float)));
+    HIP_TRY(c, c->guide_meta.reserve((size_t)frames * sizeof(dk::GuideMeta)));
+    HIP_TRY(c, c->guide_scratch.reserve(dk::guide_scratch_bytes(frames, P)));
+    HIP_TRY(c, dk::guide_build(c->stream, frames, P, d_w, c->guide_w.as<float>(), c->guide_cdf.as<uint64_t>(), c->guide_coarse.as<uint64_t>(),
+                               c->guide_meta.as<dk::GuideMeta>(), c->guide_scratch.p));
+    c->k1.guide_cdf = c->guide_cdf.as<uint64_t>();
+    c->k1.guide_meta = c->guide_meta.as<dk::GuideMeta>();
+    c->k1.guide_coarse = c->guide_coarse.as<uint64_t>();
+    return DSAC_OK;
+}
+
+int dsac_sampling_table(dsac_ctx* c, uint64_t* cdf_out) {
+    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_sampling_table: ctx is NULL");
+    if (!c->have_frame || !guided(c)) return fail(c, DSAC_ERR_INVALID, "dsac_sampling_table: no sampling weights are active (dsac_set_sampling_weights)");
+    if (!cdf_out) return fail(c, DSAC_ERR_INVALID, "dsac_sampling_table: cdf_out is NULL (frames x H*W uint64)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    begin_call(c);
+    const size_t cells = (size_t)(c->F.frames > 1 ? c->F.frames : 1) * (size_t)c->F.P;
+    uint64_t* d_out;
+    ARG_TRY(out_arg(c, cdf_out, cells, &d_out));
+    HIP_TRY(c, hipMemcpyAsync(d_out, c->k1.guide_cdf, cells * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
+    return end_call(c);
+}
+
+int dsac_sampling_weights_backward(dsac_ctx* c, int N, const int32_t* sets, const uint8_t* ok, const double* g, double* grad_w) {
+    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_sampling_weights_backward: ctx is NULL");
+    if (!c->have_frame || !guided(c)) return fail(c, DSAC_ERR_INVALID, "dsac_sampling_weights_backward: no sampling weights are active (dsac_set_sampling_weights)");
+    const int frames = c->F.frames > 1 ? c->F.frames : 1;
+    if (N <= 0 || N % frames != 0 || !sets || !ok || !g || !grad_w)
+        return fail(c, DSAC_ERR_INVALID, "dsac_sampling_weights_backward: N > 0, a multiple of the %d frame(s), and sets / ok / g / grad_w must be non-NULL", frames);
+    HIP_TRY(c, hipSetDevice(c->device));
+    begin_call(c);
+    const size_t cells = (size_t)frames * (size_t)c->F.P;
+    const int32_t* d_sets;
+    const uint8_t* d_ok;
+    const double* d_g;
+    double* d_grad;
+    ARG_TRY(in_arg(c, sets, (size_t)N * 4, &d_sets));
+    ARG_TRY(in_arg(c, ok, (size_t)N, &d_ok));
+    ARG_TRY(in_arg(c, g, (size_t)N, &d_g));
+    ARG_TRY(out_arg(c, grad_w, cells, &d_grad, /*preload=*/true));  // accumulated into, like grad_xyz
+    HIP_TRY(c, dk::guide_backward(c->stream, frames, c->F.P, N / frames, c->guide_w.as<float>(), c->k1.guide_meta, d_sets, d_ok, d_g, d_grad));
+    return end_call(c);
+}
+
 int dsac_sample(dsac_ctx* c, int N, uint64_t seed, const int32_t* sets_or_null, float thr, int max_tries, double* poses, int32_t* sets_out,
                 uint8_t* ok) {
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_sample: ctx is NULL");
@@ -882,6 +969,7 @@ int dsac_sample(dsac_ctx* c, int N, uint64_t seed, const int32_t* sets_or_null, 
     if (N == 0) return DSAC_OK;
     if (!sets_or_null && max_tries <= 0) return fail(c, DSAC_ERR_INVALID, "dsac_sample: max_tries must be > 0");
     if (!sets_or_null && c->F.P < 4) return fail(c, DSAC_ERR_INVALID, "dsac_sample: frame has fewer than 4 cells");
+    if (!sets_or_null) ARG_TRY(guide_draw_check(c, "dsac_sample"));
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c);
     const int32_t* d_sets_in;
@@ -925,6 +1013,7 @@ int dsac_sample_refstream(dsac_ctx* c, int N, float thr, long long max_attempts,
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_sample_refstream: ctx is NULL");
     if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "dsac_sample_refstream: no frame set");
     if (c->rs_threads <= 0) return fail(c, DSAC_ERR_INVALID, "dsac_sample_refstream: call dsac_refstream_init first");
+    ARG_TRY(guide_refuse(c, "dsac_sample_refstream", "the reference's stream draws its cells as the reference does"));
     if (c->F.frames > 1) return fail(c, DSAC_ERR_INVALID, "dsac_sample_refstream: one frame at a time (the reference's streams run through its images in sequence)");
     if (N < 0 || !poses || !sets_out || !ok) return fail(c, DSAC_ERR_INVALID, "dsac_sample_refstream: N >= 0 and poses/sets_out/ok must be non-NULL");
     if (max_attempts <= 0) return fail(c, DSAC_ERR_INVALID, "dsac_sample_refstream: max_attempts (per stream) must be > 0");
@@ -988,6 +1077,7 @@ int dsac_sample_refstream_frames(dsac_ctx* c, int hyps_per_frame, float thr, lon
                                  int32_t* sets_out, uint8_t* ok, unsigned long long* consumed32_or_null, long long* attempts_or_null) {
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_sample_refstream_frames: ctx is NULL");
     if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "dsac_sample_refstream_frames: no frame set");
+    ARG_TRY(guide_refuse(c, "dsac_sample_refstream_frames", "the reference's stream draws its cells as the reference does"));
     if (hyps_per_frame < 0 || !poses || !sets_out || !ok)
         return fail(c, DSAC_ERR_INVALID, "dsac_sample_refstream_frames: hyps_per_frame >= 0 and poses/sets_out/ok must be non-NULL");
     const int frames = c->F.frames > 1 ? c->F.frames : 1;
@@ -1104,6 +1194,7 @@ static int score_hypotheses_common(dsac_ctx* c, int N, int Nf, uint64_t seed, co
     if (!sets_or_null && max_tries <= 0) return fail(c, DSAC_ERR_INVALID, "dsac_score_hypotheses: max_tries must be > 0");
     if (!sets_or_null && c->F.P < 4) return fail(c, DSAC_ERR_INVALID, "dsac_score_hypotheses: frame has fewer than 4 cells");
     ARG_TRY(k2_cams_check(c, Nf > 0 ? "dsac_score_hypotheses_frames" : "dsac_score_hypotheses"));
+    if (!sets_or_null) ARG_TRY(guide_draw_check(c, Nf > 0 ? "dsac_score_hypotheses_frames" : "dsac_score_hypotheses"));
     HIP_TRY(c, hipSetDevice(c->device));
     // "pi_defer_tail" = 2 on a frame batch with device-resident arguments: the score tail (reduction of the per-tile sums + K3: two small launches that
     // leave the chip idle while they run in order) goes to the tail stream, K1 of the NEXT call follows K2 of this one without a gap -- the contract of
@@ -1215,6 +1306,7 @@ int dsac_sample_ahead(dsac_ctx* c, int slot, int N, uint64_t seed, const int32_t
     if (c->F.cams)
         return fail(c, DSAC_ERR_INVALID, "dsac_sample_ahead: the current frames carry per-frame cameras (dsac_set_frames_cams): a slot keeps its frame across later set "
                                          "calls, the library's camera table does not (dsac_score_hypotheses_frames / dsac_process_images take such a batch)");
+    ARG_TRY(guide_refuse(c, "dsac_sample_ahead", "a slot keeps its frame across later set calls, the library's sampling table does not"));
     int Nf = 0;  // frame batch: N = frames x hypotheses per frame, frame f draws from the stream of seed + f
     if (c->F.frames > 1) {
         if (sets_or_null || N % c->F.frames != 0 || (N / c->F.frames) % 128 != 0)
@@ -1406,6 +1498,7 @@ int dsac_get_option(dsac_ctx* c, const char* key, int* value) {
     else if (k == "seed_stride") *value = c->seed_stride;
     else if (k == "pi_defer_tail") *value = c->pi_defer_tail;
     else if (k == "k1_cus") *value = c->k1_cus;
+    else if (k == "sampling_weights") *value = (c->have_frame && guided(c)) ? 1 : 0;  // read-only: sampling weights are active (dsac_set_sampling_weights)
     else if (k == "frame_cams") *value = (c->have_frame && c->F.cams) ? 1 : 0;  // read-only: the current frames carry one camera each (dsac_set_frames_cams)
     else return fail(c, DSAC_ERR_INVALID, "dsac_get_option: unknown key '%s'", key);
     return DSAC_OK;
@@ -2178,6 +2271,8 @@ int dsac_process_images(dsac_ctx* c, int hyps_per_frame, uint64_t seed, float th
     if (max_inl < 1 || max_inl > 256 || min_inl < 0) return fail(c, DSAC_ERR_INVALID, "dsac_process_images: need 1 <= max_inl <= 256 (got %d), min_inl >= 0", max_inl);
     if (max_tries <= 0 || c->F.P < 4) return fail(c, DSAC_ERR_INVALID, "dsac_process_images: max_tries > 0 and a frame of at least 4 cells needed");
     ARG_TRY(k2_cams_check(c, "dsac_process_images"));
+    ARG_TRY(guide_draw_check(c, "dsac_process_images"));
+    if (c->pi_refstream) ARG_TRY(guide_refuse(c, "dsac_process_images (pi_refstream)", "the reference's stream draws its cells as the reference does"));
     if (c->pi_refstream) ARG_TRY(pi_refstream_check(c, "dsac_process_images (pi_refstream)", hyps_per_frame));  // before anything is enqueued
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c, /*keep_tail=*/c->pi_defer_tail != 0);
@@ -2274,6 +2369,8 @@ static int pi_begin_call(dsac_ctx* c, const char* who, int hyps_per_frame, uint6
     if (max_tries <= 0 || c->F.P < 4) return fail(c, DSAC_ERR_INVALID, "%s: max_tries > 0 and a frame of at least 4 cells needed", who);
     ARG_TRY(k2_cams_check(c, who));
     if (elem != dk::K2_ELEM_F32) ARG_TRY(k2_f16_check(c, who, elem, err));  // before anything is enqueued
+    ARG_TRY(guide_draw_check(c, who));
+    if (c->pi_refstream) ARG_TRY(guide_refuse(c, (std::string(who) + " (pi_refstream)").c_str(), "the reference's stream draws its cells as the reference does"));
     if (c->pi_refstream) ARG_TRY(pi_refstream_check(c, (std::string(who) + " (pi_refstream)").c_str(), hyps_per_frame));  // before anything is enqueued
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c, /*keep_tail=*/c->pi_defer_tail != 0);

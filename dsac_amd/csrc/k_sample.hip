@@ -73,10 +73,108 @@ DM_INLINE void write_staged(const FrameDev& F, const double cv6[6], float* o) {
 // false: more than 32 candidates were needed (degenerate tiny maps).  The first four candidates are drawn as straight-line code (four
 // independent 64-bit mixes whose quarter-rate multiplies overlap); the loop with the reference's redraw-on-duplicate semantics only
 // runs when two of them coincide (probability ~6/P).
-DM_INLINE bool draw_set(const FrameDev& F, uint64_t key, uint32_t attempt, int32_t set4[4]) {
-    const uint32_t W = (uint32_t)F.W, H = (uint32_t)F.H;
+// The draw is a policy of the kernel body (template parameter DRAW): where candidate k of an attempt lands is all that differs between the uniform
+// builds and the guided ones (dsac_set_sampling_weights); the redraw loop, P3P, the 4-point check and the ballot are one text.
+//   bind(F, frame): called once per hypothesis, after select_frame;  empty(): no attempt of this frame can succeed (fewer than 4 cells with mass);
+//   first4(): candidates 0 .. 3 as straight-line code;  cell(): candidate k.
+struct DrawUniform {
+    static constexpr bool ZERO_UNDRAWN = false;
+    DM_INLINE void bind(const FrameDev&, int) {}
+    DM_INLINE bool empty() const { return false; }
+    DM_INLINE void first4(const FrameDev& F, uint64_t key, uint32_t attempt, int32_t set4[4]) const {
+        const uint32_t W = (uint32_t)F.W, H = (uint32_t)F.H;
 #pragma unroll
-    for (int j = 0; j < 4; j++) set4[j] = dm::draw_cell(key, attempt, (uint32_t)j, W, H);
+        for (int j = 0; j < 4; j++) set4[j] = dm::draw_cell(key, attempt, (uint32_t)j, W, H);
+    }
+    DM_INLINE int cell(const FrameDev& F, uint64_t key, uint32_t attempt, uint32_t k) const { return dm::draw_cell(key, attempt, k, (uint32_t)F.W, (uint32_t)F.H); }
+};
+
+// Guided draw: frame f's table C_f (inclusive uint64 sums of the quantised masses, k_guide_* below) turns the same 64-bit value v into
+// t = floor(v * T_f / 2^64) and the cell into the smallest p with C_f[p] > t.  A cell without mass has C[p] == C[p - 1] (or C[0] == 0) and is never the
+// smallest index above t.  The search is two branch-free upper bounds whose trip counts depend on P alone, so the four candidates of an attempt walk their
+// dependent loads side by side (as the four mix64 chains do): first over the frame's coarse level -- the last entry of every block of 2^shift cells, at most
+// GUIDE_COARSE_MAX values, which the workgroup copies into LDS once --, then over the one block that holds the cell (reads beyond P - 1 see C[P - 1] = T > t).
+// Measured on 640x480 frames (profiles/k1_guided_ab.txt has both forms): one search over the whole table, ~19 dependent global loads, made the guided K1
+// 27.7 / 98.2 / 150.0 us at 1 x 256 / 1 x 4 096 / 16 x 256 hypotheses; with the coarse level 9 global loads remain and it takes 28.5 / 91.8 / 134.0 us -- a
+// gain only where the tables (39 MB for 16 frames) no longer sit in L2, and still 2 - 2.9 x the uniform K1 (14.3 / 41.4 / 46.2 us): every step is a gather
+// of 64 x 4 scattered 8-byte entries per wave, and the waves of a CU share one address unit.  What would shorten it further is fewer, wider steps; not built.
+// A workgroup holds ONE frame's coarse level: the guided builds are one hypothesis per wave and one wave per workgroup.
+struct DrawGuided {
+    static constexpr bool ZERO_UNDRAWN = true;
+    const uint64_t* cdf;     // frames x P
+    const GuideMeta* meta;   // frames
+    const uint64_t* coarse;  // frames x K, K = ceil(P / 2^shift)
+    int shift;
+    const uint64_t* C;
+    const uint64_t* L;       // the frame's coarse level in LDS
+    uint64_t T;
+    int P, n, K;
+    DM_INLINE void bind(const FrameDev& F, int frame) {
+        __shared__ uint64_t s_coarse[GUIDE_COARSE_MAX];
+        P = F.P;
+        K = (P + (1 << shift) - 1) >> shift;
+        C = cdf + (size_t)frame * (size_t)P;
+        T = meta[frame].T;
+        n = meta[frame].n;
+        L = s_coarse;
+        if (n >= 4) {  // uniform over the workgroup
+            const uint64_t* cf = coarse + (size_t)frame * (size_t)K;
+            for (int i = threadIdx.x; i < K; i += blockDim.x) s_coarse[i] = cf[i];
+            __syncthreads();
+        }
+    }
+    DM_INLINE bool empty() const { return n < 4; }
+    DM_INLINE static uint64_t value(uint64_t key, uint32_t attempt, uint32_t k) { return dm::mix64(key + (((uint64_t)attempt << 16) | k)); }
+    // the cells of M values t < T
+    template <int M>
+    DM_INLINE void search(const uint64_t t[M], int32_t cell[M]) const {
+        uint32_t base[M];
+        uint64_t c[M];
+#pragma unroll
+        for (int j = 0; j < M; j++) base[j] = 0;
+        for (uint32_t len = (uint32_t)K; len > 1;) {
+            const uint32_t half = len >> 1;
+#pragma unroll
+            for (int j = 0; j < M; j++) c[j] = L[base[j] + half - 1];
+#pragma unroll
+            for (int j = 0; j < M; j++) base[j] += (c[j] <= t[j]) ? half : 0u;
+            len -= half;
+        }
+#pragma unroll
+        for (int j = 0; j < M; j++) c[j] = L[base[j]];
+#pragma unroll
+        for (int j = 0; j < M; j++) base[j] = (base[j] + ((c[j] <= t[j]) ? 1u : 0u)) << shift;  // L[K - 1] = T > t: the block index stays below K
+        const uint32_t last = (uint32_t)P - 1u;
+        for (uint32_t len = 1u << shift; len > 1;) {
+            const uint32_t half = len >> 1;
+#pragma unroll
+            for (int j = 0; j < M; j++) c[j] = C[min(base[j] + half - 1, last)];
+#pragma unroll
+            for (int j = 0; j < M; j++) base[j] += (c[j] <= t[j]) ? half : 0u;
+            len -= half;
+        }
+#pragma unroll
+        for (int j = 0; j < M; j++) c[j] = C[min(base[j], last)];
+#pragma unroll
+        for (int j = 0; j < M; j++) cell[j] = (int32_t)(base[j] + ((c[j] <= t[j]) ? 1u : 0u));
+    }
+    DM_INLINE void first4(const FrameDev&, uint64_t key, uint32_t attempt, int32_t set4[4]) const {
+        uint64_t t[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) t[j] = __umul64hi(value(key, attempt, (uint32_t)j), T);
+        search<4>(t, set4);
+    }
+    DM_INLINE int cell(const FrameDev&, uint64_t key, uint32_t attempt, uint32_t k) const {
+        const uint64_t t = __umul64hi(value(key, attempt, k), T);
+        int32_t p;
+        search<1>(&t, &p);
+        return p;
+    }
+};
+
+template <class DRAW>
+DM_INLINE bool draw_set(const DRAW& D, const FrameDev& F, uint64_t key, uint32_t attempt, int32_t set4[4]) {
+    D.first4(F, key, attempt, set4);
     const bool distinct = set4[0] != set4[1] && set4[0] != set4[2] && set4[0] != set4[3] && set4[1] != set4[2] && set4[1] != set4[3] && set4[2] != set4[3];
     if (distinct) return true;
     uint32_t k = 0;
@@ -84,13 +182,16 @@ DM_INLINE bool draw_set(const FrameDev& F, uint64_t key, uint32_t attempt, int32
     set4[0] = set4[1] = set4[2] = set4[3] = 0;
     while (cnt < 4) {
         if (k >= 32) return false;
-        const int idx = dm::draw_cell(key, attempt, k++, W, H);
+        const int idx = D.cell(F, key, attempt, k++);
         const bool dup = (cnt > 0 && set4[0] == idx) || (cnt > 1 && set4[1] == idx) || (cnt > 2 && set4[2] == idx);
         if (dup) continue;
         if (cnt == 0) set4[0] = idx; else if (cnt == 1) set4[1] = idx; else if (cnt == 2) set4[2] = idx; else set4[3] = idx;
         cnt++;
     }
     return true;
+}
+DM_INLINE bool draw_set(const FrameDev& F, uint64_t key, uint32_t attempt, int32_t set4[4]) {
+    return draw_set(DrawUniform{}, F, key, attempt, set4);
 }
 
 // One wave per hypothesis.  Lane l evaluates quartic root (l & 3) of attempt base + (l >> 2): 16 attempts
@@ -116,10 +217,15 @@ DM_INLINE bool draw_set(const FrameDev& F, uint64_t key, uint32_t attempt, int32
 // RL: lanes per attempt.  4 = one lane per quartic root (16 attempts per round and hypothesis); 1 = one lane per ATTEMPT, its roots in
 // sequence (64 attempts per round): a round is longer (set-up + up to 4 root evaluations instead of one) but four times as wide, so a
 // hypothesis rarely needs a second one -- the launch time is the slowest hypothesis' number of rounds.
-template <int WPB, int HPW, bool HORN = false, int MINW = 1, int RL = 4>
+// DRAW: the draw policy (DrawUniform / DrawGuided above), TAB...: what it is built from -- nothing for the uniform builds, whose argument list is the one they
+// always had, and the table (cdf, meta, coarse level, its shift) as the guided builds' own kernel arguments: FrameDev, an argument of every kernel of the library, does not
+// know about the table.  The kernel itself is the shared body: behind a wrapper function the uniform builds come out re-allocated (246 against 252 registers).
+// The guided builds hold one hypothesis per wave (HPW = 1): the frame, and with it the table, is wave-uniform.
+template <int WPB, int HPW, bool HORN = false, int MINW = 1, int RL = 4, class DRAW = DrawUniform, class... TAB>
 __global__ __launch_bounds__(64 * WPB, MINW) void k_sample(int N, uint64_t seed, FrameDev F, int thr_int, int max_tries, double* __restrict__ poses,
                                                      int32_t* __restrict__ sets_out, uint8_t* __restrict__ ok, float* __restrict__ staged, int prio,
-                                                     int Nf) {
+                                                     int Nf, TAB... tab) {
+    DRAW D{tab...};
     if (prio >= 3) __builtin_amdgcn_s_setprio(3);
     else if (prio == 2) __builtin_amdgcn_s_setprio(2);
     else if (prio == 1) __builtin_amdgcn_s_setprio(1);
@@ -139,12 +245,24 @@ __global__ __launch_bounds__(64 * WPB, MINW) void k_sample(int N, uint64_t seed,
     else { F.cams = nullptr; select_frame(F, frame); }
     const uint64_t key = dm::hyp_key(seed + (uint64_t)frame * (uint64_t)F.seed_stride, (uint32_t)(hc - frame * Nf));
     const dm::Cam K = make_cam(F);
+    D.bind(F, frame);
+    if (D.empty()) {  // guided, fewer than four cells with mass: no attempt can succeed, and max_tries is not walked
+        if (!done && sl == 0) {
+#pragma unroll
+            for (int kk = 0; kk < 6; kk++) poses[(size_t)h * 6 + kk] = 0.0;
+#pragma unroll
+            for (int kk = 0; kk < 4; kk++) sets_out[(size_t)h * 4 + kk] = 0;
+            ok[h] = 0;
+            if (staged) { const double z6[6] = {0, 0, 0, 0, 0, 0}; write_staged(F, z6, staged + (size_t)h * POSE_STRIDE); }
+        }
+        return;
+    }
     for (int base = 0; base < max_tries; base += APR) {
         if (__ballot(!done) == 0ull) return;
         const uint32_t attempt = (uint32_t)(base + sl / RL);
         int32_t set4[4];
         bool live = !done && (int)attempt < max_tries;
-        if (live) live = draw_set(F, key, attempt, set4);
+        if (live) live = draw_set(D, F, key, attempt, set4);
         float X[4][3], uv[4][2];
         double Rc[9], Tc[3], reproj = 0;
         bool cand = false;
@@ -214,7 +332,8 @@ __global__ __launch_bounds__(64 * WPB, MINW) void k_sample(int N, uint64_t seed,
     // no accepted attempt: zero pose, ok = 0; sets_out reports the last attempt's set
     if (!done && sl == 0) {
         int32_t set4[4];
-        draw_set(F, key, (uint32_t)(max_tries - 1), set4);
+        const bool drawn = draw_set(D, F, key, (uint32_t)(max_tries - 1), set4);
+        if (DRAW::ZERO_UNDRAWN && !drawn) set4[0] = set4[1] = set4[2] = set4[3] = 0;  // guided: a last attempt that ran out of candidates reports no set
 #pragma unroll
         for (int kk = 0; kk < 6; kk++) poses[(size_t)h * 6 + kk] = 0.0;
 #pragma unroll
@@ -496,6 +615,220 @@ __global__ __launch_bounds__(64) void k_eval_sets(int N, const int32_t* __restri
     }
 }
 
+// --------------------------------------------------------------------------------------------------
+// Guided sampling: the table build (dsac_set_sampling_weights) and the score-function gradient (dsac_sampling_weights_backward).
+// A cell is valid when its weight is finite and > 0; its mass is m_p = (uint64) floor((double) w_p / (double) wmax_f * 2^24), wmax_f the frame's largest
+// valid weight -- the heaviest cell has 2^24 units, a weight below wmax_f * 2^-24 has none.  C_f[p] = sum of m_q, q <= p, in uint64: integer sums, so the
+// table does not depend on how the scan is cut into tiles.  Grid (tiles of GUIDE_TILE cells, frames), 256 lanes x 4 consecutive cells.
+// --------------------------------------------------------------------------------------------------
+constexpr int GUIDE_THREADS = 256;
+static_assert(GUIDE_TILE == 4 * GUIDE_THREADS, "a lane of the table build owns four consecutive cells");
+
+DM_INLINE bool guide_valid(float w) { return w > 0.f && w < __builtin_inff(); }  // NaN fails both
+DM_INLINE uint64_t guide_mass(float w, float wmax) {
+    if (!guide_valid(w) || !(wmax > 0.f)) return 0ull;
+    return (uint64_t)floor((double)w / (double)wmax * 16777216.0);
+}
+// inclusive scan over the workgroup's 256 lanes (Hillis-Steele in LDS); s[255] holds the total afterwards
+DM_INLINE uint64_t guide_scan256(uint64_t v, uint64_t* s, int tid) {
+    s[tid] = v;
+    __syncthreads();
+    for (int d = 1; d < GUIDE_THREADS; d <<= 1) {
+        const uint64_t a = tid >= d ? s[tid - d] : 0ull;
+        __syncthreads();
+        v += a;
+        s[tid] = v;
+        __syncthreads();
+    }
+    return v;
+}
+
+// (1) the context's copy of the weights and the frame's valid maximum (meta zeroed beforehand)
+__global__ __launch_bounds__(GUIDE_THREADS) void k_guide_max(int P, const float* __restrict__ w, float* __restrict__ w_copy, GuideMeta* __restrict__ meta) {
+    __shared__ uint32_t s_max[GUIDE_THREADS / 64];
+    const int f = blockIdx.y, tid = threadIdx.x;
+    const size_t row = (size_t)f * (size_t)P;
+    const long long p0 = (long long)blockIdx.x * GUIDE_TILE + 4 * tid;
+    uint32_t m = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        if (p0 + i >= P) continue;
+        const float v = w[row + p0 + i];
+        w_copy[row + p0 + i] = v;
+        if (guide_valid(v)) m = max(m, __float_as_uint(v));
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
+    if ((tid & 63) == 0) s_max[tid >> 6] = m;
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 1; k < GUIDE_THREADS / 64; k++) m = max(m, s_max[k]);
+        if (m) atomicMax(&meta[f].wmax, m);
+    }
+}
+
+// (2) per tile: its mass, its valid-weight sum (a fixed tree: S does not depend on scheduling) and its count of cells with mass
+__global__ __launch_bounds__(GUIDE_THREADS) void k_guide_tile_sums(int P, const float* __restrict__ w_copy, const GuideMeta* __restrict__ meta,
+                                                                   uint64_t* __restrict__ t_mass, double* __restrict__ t_S, uint64_t* __restrict__ t_n) {
+    __shared__ uint64_t s_m[GUIDE_THREADS], s_n[GUIDE_THREADS];
+    __shared__ double s_S[GUIDE_THREADS];
+    const int f = blockIdx.y, tid = threadIdx.x;
+    const size_t row = (size_t)f * (size_t)P;
+    const long long p0 = (long long)blockIdx.x * GUIDE_TILE + 4 * tid;
+    const float wmax = __uint_as_float(meta[f].wmax);
+    uint64_t m = 0, n = 0;
+    double S = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        if (p0 + i >= P) continue;
+        const float v = w_copy[row + p0 + i];
+        const uint64_t mi = guide_mass(v, wmax);
+        m += mi;
+        n += mi ? 1ull : 0ull;
+        if (guide_valid(v)) S += (double)v;
+    }
+    s_m[tid] = m; s_n[tid] = n; s_S[tid] = S;
+    __syncthreads();
+    for (int d = GUIDE_THREADS / 2; d >= 1; d >>= 1) {
+        if (tid < d) { s_m[tid] += s_m[tid + d]; s_n[tid] += s_n[tid + d]; s_S[tid] += s_S[tid + d]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const size_t t = (size_t)f * gridDim.x + blockIdx.x;
+        t_mass[t] = s_m[0]; t_S[t] = s_S[0]; t_n[t] = s_n[0];
+    }
+}
+
+// (3) one workgroup per frame: the tile masses become the tiles' offsets (exclusive scan, 256 tiles at a time with a carry); T, n and S are recorded
+__global__ __launch_bounds__(GUIDE_THREADS) void k_guide_tile_scan(int tiles, uint64_t* __restrict__ t_mass, const double* __restrict__ t_S,
+                                                                   const uint64_t* __restrict__ t_n, GuideMeta* __restrict__ meta) {
+    __shared__ uint64_t s[GUIDE_THREADS], s_n[GUIDE_THREADS];
+    __shared__ double s_S[GUIDE_THREADS];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const size_t row = (size_t)f * (size_t)tiles;
+    uint64_t carry = 0, n = 0;
+    double S = 0.0;
+    for (int base = 0; base < tiles; base += GUIDE_THREADS) {
+        const int t = base + tid;
+        const uint64_t v = t < tiles ? t_mass[row + t] : 0ull;
+        if (t < tiles) { n += t_n[row + t]; S += t_S[row + t]; }
+        const uint64_t incl = guide_scan256(v, s, tid);
+        if (t < tiles) t_mass[row + t] = carry + incl - v;
+        carry += s[GUIDE_THREADS - 1];
+        __syncthreads();  // s is rewritten by the next chunk
+    }
+    s_n[tid] = n; s_S[tid] = S;
+    __syncthreads();
+    for (int d = GUIDE_THREADS / 2; d >= 1; d >>= 1) {
+        if (tid < d) { s_n[tid] += s_n[tid + d]; s_S[tid] += s_S[tid + d]; }
+        __syncthreads();
+    }
+    if (tid == 0) { meta[f].T = carry; meta[f].n = (int32_t)min(s_n[0], (uint64_t)0x7fffffff); meta[f].S = s_S[0]; }
+}
+
+// (4) the table: the tile's offset + the inclusive scan inside the tile; the coarse level takes the last entry of every block of 2^shift cells
+__global__ __launch_bounds__(GUIDE_THREADS) void k_guide_scan(int P, const float* __restrict__ w_copy, const GuideMeta* __restrict__ meta,
+                                                              const uint64_t* __restrict__ t_off, uint64_t* __restrict__ cdf, uint64_t* __restrict__ coarse,
+                                                              int shift) {
+    __shared__ uint64_t s[GUIDE_THREADS];
+    const int f = blockIdx.y, tid = threadIdx.x;
+    const size_t row = (size_t)f * (size_t)P;
+    const long long p0 = (long long)blockIdx.x * GUIDE_TILE + 4 * tid;
+    const float wmax = __uint_as_float(meta[f].wmax);
+    uint64_t m[4], sum = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        m[i] = (p0 + i < P) ? guide_mass(w_copy[row + p0 + i], wmax) : 0ull;
+        sum += m[i];
+    }
+    uint64_t run = t_off[(size_t)f * gridDim.x + blockIdx.x] + guide_scan256(sum, s, tid) - sum;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        run += m[i];
+        const long long p = p0 + i;
+        if (p < P) {
+            cdf[row + p] = run;
+            if (((p + 1) & ((1ll << shift) - 1)) == 0 || p == P - 1) coarse[(size_t)f * (size_t)guide_coarse_entries(P) + (size_t)(p >> shift)] = run;
+        }
+    }
+}
+
+hipError_t guide_build(hipStream_t st, int frames, int P, const float* w, float* w_copy, uint64_t* cdf, uint64_t* coarse, GuideMeta* meta, void* scratch) {
+    const int tiles = guide_tiles(P);
+    const size_t nt = (size_t)frames * tiles;
+    uint64_t* t_mass = static_cast<uint64_t*>(scratch);
+    double* t_S = reinterpret_cast<double*>(t_mass + nt);
+    uint64_t* t_n = reinterpret_cast<uint64_t*>(t_S + nt);
+    hipError_t e = hipMemsetAsync(meta, 0, (size_t)frames * sizeof(GuideMeta), st);
+    if (e != hipSuccess) return e;
+    const dim3 grid((unsigned)tiles, (unsigned)frames);
+    hipLaunchKernelGGL(k_guide_max, grid, dim3(GUIDE_THREADS), 0, st, P, w, w_copy, meta);
+    hipLaunchKernelGGL(k_guide_tile_sums, grid, dim3(GUIDE_THREADS), 0, st, P, w_copy, meta, t_mass, t_S, t_n);
+    hipLaunchKernelGGL(k_guide_tile_scan, dim3((unsigned)frames), dim3(GUIDE_THREADS), 0, st, tiles, t_mass, t_S, t_n, meta);
+    hipLaunchKernelGGL(k_guide_scan, grid, dim3(GUIDE_THREADS), 0, st, P, w_copy, meta, t_mass, cdf, coarse, guide_coarse_shift(P));
+    return hipGetLastError();
+}
+
+// The score-function gradient of guided training, one launch.  Workgroup (b, f) forms G_f = sum of g[h] over the accepted hypotheses of frame f -- in
+// double-double, so that every workgroup holds the same, correctly rounded value whatever signs g carries --, adds the uniform term -4 G_f / S_f to the valid
+// cells of its tile and scatters g[h] / w_c to the set cells of its share of the hypotheses.  Both go through fp64 atomics: a cell may receive them from
+// several workgroups at once.
+DM_INLINE void guide_two_sum(double& hi, double& lo, double b_hi, double b_lo) {
+    const double s = hi + b_hi;
+    const double bb = s - hi;
+    const double err = (hi - (s - bb)) + (b_hi - bb);
+    hi = s;
+    lo += err + b_lo;
+}
+__global__ __launch_bounds__(GUIDE_THREADS) void k_guide_backward(int P, int Nf, const float* __restrict__ w_copy, const GuideMeta* __restrict__ meta,
+                                                                  const int32_t* __restrict__ sets, const uint8_t* __restrict__ ok, const double* __restrict__ g,
+                                                                  double* __restrict__ grad_w) {
+    __shared__ double s_hi[GUIDE_THREADS], s_lo[GUIDE_THREADS];
+    const int f = blockIdx.y, tid = threadIdx.x;
+    const size_t row = (size_t)f * (size_t)P, h0 = (size_t)f * (size_t)Nf;
+    double hi = 0.0, lo = 0.0;
+    for (int j = tid; j < Nf; j += GUIDE_THREADS)
+        if (ok[h0 + j]) guide_two_sum(hi, lo, g[h0 + j], 0.0);
+    s_hi[tid] = hi; s_lo[tid] = lo;
+    __syncthreads();
+    for (int d = GUIDE_THREADS / 2; d >= 1; d >>= 1) {
+        if (tid < d) {
+            double a = s_hi[tid], b = s_lo[tid];
+            guide_two_sum(a, b, s_hi[tid + d], s_lo[tid + d]);
+            s_hi[tid] = a; s_lo[tid] = b;
+        }
+        __syncthreads();
+    }
+    const double G = s_hi[0] + s_lo[0];
+    const double S = meta[f].S;
+    const double uni = -4.0 * G / S;
+    const long long p0 = (long long)blockIdx.x * GUIDE_TILE + 4 * tid;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        if (p0 + i >= P) continue;
+        if (guide_valid(w_copy[row + p0 + i]) && G != 0.0) atomicAdd(&grad_w[row + p0 + i], uni);
+    }
+    for (int j = blockIdx.x * GUIDE_THREADS + tid; j < Nf; j += gridDim.x * GUIDE_THREADS) {
+        if (!ok[h0 + j]) continue;
+        const double gh = g[h0 + j];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int p = sets[(h0 + j) * 4 + k];
+            if (p < 0 || p >= P) continue;
+            const float wp = w_copy[row + p];
+            if (guide_valid(wp)) atomicAdd(&grad_w[row + p], gh / (double)wp);
+        }
+    }
+}
+
+hipError_t guide_backward(hipStream_t st, int frames, int P, int Nf, const float* w_copy, const GuideMeta* meta, const int32_t* sets, const uint8_t* ok,
+                          const double* g, double* grad_w) {
+    if (frames <= 0 || P <= 0 || Nf <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_guide_backward, dim3((unsigned)guide_tiles(P), (unsigned)frames), dim3(GUIDE_THREADS), 0, st, P, Nf, w_copy, meta, sets, ok, g, grad_w);
+    return hipGetLastError();
+}
+
 hipError_t sample(hipStream_t st, int N, uint64_t seed, const int32_t* sets_in, const FrameDev& F, int thr_int, int max_tries, double* poses,
                   int32_t* sets_out, uint8_t* ok, float* staged, int Nf, const K1Opts& o) {
     if (N <= 0) return hipSuccess;
@@ -503,6 +836,13 @@ hipError_t sample(hipStream_t st, int N, uint64_t seed, const int32_t* sets_in, 
     if (sets_in) {
         if (o.horn) hipLaunchKernelGGL(k_eval_sets<true>, dim3((N + 63) / 64), dim3(64), 0, st, N, sets_in, F, thr_int, poses, sets_out, ok, staged);
         else hipLaunchKernelGGL(k_eval_sets<false>, dim3((N + 63) / 64), dim3(64), 0, st, N, sets_in, F, thr_int, poses, sets_out, ok, staged);
+    } else if (o.guide_cdf) {
+        // guided: the one-lane-per-attempt, one-hypothesis-per-wave build serves every N, frame batches and camera tables; "k1_horn" has no guided build
+        // (the API refuses it by name).  At a register budget for two waves per SIMD (MINW = 2): 256 registers and no scratch, where the budget for one
+        // lets the allocator take 258 and halves the occupancy of the uniform build it stands in for (252)
+        if (o.horn || !o.guide_meta || !o.guide_coarse) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((k_sample<1, 1, false, 2, 1, DrawGuided, const uint64_t*, const GuideMeta*, const uint64_t*, int>), dim3(N), dim3(64), 0, st, N, seed, F, thr_int, max_tries, poses, sets_out, ok, staged, o.prio,
+                           Nf > 0 ? Nf : N, o.guide_cdf, o.guide_meta, o.guide_coarse, guide_coarse_shift(F.P));
     } else {
         const int wpb = o.wpb, prio = o.prio;
         int H2 = o.hpw > 0 ? o.hpw : 1;  // see the measurement in the kernel's comment

@@ -113,6 +113,33 @@ hipError_t softmax(hipStream_t st, int N, const double* scores, double scale, do
 // what a single-frame call with seed + frame would draw.
 // Launch knobs of K1 (context state like K2Opts): waves per workgroup (DSAC_K1_WPB in {1, 4, 8}), wave priority (DSAC_K1_PRIO 0..3),
 // hypotheses per wave (DSAC_K1_HPW in {1, 2, 4}), OpenCV's Jacobi sweeps for the alignment of the P3P triangle instead of the closed form (DSAC_K1_HORN).
+// Guided sampling: what the table build records per frame next to the table itself.
+struct GuideMeta {
+    uint64_t T;      // total mass = C_f[P - 1]
+    double S;        // sum of the valid weights (double), for the score-function gradient
+    uint32_t wmax;   // bits of the largest valid weight (positive floats order like their bits), 0 = no valid cell
+    int32_t n;       // cells with mass > 0
+};
+// the coarse level of a frame's table: the last entry of every block of 2^shift cells, the smallest shift >= 8 that leaves at most GUIDE_COARSE_MAX blocks
+// (K1 keeps them in LDS: 16 KB; 640x480 is 1 200 blocks of 256)
+constexpr int GUIDE_COARSE_MAX = 2048;
+__host__ __device__ inline int guide_coarse_shift(int P) {
+    int s = 8;
+    while (((P + (1 << s) - 1) >> s) > GUIDE_COARSE_MAX) s++;
+    return s;
+}
+__host__ __device__ inline int guide_coarse_entries(int P) { const int s = guide_coarse_shift(P); return (P + (1 << s) - 1) >> s; }
+constexpr int GUIDE_TILE = 1024;  // cells per workgroup of the table build (256 lanes x 4 consecutive cells)
+inline int guide_tiles(int P) { return (P + GUIDE_TILE - 1) / GUIDE_TILE; }
+// scratch of a build: per frame and tile the tile's mass (uint64), its valid-weight sum (double) and its count of cells with mass (uint64)
+inline size_t guide_scratch_bytes(int frames, int P) { return (size_t)frames * guide_tiles(P) * 24; }
+// The table build, a few small launches on st: the valid maximum per frame, the masses m_p = floor((double) w_p / (double) wmax * 2^24) and their tile sums, the
+// scan of the tile sums (which records T, n and S), the inclusive uint64 scan.  w: frames x P floats (device); w_copy: the context's copy of them (the build's
+// first launch writes it; every later launch reads the copy, so the caller may overwrite w in stream order)
+hipError_t guide_build(hipStream_t st, int frames, int P, const float* w, float* w_copy, uint64_t* cdf, uint64_t* coarse, GuideMeta* meta, void* scratch);
+// grad_w[f * P + p] += sum over the accepted hypotheses h of frame f of g[h] * ([p in set_h] / w_p - 4 / S_f), valid cells only; one launch
+hipError_t guide_backward(hipStream_t st, int frames, int P, int Nf, const float* w_copy, const GuideMeta* meta, const int32_t* sets, const uint8_t* ok,
+                          const double* g, double* grad_w);
 struct K1Opts {
     int wpb = 1, prio = 3, hpw = 1, minw = 1;  // minw: minimum waves per SIMD of the register allocation (DSAC_K1_MINW)
     bool share_always = false;  // share beyond 1024 hypotheses as well (DSAC_K1_SHARE < 0)
@@ -120,6 +147,11 @@ struct K1Opts {
     bool horn = false;
     int wide = -1;  // waves per hypothesis of the one-lane-per-attempt form for few hypotheses: -1 auto (2 up to 512 hypotheses), 0 off, 2, 4 (4: up to 256) (DSAC_K1_WIDE)
     int rl = 1;  // lanes per attempt: 4 = one per quartic root, 1 = one lane per attempt with its roots in sequence (DSAC_K1_RL)
+    // guided sampling (dsac_set_sampling_weights): the context's table while weights are active, else nullptr.  sample() then launches the guided build
+    // (one lane per attempt, one hypothesis per wave) whatever the form knobs above say -- they never change a result -- and given sets ignore it
+    const uint64_t* guide_cdf = nullptr;   // frames x P inclusive sums of the quantised masses
+    const GuideMeta* guide_meta = nullptr; // frames
+    const uint64_t* guide_coarse = nullptr; // frames x guide_coarse_entries(P): the table's coarse level
 };
 hipError_t sample(hipStream_t st, int N, uint64_t seed, const int32_t* sets_in, const FrameDev& F, int thr_int, int max_tries,
                   double* poses, int32_t* sets_out, uint8_t* ok, float* staged_or_null = nullptr, int Nf = 0,

@@ -193,6 +193,44 @@ class Engine:
         self.H, self.W, self.P, self.frames = int(H), int(W), int(H) * int(W), F
         self._keep = (xyz, uv) if borrow else None
 
+    # ---- guided sampling (dsac_set_sampling_weights) ------------------------------------------------------------------------------------
+    def set_sampling_weights(self, w):
+        """Per-cell sampling weights for the frame(s) currently set: F x H*W (any shape with that many values), numpy or torch, any float dtype,
+        converted to float32; None clears them.  While they are active every call that draws minimal sets draws cell p of frame f with probability
+        m_p / T_f (include/dsac_hip.h has the rule); set_frame / set_frames clear them.  A torch device tensor only enqueues the table build."""
+        if w is None:
+            check(self._ctx, lib.dsac_set_sampling_weights(self._ctx, None))
+            return
+        if hasattr(w, "data_ptr"):  # torch
+            import torch
+            w = w.detach().to(torch.float32).contiguous()
+        else:
+            w = np.ascontiguousarray(np.asarray(w), dtype=np.float32)
+        n = int(w.numel()) if hasattr(w, "numel") else int(w.size)
+        cells = getattr(self, "frames", 1) * self.P
+        if n != cells:
+            raise ValueError("dsac_amd: sampling weights hold %d values, the frames currently set have %d cells" % (n, cells))
+        check(self._ctx, lib.dsac_set_sampling_weights(self._ctx, ptr(w)))
+        self._keep_w = w  # a device tensor is read in stream order, after this call has returned
+
+    def sampling_table(self, out=None):
+        """The table the draw uses (dsac_sampling_table): F x H*W uint64, the inclusive sums of the quantised masses of every frame.  out: a preallocated
+        buffer (numpy uint64, or a torch tensor of 8-byte integers), else a fresh numpy array."""
+        if out is None:
+            out = np.zeros((getattr(self, "frames", 1), self.P), np.uint64)
+        check(self._ctx, lib.dsac_sampling_table(self._ctx, ptr(out)))
+        return out
+
+    def sampling_weights_backward(self, sets, ok, g, grad=None):
+        """The score-function gradient of guided training (dsac_sampling_weights_backward): grad[f, p] += sum over the accepted hypotheses h of frame f of
+        g[h] * ([p in set_h] / w_p - 4 / S_f) for every valid cell.  sets F*N x 4 int32, ok F*N uint8, g F*N float64; grad F x H*W float64 is accumulated
+        into (fresh zeros without it) and returned."""
+        sets, ok, g = _np(sets, np.int32), _np(ok, np.uint8), _np(g, np.float64)
+        if grad is None:
+            grad = np.zeros((getattr(self, "frames", 1), self.P))
+        check(self._ctx, lib.dsac_sampling_weights_backward(self._ctx, int(ok.shape[0]), ptr(sets), ptr(ok), ptr(g), ptr(grad)))
+        return grad
+
     def scoreHypothesesFrames(self, hyps_per_frame, seed=1305, thr=10.0, max_tries=1 << 20, clamp=CNN_OBJ_MAXINPUT, tau=10.0, beta=0.5, scale=0.1,
                               err=None, out=None):
         """K1 + K2 + K3 for every frame of the batch in three launches; frame f uses the random stream of seed + f.

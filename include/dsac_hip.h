@@ -283,6 +283,47 @@ DSAC_API int dsac_score_hypotheses_frames(dsac_ctx* ctx, int hyps_per_frame, uin
 DSAC_API int dsac_sample(dsac_ctx* ctx, int N, uint64_t seed, const int32_t* sets_or_null, float thr, int max_tries, double* poses,
                 int32_t* sets_out, uint8_t* ok);
 
+/* GUIDED SAMPLING: K1 draws its minimal sets from per-cell weights -- "these cells are invalid" (the border after an augmentation, masked depth), "these
+ * cells are unreliable" (a learned confidence, neural-guided DSAC), or a set of cells kept out of the minimal sets while scoring and refinement still use them.
+ * weights: frames x H*W float32, one value per cell of the frame(s) currently set, host or device pointer.  With a device pointer the call only enqueues the
+ * table build (a few small launches) on the context's stream and returns; the build's first launch copies the weights, so the caller may overwrite the buffer
+ * afterwards in stream order.  The context owns the table (frames x H*W uint64 and per frame T, n, S below) and a device copy of the weights; both grow like
+ * other scratch.  NULL clears the weights, and so do dsac_set_frame, dsac_set_frames and dsac_set_frames_cams (as they reset "frame_cams");
+ * dsac_get_option("sampling_weights") reads 1 while weights are active.  Without a frame: DSAC_ERR_NO_FRAME.
+ * The draw, for frame f:
+ *   - a cell is VALID when its weight is finite and > 0; wmax_f is the largest valid weight;
+ *   - its mass is m_p = (uint64) floor((double) w_p / (double) wmax_f * 2^24), 0 for an invalid cell: the heaviest cell has 2^24 units, and a positive weight
+ *     below wmax_f * 2^-24 has mass 0 and is NEVER drawn (24 bits of dynamic range per frame);
+ *   - C_f[p] = sum of m_q over q <= p (inclusive, uint64), T_f = C_f[H*W - 1], n_f = the number of cells with mass, S_f = the double sum of the valid weights;
+ *   - candidate k of attempt a of hypothesis h takes the same 64-bit value as the uniform draw, v = mix64(key(h) + ((a << 16) | k)), forms
+ *     t = floor(v * T_f / 2^64) and draws the smallest cell p with C_f[p] > t, i.e. cell p with probability m_p / T_f.
+ *   Everything else is the uniform K1: a duplicate is redrawn with the next k, more than 32 candidates fail the attempt, the first accepted attempt in
+ *   a = 0, 1, 2, ... wins, key(h), seed + f * seed_stride, the P3P solve and the 4-point check are unchanged.
+ *   Rows with ok = 0: (1) n_f < 4 -- all-zero, all-NaN, negative weights -- no attempt can succeed: every hypothesis of that frame returns at once (max_tries
+ *   is not walked) with a zero pose and sets_out = (0, 0, 0, 0); (2) attempts exhausted: a zero pose, and sets_out = the set of attempt max_tries - 1 if that
+ *   attempt drew four distinct cells, else four zeros.
+ * While weights are active EVERY call that draws from the counter stream draws by this rule -- dsac_sample and dsac_score_hypotheses without given sets,
+ * dsac_score_hypotheses_frames, dsac_process_images, dsac_process_images_begin and its _f16 / _bf16 twins -- with a frame batch, per-frame cameras,
+ * "seed_stride" and every "pi_defer_tail" mode.  Given sets, dsac_dpnp and everything downstream of K1 are untouched.  K1's form knobs ("k1_rl", "k1_share",
+ * "k1_wide", ...) never change a result; with weights the launcher takes the guided build (one lane per attempt, one hypothesis per wave) whatever they say.
+ * Refused by name with DSAC_ERR_INVALID while weights are active, nothing enqueued:
+ *   - dsac_sample_refstream, dsac_sample_refstream_frames and "pi_refstream" = 1: their stream is the reference's;
+ *   - dsac_sample_ahead: a slot keeps its frame across later set calls, the table has no such lifetime (the camera table's reason);
+ *   - "k1_horn" = 1 in any call that draws: the Jacobi-sweep alignment has no guided build.
+ * Not part of this: the C++ host shim and the driver programs; shard.ShardRunner; bench.py; e2e.ScoredFrameBatch; the reference stream and the pipelined
+ * pair; weighting the soft-inlier score itself. */
+DSAC_API int dsac_set_sampling_weights(dsac_ctx* ctx, const float* weights_or_null);
+/* The table as built: cdf_out receives frames x H*W uint64 (C_f of every frame; host or device pointer) -- for tests and for a caller who wants to see what
+ * was quantised.  DSAC_ERR_INVALID without active weights. */
+DSAC_API int dsac_sampling_table(dsac_ctx* ctx, uint64_t* cdf_out);
+/* The score-function gradient of guided training: the gradient of sum_h g[h] * log p(set_h) under the with-replacement model p(set) = prod_k w_{c_k} / S_f,
+ * with respect to the real-valued weights (not the quantised masses).  For every valid cell p of frame f
+ *   grad_w[f * H*W + p] += sum over the hypotheses h of frame f with ok[h] of g[h] * ([p in set_h] / w_p - 4 / S_f);
+ * invalid cells receive nothing.  grad_w is frames x H*W doubles and is ACCUMULATED into, like grad_xyz.  On a frame batch N = frames x hypotheses per
+ * frame, frame-major.  One launch (fp64 atomics for the set cells); the uniform term uses one correctly rounded sum of the accepted g per frame.  Needs active
+ * weights (it reads their values from the context's copy): DSAC_ERR_INVALID otherwise. */
+DSAC_API int dsac_sampling_weights_backward(dsac_ctx* ctx, int N, const int32_t* sets, const uint8_t* ok, const double* g, double* grad_w);
+
 /* K1 in the REFERENCE'S OWN random stream (round 6).  The reference draws from ThreadRand (core/thread_rand.cpp:40-69): one std::mt19937(seed + t) per
  * OpenMP thread t, irand(0, n) = std::uniform_int_distribution<int>(0, n - 1) (:59-69, :95-98), x before y, a re-draw for a cell already in the set, a new
  * attempt after a failed P3P / re-projection check, no cap (core/cnn_softam.h:1010-1060); `#pragma omp parallel for` (static schedule) gives thread t the
