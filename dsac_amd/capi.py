@@ -52,6 +52,7 @@ EXPORTS = [
     "dsac_score_backward_bf16", "dsac_soft_score_derr_bf16",
     "dsac_set_frames_cams",
     "dsac_set_sampling_weights", "dsac_sampling_table", "dsac_sampling_weights_backward",
+    "dsac_refine_gn_backward",
 ]
 
 # enum dsac_k2_form (dsac_get_option "k2_form_last") and the DSAC_K2_WHY_* bits ("k2_form_why_last")
@@ -136,7 +137,8 @@ def _load():
     lib.dsac_gather_rows.argtypes = [vp, vp, vp, C.c_size_t, i32, vp]
     lib.dsac_process_images.argtypes = [vp, i32, u64, f32, i32, f32, f32, f32, f64, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.dsac_refine_fd_sets_frames.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, f32, vp, f32, f32, vp, vp, vp, i32, vp]
-    lib.dsac_loss_batch_frames.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    lib.dsac_refine_gn_backward.argtypes = [vp, i32, vp, vp, vp, i32, vp, i32, i32, f32, vp, vp, vp, vp, vp, vp]
+    lib.dsac_loss_batch_frames.argtypes =[vp, i32, i32, vp, vp, vp, vp]
     lib.dsac_select_frames.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.dsac_soft_score_derr.argtypes = [vp, i32, vp, vp, f32, f32, f32, vp]
     lib.dsac_soft_score_derr_f16.argtypes = [vp, i32, vp, vp, f32, f32, f32, vp]

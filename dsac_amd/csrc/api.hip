@@ -1899,6 +1899,46 @@ int dsac_refine_fd_sets_frames(dsac_ctx* c, int M, const int32_t* sets, const in
                                  J_obj, cap, n_obj);
 }
 
+int dsac_refine_gn_backward(dsac_ctx* c, int B, const double* ref_poses, const int32_t* frame_of_or_null, const int32_t* perm, int steps,
+                            const int32_t* rows_or_null, int max_inl, int min_inl, float thr, const double* dL_jp6_or_null, const double* coef_or_null,
+                            double* grad_xyz_or_null, int32_t* cells_or_null, double* J_obj_or_null, int32_t* n_out_or_null) {
+    const char* who = "dsac_refine_gn_backward";
+    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "%s: ctx is NULL", who);
+    if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "%s: no frame set", who);
+    const int frames = c->F.frames > 1 ? c->F.frames : 1;
+    if (B < 1 || steps < 1 || !perm || !ref_poses) return fail(c, DSAC_ERR_INVALID, "%s: need B >= 1, steps >= 1, perm and ref_poses", who);
+    if (max_inl < 1 || max_inl > 256 || min_inl < 3) return fail(c, DSAC_ERR_INVALID, "%s: need 1 <= max_inl <= 256 (got %d) and min_inl >= 3 (got %d)", who, max_inl, min_inl);
+    if (!grad_xyz_or_null != !dL_jp6_or_null) return fail(c, DSAC_ERR_INVALID, "%s: grad_xyz and dL go together", who);
+    if (J_obj_or_null && !cells_or_null) return fail(c, DSAC_ERR_INVALID, "%s: J_obj without cells (which cells would its rows belong to?)", who);
+    if (!grad_xyz_or_null && !J_obj_or_null) return fail(c, DSAC_ERR_INVALID, "%s: nothing requested: give grad_xyz (with dL) or cells and J_obj", who);
+    if (frames > 1 && !frame_of_or_null && B % frames != 0)
+        return fail(c, DSAC_ERR_INVALID, "%s: with a frame batch B must be frames x (problems per frame) -- or give every problem its frame (frame_of)", who);
+    if (rows_or_null && !is_device_ptr(rows_or_null, c))
+        for (int b = 0; b < B; b++)
+            if (rows_or_null[b] < 0 || rows_or_null[b] >= steps) return fail(c, DSAC_ERR_INVALID, "%s: rows[%d] = %d is not a row of perm (%d steps)", who, b, rows_or_null[b], steps);
+    HIP_TRY(c, hipSetDevice(c->device));
+    begin_call(c);
+    const size_t P = (size_t)c->F.P;
+    const double *d_poses, *d_dL, *d_coef;
+    const int32_t *d_fof, *d_perm, *d_rows;
+    double *d_grad, *d_J;
+    int32_t *d_cells, *d_n;
+    ARG_TRY(in_arg(c, ref_poses, (size_t)B * 6, &d_poses));
+    ARG_TRY(in_arg(c, frames > 1 ? frame_of_or_null : nullptr, (size_t)B, &d_fof));
+    ARG_TRY(in_arg(c, perm, (size_t)steps * P, &d_perm));
+    ARG_TRY(in_arg(c, rows_or_null, (size_t)B, &d_rows));
+    ARG_TRY(in_arg(c, dL_jp6_or_null, (size_t)B * 6, &d_dL));
+    ARG_TRY(in_arg(c, grad_xyz_or_null ? coef_or_null : nullptr, (size_t)B, &d_coef));
+    // accumulated (grad_xyz) or left as they were where a problem gives no result (cells, J_obj): host arrays go up first
+    ARG_TRY(out_arg(c, grad_xyz_or_null, (size_t)frames * P * 3, &d_grad, /*preload=*/true));
+    ARG_TRY(out_arg(c, cells_or_null, (size_t)B * max_inl, &d_cells, /*preload=*/true));
+    ARG_TRY(out_arg(c, J_obj_or_null, (size_t)B * max_inl * 18, &d_J, /*preload=*/true));
+    ARG_TRY(out_arg(c, n_out_or_null, (size_t)B, &d_n));
+    HIP_TRY(c, dk::refine_gn(c->stream, B, d_poses, d_fof, frames > 1 ? B / frames : 0, d_perm, steps, d_rows, max_inl, min_inl, thr, d_dL, d_coef, d_grad, d_cells, d_J, d_n,
+                             c->F));
+    return end_call(c);
+}
+
 int dsac_gather_patches(dsac_ctx* c, const uint8_t* bgr, int H, int W, const int32_t* sampling_xy, int n, int patch, float* patches, int32_t* skipped_or_null) {
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_gather_patches: ctx is NULL");
     if (!bgr || !sampling_xy || !patches || H <= 0 || W <= 0 || n < 0 || patch <= 0 || (patch & 1))

@@ -1408,4 +1408,229 @@ hipError_t refine_fd_finish(hipStream_t st, const FdLists& L, const double* rep_
     return hipGetLastError();
 }
 
+// --------------------------------------------------------------------------------------------------
+// K6's analytic backward (dsac_refine_gn_backward; the quantity is defined in include/dsac_hip.h): the derivative of a refined pose with respect to the scene
+// coordinates of the cells its last step was solved on, from the Gauss-Newton linearisation of that step's stationarity condition sum J_p^T r_p = 0 --
+// dh/dX_p = -A^-1 J_p^T G_p with A = sum J_p^T J_p -- instead of 6 re-run refinements per cell.  ONE WAVE PER PROBLEM, one launch for all problems of all frames:
+// the serial walk of k_refine over one permutation row at the given pose (same residual, same order, same list), one lm_eval<true> for A, one solve6_spd, then
+// lanes over the collected cells.  For the gradient dL is folded through T (d jp6 / d cv6) and A^-1 into one 6-vector q = A^-1 T^T dL first, so that a cell costs
+// one 2 x 6 and one 2 x 3 product: grad[p] -= coef (J_p q)^T G_p.  A^-1 itself (six solves) exists only when the Jacobians are asked for; T A^-1 then waits in LDS.
+// --------------------------------------------------------------------------------------------------
+// J_l(r) = I + a [r]x + b [r]x^2 (the left Jacobian of SO(3): R(r + d) = exp([J_l d]x) R(r) to first order), a = (1 - cos t) / t^2, b = (t - sin t) / t^3, or its
+// inverse I - [r]x / 2 + c [r]x^2, c = 1 / t^2 - cot(t / 2) / (2 t).  Half-angle forms (no cancellation in 1 - cos t, finite at t = pi); below t = 0.1 the
+// differences t - sin t and 1 / t^2 - ... cancel, there the series (next term below 3e-16)
+DM_INLINE void so3_left_jacobian(const double r[3], bool inverse, double J[9]) {
+    const double t2 = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
+    const bool small = t2 < 1e-2;
+    const double th = sqrt(small ? 1.0 : t2);
+    double sh, ch;
+    sincos(0.5 * th, &sh, &ch);
+    const double it2 = 1.0 / (small ? 1.0 : t2);
+    double a, b;
+    if (inverse) {
+        a = -0.5;
+        b = small ? 1.0 / 12 + t2 * (1.0 / 720 + t2 * (1.0 / 30240 + t2 * (1.0 / 1209600))) : it2 - ch / (2.0 * th * sh);
+    } else {
+        a = small ? 0.5 - t2 * (1.0 / 24 - t2 * (1.0 / 720 - t2 * (1.0 / 40320))) : 2.0 * sh * sh * it2;
+        b = small ? 1.0 / 6 - t2 * (1.0 / 120 - t2 * (1.0 / 5040 - t2 * (1.0 / 362880))) : (th - 2.0 * sh * ch) * it2 / th;
+    }
+    const double skew[9] = {0, -r[2], r[1], r[2], 0, -r[0], -r[1], r[0], 0};
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        const double id = (k % 4 == 0) ? 1.0 : 0.0;
+        J[k] = id + a * skew[k] + b * (r[k / 3] * r[k % 3] - t2 * id);
+    }
+}
+
+// the rotation block of T = d cv_to_jp6 / d cv6 at the cv pose h: R' = D R(r) with D = diag(1, -1, -1) (a rotation: D exp([a]x) = exp([D a]x) D), so
+// J_l(r') dr' = D J_l(r) dr.  The translation block is D itself.
+DM_INLINE void cv_to_jp6_jacobian_rot(const double h[6], double T[9]) {
+    double jp[6], Ji[9], Jc[9];
+    dm::cv_to_jp6(h, jp);
+    so3_left_jacobian(jp, true, Ji);
+    so3_left_jacobian(h, false, Jc);
+#pragma unroll
+    for (int k = 3; k < 9; k++) Jc[k] = -Jc[k];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) T[i * 3 + j] = Ji[i * 3] * Jc[j] + Ji[i * 3 + 1] * Jc[3 + j] + Ji[i * 3 + 2] * Jc[6 + j];
+}
+
+__global__ __launch_bounds__(64) void k_refine_gn(int B, const double* __restrict__ ref_poses, const int32_t* __restrict__ frame_of, int per_frame,
+                                                  const int32_t* __restrict__ perm, int steps, const int32_t* __restrict__ rows, int max_inl, int min_inl, float thr,
+                                                  const double* __restrict__ dL, const double* __restrict__ coef, double* __restrict__ grad_xyz,
+                                                  int32_t* __restrict__ cells_out, double* __restrict__ J_obj, int32_t* __restrict__ n_out, FrameDev F) {
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    // the problem's frame (frame_of comes from device memory: clamped) and its permutation row (likewise)
+    int f = 0;
+    if (F.frames > 1) {
+        f = uniform_frame(clamp_frame(frame_of ? frame_of[b] : (per_frame > 0 ? b / per_frame : 0), F));
+        select_frame(F, f);
+    }
+    const int row = __builtin_amdgcn_readfirstlane(min(max(rows ? rows[b] : 0, 0), steps - 1));
+    __shared__ float s_X[RF_MAX_INL * 3];
+    __shared__ float s_uv[RF_MAX_INL * 2];
+    __shared__ int s_cell[RF_MAX_INL];
+    __shared__ double s_red[32];
+    __shared__ double s_M[36];  // T A^-1, when the Jacobians are wanted
+    const dm::Cam K = make_cam_r(F);
+    double pose[6];
+    bool finite = true;
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        pose[i] = ref_poses[(size_t)b * 6 + i];
+        finite = finite && (pose[i] - pose[i] == 0.0);
+    }
+    if (!finite) {  // no result: every output of the problem stays as it was
+        if (lane == 0 && n_out) n_out[b] = 0;
+        return;
+    }
+    const int P = F.P;
+    const int32_t* pidx = perm + (size_t)row * P;
+    RodCache rc;
+    WalkCells cells;
+    rod_at(rc, pose);
+    const double* R = rc.R;
+    // K6's serial walk (k_refine, wave 0 alone): the first max_inl cells of the row below the threshold, in the row's order, and which cells they are
+    int cnt = 0;
+    for (int base = 0; base < P && cnt < max_inl; base += 64 * WALK_AHEAD) {
+        load_walk_cells(pidx, base, lane, F, cells);
+        float e[WALK_AHEAD], pu[WALK_AHEAD], pv[WALK_AHEAD];
+#pragma unroll
+        for (int s = 0; s < WALK_AHEAD; s++) {
+            walk_cell_uv(F, cells, s, pu[s], pv[s]);
+            e[s] = dm::residual_f(R, pose + 3, K, cells.X[s], cells.Y[s], cells.Z[s], pu[s], pv[s], 100.0);
+        }
+#pragma unroll
+        for (int s = 0; s < WALK_AHEAD; s++) {
+            if (cnt >= max_inl) break;
+            const int p = cells.p[s];
+            const bool inl = (p >= 0) && (e[s] < thr);
+            const unsigned long long m = __ballot(inl);
+            const int prefix = __popcll(m & ((1ull << lane) - 1ull));
+            if (inl && (cnt + prefix < max_inl)) {
+                const int slot = cnt + prefix;
+                s_X[slot * 3] = cells.X[s]; s_X[slot * 3 + 1] = cells.Y[s]; s_X[slot * 3 + 2] = cells.Z[s];
+                s_uv[slot * 2] = pu[s]; s_uv[slot * 2 + 1] = pv[s];
+                s_cell[slot] = p;
+            }
+            cnt += __popcll(m);
+        }
+    }
+    wave_sync_lds();
+    const int n = min(cnt, max_inl);
+    if (n < min_inl) {
+        if (lane == 0 && n_out) n_out[b] = 0;
+        return;
+    }
+    double JtJ[21], JtE[6], A[36];
+    lm_eval<true>(n, s_X, s_uv, s_red, K, rc, pose, JtJ, JtE);
+    {
+        int q = 0;
+#pragma unroll
+        for (int a = 0; a < 6; a++)
+#pragma unroll
+            for (int c = a; c < 6; c++) { A[a * 6 + c] = JtJ[q]; A[c * 6 + a] = JtJ[q]; q++; }
+    }
+    double T[9];
+    cv_to_jp6_jacobian_rot(pose, T);
+    bool ok = true;
+    double q6[6] = {0, 0, 0, 0, 0, 0}, w = 0.0;
+    if (grad_xyz) {  // q = A^-1 T^T dL
+        double d6[6], rhs[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) d6[i] = dL[(size_t)b * 6 + i];
+#pragma unroll
+        for (int j = 0; j < 3; j++) rhs[j] = T[j] * d6[0] + T[3 + j] * d6[1] + T[6 + j] * d6[2];
+        rhs[3] = d6[3]; rhs[4] = -d6[4]; rhs[5] = -d6[5];
+        ok = solve6_spd(A, rhs, q6);
+        w = coef ? coef[b] : 1.0;
+    }
+    if (J_obj) {  // T A^-1, row-major, for every lane through LDS
+        double Ai[36];
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            double ek[6], col[6];
+#pragma unroll
+            for (int i = 0; i < 6; i++) ek[i] = (i == k) ? 1.0 : 0.0;
+            ok = solve6_spd(A, ek, col) && ok;
+#pragma unroll
+            for (int i = 0; i < 6; i++) Ai[i * 6 + k] = col[i];
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int j = 0; j < 6; j++) {
+#pragma unroll
+                for (int i = 0; i < 3; i++) s_M[i * 6 + j] = T[i * 3] * Ai[j] + T[i * 3 + 1] * Ai[6 + j] + T[i * 3 + 2] * Ai[12 + j];
+                s_M[18 + j] = Ai[18 + j];
+                s_M[24 + j] = -Ai[24 + j];
+                s_M[30 + j] = -Ai[30 + j];
+            }
+        }
+        wave_sync_lds();
+    }
+    if (!ok) {  // a non-positive pivot: A is not positive definite to working precision
+        if (lane == 0 && n_out) n_out[b] = 0;
+        return;
+    }
+    double dRdr[27];
+    dm::rodrigues_J(rc.aux, dRdr);
+    for (int i = lane; i < n; i += 64) {
+        // residual Jacobians of cell i with lm_eval's formulas: J_p = (ju | tu 0 wu ; jv | 0 tv wv), G_p = (tu (R0 - x R2) ; tv (R1 - y R2))
+        const double Mx = s_X[i * 3], My = s_X[i * 3 + 1], Mz = s_X[i * 3 + 2];
+        const double Xc = R[0] * Mx + R[1] * My + R[2] * Mz + pose[3];
+        const double Yc = R[3] * Mx + R[4] * My + R[5] * Mz + pose[4];
+        const double Zc = R[6] * Mx + R[7] * My + R[8] * Mz + pose[5];
+        const double z = (Zc != 0.0) ? drcp(Zc) : 1.;
+        const double x = Xc * z, y = Yc * z;
+        const double tu = K.fx * z, tv = K.fy * z;
+        double ju[3], jv[3], gu[3], gv[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const double* dR = dRdr + j * 9;
+            const double dX = dR[0] * Mx + dR[1] * My + dR[2] * Mz;
+            const double dY = dR[3] * Mx + dR[4] * My + dR[5] * Mz;
+            const double dZ = dR[6] * Mx + dR[7] * My + dR[8] * Mz;
+            ju[j] = tu * (dX - x * dZ);
+            jv[j] = tv * (dY - y * dZ);
+            gu[j] = tu * (R[j] - x * R[6 + j]);
+            gv[j] = tv * (R[3 + j] - y * R[6 + j]);
+        }
+        const double wu = -tu * x, wv = -tv * y;
+        const int p = s_cell[i];
+        if (cells_out) cells_out[(size_t)b * max_inl + i] = p;
+        if (grad_xyz) {
+            const double su = ju[0] * q6[0] + ju[1] * q6[1] + ju[2] * q6[2] + tu * q6[3] + wu * q6[5];
+            const double sv = jv[0] * q6[0] + jv[1] * q6[1] + jv[2] * q6[2] + tv * q6[4] + wv * q6[5];
+            double* g = grad_xyz + ((size_t)f * P + p) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; c++) atomicAdd(g + c, -w * (su * gu[c] + sv * gv[c]));
+        }
+        if (J_obj) {
+            double* Jo = J_obj + ((size_t)b * max_inl + i) * 18;
+#pragma unroll
+            for (int k = 0; k < 6; k++) {
+                const double* m = s_M + k * 6;
+                const double su = ju[0] * m[0] + ju[1] * m[1] + ju[2] * m[2] + tu * m[3] + wu * m[5];
+                const double sv = jv[0] * m[0] + jv[1] * m[1] + jv[2] * m[2] + tv * m[4] + wv * m[5];
+#pragma unroll
+                for (int c = 0; c < 3; c++) Jo[k * 3 + c] = -(su * gu[c] + sv * gv[c]);
+            }
+        }
+    }
+    if (lane == 0 && n_out) n_out[b] = n;
+}
+
+hipError_t refine_gn(hipStream_t st, int B, const double* ref_poses, const int32_t* frame_of, int per_frame, const int32_t* perm, int steps, const int32_t* rows,
+                     int max_inl, int min_inl, float thr, const double* dL, const double* coef, double* grad_xyz, int32_t* cells, double* J_obj, int32_t* n_out,
+                     const FrameDev& F) {
+    if (B < 1 || steps < 1 || max_inl < 1 || max_inl > RF_MAX_INL || F.P < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_refine_gn, dim3((unsigned)B), dim3(64), 0, st, B, ref_poses, frame_of, per_frame, perm, steps, rows, max_inl, min_inl, thr, dL, coef, grad_xyz,
+                       cells, J_obj, n_out, F);
+    return hipGetLastError();
+}
+
 }  // namespace dk

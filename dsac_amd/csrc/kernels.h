@@ -280,6 +280,13 @@ hipError_t refine_fd_run(hipStream_t st, const FdLists& L, const int32_t* n_obj,
 // J_head: lists x 6 x 6 (J_hyp; rows 3-5 over 2 eps_hyp * 1000) or lists x 6 x 9 (J_set, over 2 eps_obj); J_obj over 2 eps_obj, scaled by skip
 hipError_t refine_fd_finish(hipStream_t st, const FdLists& L, const double* rep_out, const int32_t* n_obj, int skip, float eps_hyp, float eps_obj, double* J_head,
                             double* J_obj);
+// ---- K6's analytic backward: the Gauss-Newton linearisation of a refined pose (dsac_refine_gn_backward, include/dsac_hip.h), one launch of B waves ----
+// problem b: pose ref_poses[b] (cv), frame frame_of[b] (clamped) or b / per_frame (per_frame 0: frame 0), permutation row rows[b] (clamped; nullptr: row 0).
+// grad_xyz (frames x P x 3, accumulated with fp64 atomics) needs dL (B x 6, jp); coef nullptr = 1.  cells B x max_inl, J_obj B x max_inl x 6 x 3, n_out B.
+// A problem without a result (fewer than min_inl cells, a non-finite pose, a non-positive pivot) writes n_out[b] = 0 and nothing else.
+hipError_t refine_gn(hipStream_t st, int B, const double* ref_poses, const int32_t* frame_of, int per_frame, const int32_t* perm, int steps, const int32_t* rows,
+                     int max_inl, int min_inl, float thr, const double* dL, const double* coef, double* grad_xyz, int32_t* cells, double* J_obj, int32_t* n_out,
+                     const FrameDev& F);
 
 // ---- k_loss.hip ------------------------------------------------------------------------------------
 // gt_stride: 0 = one ground truth (6 doubles) for all estimates, 6 = one per estimate

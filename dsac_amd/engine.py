@@ -749,6 +749,28 @@ class Engine:
                                                  float(sub_sample), float(eps_obj), ptr(J_set), ptr(px), ptr(J_obj), int(cap), ptr(n)))
         return J_set, n, px, J_obj
 
+    def dRefineGN(self, ref_poses, perm, rows=None, frame_of=None, max_inl=100, min_inl=50, thr=10.0, dL=None, coef=None, grad=None, want_jacobians=False):
+        """dsac_refine_gn_backward: the Gauss-Newton linearisation of B refined poses (cv, B x 6) with respect to the scene coordinates, one launch.  rows: the
+        permutation row each pose's list is walked on (B, default row 0); frame_of: the frame of every problem of a batch (default b // (B // frames)).
+        With dL (B x 6, jp: maxLossBatch(..., want_grad=True)["grad"]) the gradient sum_b coef[b] dL[b]^T J_obj[b] is ADDED to grad (frames * P x 3, zeros when
+        not given).  Returns (grad or None, n B [, cells B x max_inl, J_obj B x max_inl x 6 x 3]); n[b] = 0: no result, the problem's rows are untouched."""
+        def arr(a, dtype, *shape):  # torch tensors (host or device) pass as they are: the caller guarantees dtype and layout
+            return a if a is None or hasattr(a, "data_ptr") else np.ascontiguousarray(np.asarray(a, dtype=dtype).reshape(shape))
+
+        ref = arr(ref_poses, np.float64, -1, 6)
+        B = int(ref.shape[0])
+        perm = arr(perm, np.int32, -1, self.P)
+        rows, frame_of = arr(rows, np.int32, B), arr(frame_of, np.int32, B)
+        dL, coef = arr(dL, np.float64, B, 6), arr(coef, np.float64, B)
+        if dL is not None and grad is None:
+            grad = np.zeros((getattr(self, "frames", 1) * self.P, 3))
+        n = np.zeros(B, np.int32)
+        cells = np.zeros((B, int(max_inl)), np.int32) if want_jacobians else None
+        J_obj = np.zeros((B, int(max_inl), 6, 3)) if want_jacobians else None
+        check(self._ctx, lib.dsac_refine_gn_backward(self._ctx, B, ptr(ref), ptr(frame_of), ptr(perm), int(perm.shape[0]), ptr(rows), int(max_inl), int(min_inl),
+                                                     float(thr), ptr(dL), ptr(coef), ptr(grad), ptr(cells), ptr(J_obj), ptr(n)))
+        return (grad, n, cells, J_obj) if want_jacobians else (grad, n)
+
     def maxLossBatch(self, est_cv6, gt_jp6, want_grad=False):
         """maxLoss [+ dLossMax] of B estimates against one ground truth (losses of expectedMaxLoss, core/cnn.h:137-150)."""
         est = np.ascontiguousarray(np.asarray(est_cv6, dtype=np.float64).reshape(-1, 6))
@@ -837,16 +859,25 @@ class Engine:
         return dict(hyps=hyps, sampledPoints=sets, ok=ok, scores=soft, score_scale=alpha, sfScores=w, sfEntropy=ent, refHyps=ref, refSteps=sd, inlierMaps=maps, out4=out4,
                     hypIdx=idx, expectedLoss=eloss, scoreOutputGradients=g)
 
-    def backwardDSAC(self, fwd, gt_jp6, d_scores_fn=None, thr=10.0, inlierCount=100, minInliers=50, tau=10.0, beta=0.5, sub_sample=0.01, min_prob=1e-4):
+    def backwardDSAC(self, fwd, gt_jp6, d_scores_fn=None, thr=10.0, inlierCount=100, minInliers=50, tau=10.0, beta=0.5, sub_sample=0.01, min_prob=1e-4,
+                     refine_grad="fd"):
         """Backward section of the DSAC trainer (core/train_ransac.cpp:303-399): dE[loss]/d(scene coordinates), P x 3.
         Path I: sum_h w_h dLossMax(ref_h) . dRefine_h (hypotheses with w_h <= 1e-4 skipped, :318); path II: dSMScore (core/cnn.h:
-        726-768), whose result the reference re-orders to row-major, i.e. no index quirk here."""
+        726-768), whose result the reference re-orders to row-major, i.e. no index quirk here.
+        refine_grad: "fd" = the reference's finite differences of the refinement (every 1 / sub_sample-th inlier cell, times skip); "gn" = the Gauss-Newton
+        linearisation of every hypothesis' last refinement step (dsac_refine_gn_backward: one launch, every cell of the step's list, no J_set term -- under
+        the linearisation the optimum does not depend on where the refinement started)."""
+        if refine_grad not in ("fd", "gn"):
+            raise ValueError("dsac_amd: refine_grad is \"fd\" or \"gn\", got %r" % (refine_grad,))
         w, sets, ref = fwd["sfScores"], fwd["sampledPoints"], fwd["refHyps"]
         N = len(w)
         grad = np.zeros((self.P, 3))
         dL = self.maxLossBatch(ref, gt_jp6, want_grad=True)["grad"]
         sel = np.flatnonzero(w > min_prob)
-        if len(sel):  # one batched launch for all hypotheses that carry weight (train_ransac.cpp:318)
+        if len(sel) and refine_grad == "gn":  # the list of a hypothesis' last step: the row that step walked
+            rows = np.maximum(np.asarray(fwd["refSteps"], dtype=np.int64)[sel] - 1, 0)
+            self.dRefineGN(ref[sel], fwd["pixelIdxs"], rows=rows, max_inl=inlierCount, min_inl=minInliers, thr=float(int(thr)), dL=dL[sel], coef=w[sel], grad=grad)
+        elif len(sel):  # one batched launch for all hypotheses that carry weight (train_ransac.cpp:318)
             J_set, n_obj, px, J_obj = self.dRefineSets(sets[sel], fwd["pixelIdxs"], fwd["inlierMaps"][sel], max_inl=inlierCount, min_inl=minInliers,
                                                        thr=float(int(thr)), sub_sample=sub_sample)
             for i, h in enumerate(sel):

@@ -579,6 +579,33 @@ DSAC_API int dsac_refine_fd_sets(dsac_ctx* ctx, int M, const int32_t* sets, cons
 DSAC_API int dsac_refine_fd_sets_frames(dsac_ctx* ctx, int M, const int32_t* sets, const int32_t* frame_of, const int32_t* perm, int steps, int max_inl, int min_inl,
                                float thr, const int32_t* inlier_maps, float sub_sample, float eps_obj, double* J_set, int32_t* obj_pixels, double* J_obj,
                                int cap, int32_t* n_obj);
+/* Analytic refinement gradients: the derivative of B refined poses with respect to the scene coordinates, from the Gauss-Newton linearisation of the last
+ * refinement step, in ONE launch of B waves -- what DSAC++ and its successors use in place of the finite differences above.  The quantity, for problem b with
+ * pose h_b = ref_poses[b] (cv 6-vector, the output of a refinement) on frame f_b:
+ *   list      L_b = the first max_inl cells p along the permutation row perm[rows[b]] whose residual at h_b is below thr -- the test and the order of K6's walk:
+ *             the projection rounded to float, the norm taken in double, clamped at 100, a NaN below no threshold; n_b = |L_b|
+ *   residual  r_p = project(h, X_p) - uv_p, J_p = d r_p / d h (2 x 6), G_p = d r_p / d X_p = diag(fx z, fy z) [R_0 - x R_2 ; R_1 - y R_2] (2 x 3; R_i the rows
+ *             of R(h), (x, y, 1 / z) the normalised camera point), all in double, the formulas of the Levenberg-Marquardt solve;  A_b = sum over L_b of J_p^T J_p
+ *   GN        the stationarity condition sum J_p^T r_p = 0 linearised with the residual-weighted second derivatives dropped:
+ *             d h / d X_p = -A_b^-1 J_p^T G_p (6 x 3, cv parameters) for p in L_b, zero for every other cell
+ *   output    J_obj[b][i] = T_b . d h / d X_{L_b[i]}, T_b = d cv_to_jp6 / d cv6 at h_b (getRodVecAndTrans(Hypothesis(cv2our(.)))): the jp convention and the layout
+ *             of dsac_refine_fd_sets' J_obj, what dsac_loss* differentiates against
+ * Dropping the second-order terms is part of the definition: on a map without noise the result is the exact derivative of the converged refinement (central
+ * differences of a converged solve agree to 1e-7); with 20 mm of noise (3.6 px rms residual) it deviates from the exact derivative by 1.5 - 2.6 %.  There is no
+ * sub-sampling and no skip factor: every cell of L_b receives its own gradient.
+ * No result: n_b < min_inl, a non-finite entry of h_b, or a non-positive pivot in the L D L^T factorisation of A_b.  Then n_out[b] = 0 and every other output of
+ * problem b stays as it was; otherwise n_out[b] = n_b, cells[b][i] = L_b[i] and J_obj[b][i] for i < n_b (entries beyond n_b are untouched).
+ * Frames: a single frame serves every problem.  On a frame batch without frame_of B must be frames x (problems per frame), problem b lives in frame
+ * b / (B / frames) as in dsac_refine_all; with frame_of (B int32) any B is accepted, entries outside the batch are clamped to it.  Shared and per-frame
+ * cameras (dsac_set_frames_cams) both work, fx != fy included.  rows: B int32 in [0, steps) (a host array is checked, device entries are clamped), NULL = row 0.
+ * grad_xyz (frames x H*W x 3 doubles, ACCUMULATED into with fp64 atomics): grad_xyz[f_b * H*W + p] += coef[b] * dL[b]^T J_obj[b][i] for p = L_b[i]; dL is B x 6 (jp,
+ * dsac_loss_batch's J6), coef B or NULL for 1.  Host or device pointers; with device pointers the call only enqueues.
+ * DSAC_ERR_INVALID with nothing enqueued: B < 1, max_inl outside 1 .. 256, min_inl < 3, steps < 1, perm or ref_poses NULL, grad_xyz without dL or dL without
+ * grad_xyz, neither grad_xyz nor (cells and J_obj) requested, J_obj without cells, B % frames != 0 on a batch without frame_of, a host rows entry outside
+ * [0, steps).  DSAC_ERR_NO_FRAME without a frame. */
+DSAC_API int dsac_refine_gn_backward(dsac_ctx* ctx, int B, const double* ref_poses, const int32_t* frame_of_or_null, const int32_t* perm, int steps,
+                            const int32_t* rows_or_null, int max_inl, int min_inl, float thr, const double* dL_jp6_or_null, const double* coef_or_null,
+                            double* grad_xyz_or_null, int32_t* cells_or_null, double* J_obj_or_null, int32_t* n_out_or_null);
 /* maxLoss / dLossMax for B estimates against one ground truth: the losses[] of expectedMaxLoss core/cnn.h:137-150 and
  * the per-hypothesis dLossMax of core/train_ransac.cpp:345-349.  out4 is B x 4, J6 B x 6 (layouts of dsac_loss). */
 DSAC_API int dsac_loss_batch(dsac_ctx* ctx, int B, const double* est_cv6, const double* gt_jp6, double* out4, double* J6_or_null);
