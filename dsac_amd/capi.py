@@ -53,7 +53,10 @@ EXPORTS = [
     "dsac_set_frames_cams",
     "dsac_set_sampling_weights", "dsac_sampling_table", "dsac_sampling_weights_backward",
     "dsac_refine_gn_backward",
+    "dsac_refine_soft", "dsac_refine_soft_backward",
 ]
+DSAC_SOFT_BWD_FIXED_WEIGHTS = 1
+SOFT_STATUS = ("CONVERGED", "MAXIT", "SCORE", "FEW", "SINGULAR", "NONFINITE")  # enum dsac_soft_status
 
 # enum dsac_k2_form (dsac_get_option "k2_form_last") and the DSAC_K2_WHY_* bits ("k2_form_why_last")
 K2_FORMS = ("none", "fp32 valu", "fp32 mfma", "records in two pieces", "exact (vector build)", "exact (any-map build)", "precise")
@@ -138,6 +141,8 @@ def _load():
     lib.dsac_process_images.argtypes = [vp, i32, u64, f32, i32, f32, f32, f32, f64, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.dsac_refine_fd_sets_frames.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, f32, vp, f32, f32, vp, vp, vp, i32, vp]
     lib.dsac_refine_gn_backward.argtypes = [vp, i32, vp, vp, vp, i32, vp, i32, i32, f32, vp, vp, vp, vp, vp, vp]
+    lib.dsac_refine_soft.argtypes = [vp, i32, vp, vp, f64, f64, f64, f64, i32, f64, vp, vp, vp, vp]
+    lib.dsac_refine_soft_backward.argtypes = [vp, i32, vp, vp, f64, f64, f64, f64, vp, vp, u32, vp, vp]
     lib.dsac_loss_batch_frames.argtypes =[vp, i32, i32, vp, vp, vp, vp]
     lib.dsac_select_frames.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.dsac_soft_score_derr.argtypes = [vp, i32, vp, vp, f32, f32, f32, vp]

@@ -72,6 +72,8 @@ struct dsac_ctx {
     int pi_refstream = 0, pi_refstream_discard0 = 0, pi_refstream_attempts = 0;
     int k6_walk_exact = 0;  // "k6_walk_exact": 1 = the split walk decides every cell by the fp64 residual (no fp32 filter; A/B)
     int k6_waves = 0;  // "k6_waves": waves per refinement problem of K6's walk (0 = by the problem count)
+    int refine_soft_form = -1;  // "refine_soft_form": dsac_refine_soft's loop, -1 = by the map size, 0 = split (pass + step launches), 1 = fused (one launch)
+    DevBuf soft_scratch;        // dsac_refine_soft / dsac_refine_soft_backward: per-chunk sums, loop state, backward records
     DevBuf staged, staged_lo, staged_split, soft_part, bwd_staged, dRdH, grad_part, g12_part, g6;
     int g6_n = 0;  // hypotheses held by g6 (dsac_last_pose_gradients)
     // staging for host-pointer arguments: slots are bump-allocated per call.  A deque: next_slot() hands out references that
@@ -624,7 +626,7 @@ void dsac_destroy(dsac_ctx* c) {
     if (c->aux2) (void)hipStreamSynchronize(c->aux2);
     c->frame_xyz.release(); c->frame_uv.release(); c->cams_d.release();
     c->guide_cdf.release(); c->guide_coarse.release(); c->guide_meta.release(); c->guide_w.release(); c->guide_scratch.release();
-    c->staged.release(); c->staged_lo.release(); c->staged_split.release(); c->rs_states.release(); c->rs_scratch.release(); c->rs_small.release(); c->k6_scratch.release(); c->soft_part.release(); c->bwd_staged.release(); c->dRdH.release();
+    c->staged.release(); c->staged_lo.release(); c->staged_split.release(); c->rs_states.release(); c->rs_scratch.release(); c->rs_small.release(); c->k6_scratch.release(); c->soft_scratch.release(); c->soft_part.release(); c->bwd_staged.release(); c->dRdH.release();
     c->grad_part.release(); c->g12_part.release(); c->g6.release();
     for (auto& s : c->slots) s.release();
     if (c->aux) { (void)hipStreamSynchronize(c->aux); (void)hipStreamDestroy(c->aux); }
@@ -1413,6 +1415,10 @@ int dsac_set_option(dsac_ctx* c, const char* key, int value) {
         if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return fail(c, DSAC_ERR_INVALID, "dsac_set_option: k6_waves is 0 (auto), 1, 2, 4 or 8");
         c->k6_waves = value;
     }
+    else if (k == "refine_soft_form") {
+        if (value < -1 || value > 1) return fail(c, DSAC_ERR_INVALID, "dsac_set_option: refine_soft_form is -1 (by the map size), 0 (split) or 1 (fused)");
+        c->refine_soft_form = value;
+    }
     else if (k == "refstream_mode") {
         if (value < -1 || value > 1) return fail(c, DSAC_ERR_INVALID, "dsac_set_option: refstream_mode is 0 (libstdc++ >= 11), 1 (libstdc++ <= 10) or -1 (this build's)");
         c->rs_mode = value < 0 ? DSAC_RS_DEFAULT_MODE : value;
@@ -1480,6 +1486,7 @@ int dsac_get_option(dsac_ctx* c, const char* key, int* value) {
     else if (k == "k6_walk_exact") *value = c->k6_walk_exact;
     else if (k == "k6_scan_tune") *value = dk::refine_scan_tune_get();
     else if (k == "k6_waves") *value = c->k6_waves;
+    else if (k == "refine_soft_form") *value = c->refine_soft_form;
     else if (k == "refstream_mode") *value = c->rs_mode;
     else if (k == "pi_refstream") *value = c->pi_refstream;
     else if (k == "pi_refstream_discard0") *value = c->pi_refstream_discard0;
@@ -1936,6 +1943,76 @@ int dsac_refine_gn_backward(dsac_ctx* c, int B, const double* ref_poses, const i
     ARG_TRY(out_arg(c, n_out_or_null, (size_t)B, &d_n));
     HIP_TRY(c, dk::refine_gn(c->stream, B, d_poses, d_fof, frames > 1 ? B / frames : 0, d_perm, steps, d_rows, max_inl, min_inl, thr, d_dL, d_coef, d_grad, d_cells, d_J, d_n,
                              c->F));
+    return end_call(c);
+}
+
+// what dsac_refine_soft and dsac_refine_soft_backward refuse alike, by the caller's name
+static int refine_soft_check(dsac_ctx* c, const char* who, int B, const double* poses, const int32_t* frame_of_or_null, double tau, double beta, double cut, double min_soft) {
+    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "%s: ctx is NULL", who);
+    if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "%s: no frame set", who);
+    const int frames = c->F.frames > 1 ? c->F.frames : 1;
+    if (B < 1 || !poses) return fail(c, DSAC_ERR_INVALID, "%s: need B >= 1 (got %d) and non-NULL poses", who, B);
+    if (!std::isfinite(tau) || !std::isfinite(beta) || !std::isfinite(min_soft)) return fail(c, DSAC_ERR_INVALID, "%s: tau, beta and min_soft must be finite", who);
+    if (!(beta > 0.0)) return fail(c, DSAC_ERR_INVALID, "%s: beta must be > 0 (got %g)", who, beta);
+    if (!(cut > 0.0) || !(cut <= 100.0)) return fail(c, DSAC_ERR_INVALID, "%s: cut must lie in (0, 100] (got %g)", who, cut);
+    if (frames > 1 && !frame_of_or_null && B % frames != 0)
+        return fail(c, DSAC_ERR_INVALID, "%s: with a frame batch B must be frames x (problems per frame) -- or give every problem its frame (frame_of)", who);
+    if ((long long)B * dk::refine_soft_geom(c->F.P).nchunks > 0x7fffffffll) return fail(c, DSAC_ERR_INVALID, "%s: B = %d problems on this map are too many for one call", who, B);
+    return DSAC_OK;
+}
+
+int dsac_refine_soft(dsac_ctx* c, int B, const double* init_poses, const int32_t* frame_of_or_null, double tau, double beta, double cut, double min_soft, int max_iters,
+                     double step_tol, double* out_poses, double* soft_out_or_null, int32_t* iters_out_or_null, int32_t* status_out_or_null) {
+    const char* who = "dsac_refine_soft";
+    ARG_TRY(refine_soft_check(c, who, B, init_poses, frame_of_or_null, tau, beta, cut, min_soft));
+    if (!out_poses) return fail(c, DSAC_ERR_INVALID, "%s: out_poses is NULL", who);
+    if (max_iters < 1 || max_iters > 64) return fail(c, DSAC_ERR_INVALID, "%s: max_iters must lie in 1 .. 64 (got %d)", who, max_iters);
+    if (!std::isfinite(step_tol) || step_tol < 0.0) return fail(c, DSAC_ERR_INVALID, "%s: step_tol must be finite and >= 0 (got %g)", who, step_tol);
+    const int frames = c->F.frames > 1 ? c->F.frames : 1;
+    HIP_TRY(c, hipSetDevice(c->device));
+    begin_call(c);
+    const double* d_init;
+    const int32_t* d_fof;
+    double *d_out, *d_soft;
+    int32_t *d_it, *d_status;
+    ARG_TRY(in_arg(c, init_poses, (size_t)B * 6, &d_init));
+    ARG_TRY(in_arg(c, frames > 1 ? frame_of_or_null : nullptr, (size_t)B, &d_fof));
+    ARG_TRY(out_arg(c, out_poses, (size_t)B * 6, &d_out));
+    ARG_TRY(out_arg(c, soft_out_or_null, (size_t)B, &d_soft));
+    ARG_TRY(out_arg(c, iters_out_or_null, (size_t)B, &d_it));
+    ARG_TRY(out_arg(c, status_out_or_null, (size_t)B, &d_status));
+    const dk::SoftGeom geom = dk::refine_soft_geom(c->F.P);  // once: the scratch is sized and the passes are launched with the same chunks
+    const bool fused = c->refine_soft_form < 0 ? dk::refine_soft_auto_fused(c->F.P) : c->refine_soft_form == 1;
+    if (!fused) HIP_TRY(c, c->soft_scratch.reserve(dk::refine_soft_scratch_bytes(B, geom)));
+    HIP_TRY(c, dk::refine_soft(c->stream, B, d_init, d_fof, frames > 1 ? B / frames : 0, tau, beta, cut, min_soft, max_iters, step_tol, fused, geom, c->soft_scratch.p, d_out,
+                               d_soft, d_it, d_status, c->F));
+    return end_call(c);
+}
+
+int dsac_refine_soft_backward(dsac_ctx* c, int B, const double* ref_poses, const int32_t* frame_of_or_null, double tau, double beta, double cut, double min_soft,
+                              const double* dL_jp6, const double* coef_or_null, unsigned flags, double* grad_xyz, int32_t* ok_out_or_null) {
+    const char* who = "dsac_refine_soft_backward";
+    ARG_TRY(refine_soft_check(c, who, B, ref_poses, frame_of_or_null, tau, beta, cut, min_soft));
+    if (!dL_jp6 || !grad_xyz) return fail(c, DSAC_ERR_INVALID, "%s: dL and grad_xyz must be non-NULL", who);
+    if (flags & ~(unsigned)DSAC_SOFT_BWD_FIXED_WEIGHTS) return fail(c, DSAC_ERR_INVALID, "%s: unknown flag bits 0x%x", who, flags);
+    const int frames = c->F.frames > 1 ? c->F.frames : 1;
+    HIP_TRY(c, hipSetDevice(c->device));
+    begin_call(c);
+    const size_t P = (size_t)c->F.P;
+    const double *d_poses, *d_dL, *d_coef;
+    const int32_t* d_fof;
+    double* d_grad;
+    int32_t* d_ok;
+    ARG_TRY(in_arg(c, ref_poses, (size_t)B * 6, &d_poses));
+    ARG_TRY(in_arg(c, frames > 1 ? frame_of_or_null : nullptr, (size_t)B, &d_fof));
+    ARG_TRY(in_arg(c, dL_jp6, (size_t)B * 6, &d_dL));
+    ARG_TRY(in_arg(c, coef_or_null, (size_t)B, &d_coef));
+    ARG_TRY(out_arg(c, grad_xyz, (size_t)frames * P * 3, &d_grad, /*preload=*/true));  // accumulated into: a host array goes up first
+    ARG_TRY(out_arg(c, ok_out_or_null, (size_t)B, &d_ok));
+    const dk::SoftGeom geom = dk::refine_soft_geom(c->F.P);
+    HIP_TRY(c, c->soft_scratch.reserve(dk::refine_soft_scratch_bytes(B, geom)));
+    HIP_TRY(c, dk::refine_soft_backward(c->stream, B, d_poses, d_fof, frames > 1 ? B / frames : 0, tau, beta, cut, min_soft, d_dL, d_coef, flags, geom, c->soft_scratch.p,
+                                        d_grad, d_ok, c->F));
     return end_call(c);
 }
 

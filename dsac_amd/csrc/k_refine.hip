@@ -1633,4 +1633,462 @@ hipError_t refine_gn(hipStream_t st, int B, const double* ref_poses, const int32
     return hipGetLastError();
 }
 
+// ---- Soft-inlier refinement over the whole map and its backward (dsac_refine_soft / dsac_refine_soft_backward; include/dsac_hip.h has the definition) ----
+// A pass at a pose evaluates every cell of the problem's frame: weight w = sigmoid(beta (tau - e)), zero at and beyond `cut`, and the sums S = sum w,
+// A = sum w J^T J, g = sum w J^T r.  Two forms of the forward loop: split (a pass kernel on cell chunks x problems whose per-chunk sums go to scratch, and a
+// one-wave step kernel that adds them in index order, decides and moves the pose; the host enqueues max_iters + 1 of each with no round trip) and fused (one
+// workgroup per problem runs the whole loop).  Both call soft_cell / soft_accumulate per cell and soft_decide per iteration.  No floating-point atomics
+// anywhere: every sum has one order, so two calls give the same bits.
+constexpr int SOFT_NACC = 28;      // 21 of A (packed upper triangle, lm_eval's order), 6 of g, S
+constexpr int SOFT_STATE = 16;     // doubles per problem between the launches of the split form: pose (6), trial pose (6), S, 3 unused
+constexpr int SOFT_REC = 26;       // doubles per problem between solve and scatter of the backward: R (9), t (3), sum_j q_j dR / d rho_j (9), q[3..5], coef, 1 unused
+constexpr int SOFT_FUSED_WAVES = 4;
+constexpr int SOFT_SCATTER_TILE = 32;  // records staged in LDS at a time (6.5 KB)
+// auto takes the fused form up to this many cells.  Measured (profiles/refine_soft_ab.txt, whole calls of 20 steps, split / fused in us): B = 64: 1 600 cells 237 / 136,
+// 4 800 cells 360 / 292, 12 288 cells 572 / 668; 16 x 256 on 1 600 cells 1 530 / 1 250; B = 1: 1 600 cells 141 / 70, 4 800 cells 227 / 249.  The crossover lies between
+// 4 800 and 12 288 cells with many problems and near 4 800 with one
+constexpr int SOFT_FUSED_MAX_CELLS = 4800;
+enum { SOFT_CONVERGED = 0, SOFT_MAXIT = 1, SOFT_SCORE = 2, SOFT_FEW = 3, SOFT_SINGULAR = 4, SOFT_NONFINITE = 5 };
+
+SoftGeom refine_soft_geom(int P) {
+    // at most 256 chunks per problem (the step kernel adds them one after the other), at least 256 cells each, whole 64-lane trips
+    int chunk = (P + 255) / 256;
+    chunk = max(256, (chunk + 63) / 64 * 64);
+    return SoftGeom{chunk, (P + chunk - 1) / chunk};
+}
+bool refine_soft_auto_fused(int P) { return P <= SOFT_FUSED_MAX_CELLS; }
+// scratch: per-chunk sums | state | done | iters | records | record frames
+static size_t soft_off_state(int B, const SoftGeom& g) { return align256((size_t)B * g.nchunks * SOFT_NACC * 8); }
+static size_t soft_off_done(int B, const SoftGeom& g) { return soft_off_state(B, g) + align256((size_t)B * SOFT_STATE * 8); }
+static size_t soft_off_iters(int B, const SoftGeom& g) { return soft_off_done(B, g) + align256((size_t)B * 4); }
+static size_t soft_off_rec(int B, const SoftGeom& g) { return soft_off_iters(B, g) + align256((size_t)B * 4); }
+static size_t soft_off_recf(int B, const SoftGeom& g) { return soft_off_rec(B, g) + align256((size_t)B * SOFT_REC * 8); }
+size_t refine_soft_scratch_bytes(int B, const SoftGeom& g) { return soft_off_recf(B, g) + align256((size_t)B * 4); }
+
+// The per-cell code of every pass and of the scatter: camera point, residual and weight of one cell at the pose (R, t), lm_eval's formulas in double.
+struct SoftCell {
+    double x, y, tu, tv, eu, ev, e, w;
+};
+DM_INLINE bool soft_cell(const double* R, const double* t, const dm::Cam& K, double Mx, double My, double Mz, double u, double v, double tau, double beta,
+                         double cut, SoftCell& c) {
+    const double Xc = R[0] * Mx + R[1] * My + R[2] * Mz + t[0];
+    const double Yc = R[3] * Mx + R[4] * My + R[5] * Mz + t[1];
+    const double Zc = R[6] * Mx + R[7] * My + R[8] * Mz + t[2];
+    const double z = (Zc != 0.0) ? drcp(Zc) : 1.;
+    c.x = Xc * z;
+    c.y = Yc * z;
+    c.tu = K.fx * z;
+    c.tv = K.fy * z;
+    c.eu = c.x * K.fx + K.cx - u;
+    c.ev = c.y * K.fy + K.cy - v;
+    c.e = sqrt(c.eu * c.eu + c.ev * c.ev);
+    const bool near = c.e < cut;  // false for a NaN; an infinite e is not below cut <= 100
+    c.w = near ? 1.0 / (1.0 + exp(-beta * (tau - c.e))) : 0.0;
+    return c.w > 0.0;
+}
+// d w / d e over e: the factor of r r^T in M = w I + (w' / e) r r^T; 0 where e = 0 and with fixed weights
+DM_INLINE double soft_wprime_over_e(const SoftCell& c, double beta, bool fixed_w) {
+    return (fixed_w || !(c.e > 0.0)) ? 0.0 : -beta * c.w * (1.0 - c.w) / c.e;
+}
+// the cell's terms of a pass: acc[0..20] += w J^T J (BWD: J^T M J), acc[21..26] += w J^T r (forward only), acc[27] += w.  A cell that is not live adds exact
+// zeros, whatever its coordinates hold.  J = (ju | tu 0 wu ; jv | 0 tv wv): the structural zeros are left out of the products
+template <bool BWD>
+DM_INLINE void soft_accumulate(const SoftCell& c, bool live, const double* dRdr, double Mx, double My, double Mz, double k_rr, double (&acc)[32]) {
+    const double x = live ? c.x : 0.0, y = live ? c.y : 0.0, tu = live ? c.tu : 0.0, tv = live ? c.tv : 0.0;
+    const double eu = live ? c.eu : 0.0, ev = live ? c.ev : 0.0, w = live ? c.w : 0.0;
+    double Ju[6], Jv[6];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const double* dR = dRdr + j * 9;
+        const double dX = dR[0] * Mx + dR[1] * My + dR[2] * Mz;
+        const double dY = dR[3] * Mx + dR[4] * My + dR[5] * Mz;
+        const double dZ = dR[6] * Mx + dR[7] * My + dR[8] * Mz;
+        Ju[j] = live ? tu * (dX - x * dZ) : 0.0;
+        Jv[j] = live ? tv * (dY - y * dZ) : 0.0;
+    }
+    Ju[3] = tu; Ju[4] = 0.0; Ju[5] = -tu * x;
+    Jv[3] = 0.0; Jv[4] = tv; Jv[5] = -tv * y;
+    double wJu[6], wJv[6], c6[6], kc[6];
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+        wJu[a] = w * Ju[a];
+        wJv[a] = w * Jv[a];
+        if (BWD) {  // J^T r, for the r r^T term
+            c6[a] = (a == 4) ? Jv[a] * ev : (a == 3) ? Ju[a] * eu : fma(Ju[a], eu, Jv[a] * ev);
+            kc[a] = (live ? k_rr : 0.0) * c6[a];
+        }
+    }
+    int q = 0;
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+#pragma unroll
+        for (int b = a; b < 6; b++) {
+            double s = acc[q];
+            if (a != 4 && b != 4) s = fma(wJu[a], Ju[b], s);
+            if (a != 3 && b != 3) s = fma(wJv[a], Jv[b], s);
+            if (BWD) s = fma(kc[a], c6[b], s);
+            acc[q++] = s;
+        }
+        if (!BWD) {
+            double s = acc[21 + a];
+            if (a != 4) s = fma(wJu[a], eu, s);
+            if (a != 3) s = fma(wJv[a], ev, s);
+            acc[21 + a] = s;
+        }
+    }
+    acc[27] += w;
+}
+
+// a wave's share of a pass: the cells first + lane, first + stride + lane, ... below `end`.  A 64-cell trip without a live cell skips the Jacobian work
+template <bool BWD>
+DM_INLINE void soft_pass_cells(const FrameDev& F, const dm::Cam& K, const double* R, const double* dRdr, const double* t, int first, int end, int stride, double tau,
+                               double beta, double cut, bool fixed_w, double (&acc)[32]) {
+    const int lane = threadIdx.x & 63;
+    for (int base = first; base < end; base += stride) {
+        const int p = base + lane;
+        const bool in = p < end;
+        const int pc = in ? p : end - 1;
+        const double Mx = F.xyz[(size_t)pc * 3], My = F.xyz[(size_t)pc * 3 + 1], Mz = F.xyz[(size_t)pc * 3 + 2];
+        double u, v;
+        if (F.uv) {
+            u = F.uv[(size_t)pc * 2];
+            v = F.uv[(size_t)pc * 2 + 1];
+        } else {
+            const int row = pc / F.W;
+            u = (double)(float)(pc - row * F.W);
+            v = (double)(float)row;
+        }
+        SoftCell c;
+        const bool live = soft_cell(R, t, K, Mx, My, Mz, u, v, tau, beta, cut, c) && in;
+        if (__ballot(live) == 0ull) continue;
+        soft_accumulate<BWD>(c, live, dRdr, Mx, My, Mz, BWD ? soft_wprime_over_e(c, beta, fixed_w) : 0.0, acc);
+    }
+}
+
+DM_INLINE int soft_problem_frame(FrameDev& F, const int32_t* frame_of, int per_frame, int b) {
+    if (F.frames <= 1) return 0;
+    const int f = uniform_frame(clamp_frame(frame_of ? frame_of[b] : (per_frame > 0 ? b / per_frame : 0), F));
+    select_frame(F, f);
+    return f;
+}
+
+// One decision of the loop, after the pass at `trial` gave tot[]: -1 = go on (h, S, it updated, trial = the next pose to take a pass at), else the status
+// (h, S, it are the problem's output).  first: the pass at the start pose.  The same bits in every lane.
+DM_INLINE int soft_decide(bool first, const double* tot, double h[6], double trial[6], double& S, int& it, double min_soft, int max_iters, double step_tol) {
+    const double Sn = tot[27];
+    if (first) {
+        bool finite = true;
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            h[i] = trial[i];
+            finite = finite && (trial[i] - trial[i] == 0.0);
+        }
+        it = 0;
+        S = finite ? Sn : 0.0;
+        if (!finite) return SOFT_NONFINITE;
+        if (!(Sn >= min_soft)) return SOFT_FEW;
+    } else {
+        if (!(Sn >= S)) return SOFT_SCORE;
+        S = Sn;
+        it++;
+#pragma unroll
+        for (int i = 0; i < 6; i++) h[i] = trial[i];
+        if (it >= max_iters) return SOFT_MAXIT;
+    }
+    double A[36], d[6];
+    int q = 0;
+#pragma unroll
+    for (int a = 0; a < 6; a++)
+#pragma unroll
+        for (int c = a; c < 6; c++) { A[a * 6 + c] = tot[q]; A[c * 6 + a] = tot[q]; q++; }
+    if (!solve6_spd(A, tot + 21, d)) return SOFT_SINGULAR;
+    double num = 0.0, den = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) { num += d[i] * d[i]; den += h[i] * h[i]; }
+    if (sqrt(num) <= step_tol * (sqrt(den) + 2.220446049250313e-16)) return SOFT_CONVERGED;
+#pragma unroll
+    for (int i = 0; i < 6; i++) trial[i] = h[i] - d[i];
+    return -1;
+}
+
+DM_INLINE void soft_write_result(int b, int status, const double h[6], double S, int it, double* __restrict__ out_poses, double* __restrict__ soft_out,
+                                 int32_t* __restrict__ iters_out, int32_t* __restrict__ status_out) {
+#pragma unroll
+    for (int i = 0; i < 6; i++) out_poses[(size_t)b * 6 + i] = h[i];
+    if (soft_out) soft_out[b] = S;
+    if (iters_out) iters_out[b] = it;
+    if (status_out) status_out[b] = status;
+}
+
+// split form, the pass: workgroup (one wave) = one chunk of one problem's cells at poses[b * pose_stride .. + 6]; its 28 sums go to part[b][chunk][28]
+template <bool BWD>
+__global__ __launch_bounds__(64) void k_soft_pass(int B, const double* __restrict__ poses, int pose_stride, const int32_t* __restrict__ done,
+                                                  const int32_t* __restrict__ frame_of, int per_frame, int chunk, int nchunks, double tau, double beta, double cut,
+                                                  int fixed_w, double* __restrict__ part, FrameDev F) {
+    const int b = blockIdx.x / nchunks, ck = blockIdx.x - b * nchunks;
+    if (b >= B) return;
+    if (done && done[b]) return;  // a finished problem: one flag load
+    const int lane = threadIdx.x & 63;
+    soft_problem_frame(F, frame_of, per_frame, b);
+    __shared__ double s_red[32];
+    const dm::Cam K = make_cam_r(F);
+    double pose[6], R[9], dRdr[27];
+#pragma unroll
+    for (int i = 0; i < 6; i++) pose[i] = poses[(size_t)b * pose_stride + i];
+    dm::RodAux aux;
+    dm::rodrigues_R(pose, R, aux);
+    dm::rodrigues_J(aux, dRdr);
+    double acc[32];
+#pragma unroll
+    for (int i = 0; i < 32; i++) acc[i] = 0.0;
+    const int first = ck * chunk, end = min(F.P, first + chunk);
+    soft_pass_cells<BWD>(F, K, R, dRdr, pose + 3, first, end, 64, tau, beta, cut, fixed_w != 0, acc);
+    wave_allsum32(acc, s_red);
+    if (lane < SOFT_NACC) part[((size_t)b * nchunks + ck) * SOFT_NACC + lane] = s_red[lane];
+}
+
+// the chunk sums of problem b added in index order: lane l < 28 adds value l; the totals in s_tot for every lane
+DM_INLINE void soft_ordered_sum(const double* __restrict__ part, int b, int nchunks, double* s_tot) {
+    const int lane = threadIdx.x & 63;
+    if (lane < SOFT_NACC) {
+        const double* p = part + (size_t)b * nchunks * SOFT_NACC + lane;
+        double v = 0.0;
+        for (int ck = 0; ck < nchunks; ck++) v += p[(size_t)ck * SOFT_NACC];
+        s_tot[lane] = v;
+    }
+    wave_sync_lds();
+}
+
+// split form, the step: one wave per problem
+__global__ __launch_bounds__(64) void k_soft_step(int B, int first, const double* __restrict__ init_poses, const double* __restrict__ part, int nchunks,
+                                                  double* __restrict__ state, int32_t* __restrict__ done, int32_t* __restrict__ iters, double min_soft, int max_iters,
+                                                  double step_tol, double* __restrict__ out_poses, double* __restrict__ soft_out, int32_t* __restrict__ iters_out,
+                                                  int32_t* __restrict__ status_out) {
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    if (!first && done[b]) return;
+    const int lane = threadIdx.x & 63;
+    __shared__ double s_tot[32];
+    soft_ordered_sum(part, b, nchunks, s_tot);
+    double* st = state + (size_t)b * SOFT_STATE;
+    double h[6], trial[6], S = 0.0;
+    int it = 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        trial[i] = first ? init_poses[(size_t)b * 6 + i] : st[6 + i];
+        h[i] = first ? trial[i] : st[i];
+    }
+    if (!first) { S = st[12]; it = iters[b]; }
+    const int status = soft_decide(first != 0, s_tot, h, trial, S, it, min_soft, max_iters, step_tol);
+    if (lane != 0) return;
+    if (status >= 0) {
+        soft_write_result(b, status, h, S, it, out_poses, soft_out, iters_out, status_out);
+        done[b] = 1;
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) { st[i] = h[i]; st[6 + i] = trial[i]; }
+    st[12] = S;
+    iters[b] = it;
+    if (first) done[b] = 0;
+}
+
+// fused form: one workgroup per problem runs the whole loop; wave w takes the cells w * 64 + lane, + 256, ...; the waves' sums are added in wave order
+__global__ __launch_bounds__(64 * SOFT_FUSED_WAVES) void k_soft_fused(int B, const double* __restrict__ init_poses, const int32_t* __restrict__ frame_of,
+                                                                      int per_frame, double tau, double beta, double cut, double min_soft, int max_iters,
+                                                                      double step_tol, double* __restrict__ out_poses, double* __restrict__ soft_out,
+                                                                      int32_t* __restrict__ iters_out, int32_t* __restrict__ status_out, FrameDev F) {
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    const int wave = threadIdx.x >> 6;
+    soft_problem_frame(F, frame_of, per_frame, b);
+    __shared__ double s_part[SOFT_FUSED_WAVES][32];
+    __shared__ double s_tot[32];
+    const dm::Cam K = make_cam_r(F);
+    double h[6], trial[6], S = 0.0;
+    int it = 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) { trial[i] = init_poses[(size_t)b * 6 + i]; h[i] = trial[i]; }
+    int status = -1;
+    for (int k = 0; k <= max_iters && status < 0; k++) {
+        double R[9], dRdr[27], acc[32];
+        dm::RodAux aux;
+        dm::rodrigues_R(trial, R, aux);
+        dm::rodrigues_J(aux, dRdr);
+#pragma unroll
+        for (int i = 0; i < 32; i++) acc[i] = 0.0;
+        soft_pass_cells<false>(F, K, R, dRdr, trial + 3, wave * 64, F.P, 64 * SOFT_FUSED_WAVES, tau, beta, cut, false, acc);
+        __syncthreads();  // the readers of the previous totals are through
+        wave_allsum32(acc, s_part[wave]);
+        __syncthreads();
+        if (threadIdx.x < SOFT_NACC) {
+            double v = s_part[0][threadIdx.x];
+#pragma unroll
+            for (int w = 1; w < SOFT_FUSED_WAVES; w++) v += s_part[w][threadIdx.x];
+            s_tot[threadIdx.x] = v;
+        }
+        __syncthreads();
+        status = soft_decide(k == 0, s_tot, h, trial, S, it, min_soft, max_iters, step_tol);
+    }
+    if (threadIdx.x == 0) soft_write_result(b, status, h, S, it, out_poses, soft_out, iters_out, status_out);
+}
+
+// backward, the solve: one wave per problem.  H_b from the chunk sums of k_soft_pass<true>, q = H_b^-1 T_b^T dL_b, and the record the scatter reads
+__global__ __launch_bounds__(64) void k_soft_bwd_solve(int B, const double* __restrict__ ref_poses, const int32_t* __restrict__ frame_of, int per_frame,
+                                                       const double* __restrict__ part, int nchunks, double min_soft, const double* __restrict__ dL,
+                                                       const double* __restrict__ coef, double* __restrict__ rec, int32_t* __restrict__ rec_frame,
+                                                       int32_t* __restrict__ ok_out, FrameDev F) {
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    const int f = soft_problem_frame(F, frame_of, per_frame, b);
+    __shared__ double s_tot[32];
+    soft_ordered_sum(part, b, nchunks, s_tot);
+    double pose[6];
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        pose[i] = ref_poses[(size_t)b * 6 + i];
+        ok = ok && (pose[i] - pose[i] == 0.0);
+    }
+    ok = ok && (s_tot[27] >= min_soft);
+    double q6[6] = {0, 0, 0, 0, 0, 0}, R[9], dRdr[27];
+    if (ok) {
+        double A[36], T[9], d6[6], rhs[6];
+        int q = 0;
+#pragma unroll
+        for (int a = 0; a < 6; a++)
+#pragma unroll
+            for (int c = a; c < 6; c++) { A[a * 6 + c] = s_tot[q]; A[c * 6 + a] = s_tot[q]; q++; }
+        cv_to_jp6_jacobian_rot(pose, T);
+#pragma unroll
+        for (int i = 0; i < 6; i++) d6[i] = dL[(size_t)b * 6 + i];
+#pragma unroll
+        for (int j = 0; j < 3; j++) rhs[j] = T[j] * d6[0] + T[3 + j] * d6[1] + T[6 + j] * d6[2];
+        rhs[3] = d6[3]; rhs[4] = -d6[4]; rhs[5] = -d6[5];
+        ok = solve6_spd(A, rhs, q6);
+    }
+    if (lane != 0) return;
+    rec_frame[b] = ok ? f : -1;
+    if (ok_out) ok_out[b] = ok ? 1 : 0;
+    if (!ok) return;
+    dm::RodAux aux;
+    dm::rodrigues_R(pose, R, aux);
+    dm::rodrigues_J(aux, dRdr);
+    double* r = rec + (size_t)b * SOFT_REC;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        r[i] = R[i];
+        r[12 + i] = q6[0] * dRdr[i] + q6[1] * dRdr[9 + i] + q6[2] * dRdr[18 + i];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; i++) { r[9 + i] = pose[3 + i]; r[21 + i] = q6[3 + i]; }
+    r[24] = coef ? coef[b] : 1.0;
+    r[25] = 0.0;
+}
+
+// backward, the scatter: a lane owns one cell of one frame and adds the frame's problems in index order; grad_xyz of the cell is read once and, if a
+// problem gave it weight, written once
+__global__ __launch_bounds__(256) void k_soft_scatter(int B, int per_frame, int tiles, const double* __restrict__ rec, const int32_t* __restrict__ rec_frame,
+                                                      double tau, double beta, double cut, int fixed_w, double* __restrict__ grad_xyz, FrameDev F) {
+    const int f = uniform_frame(blockIdx.x / tiles), tile = blockIdx.x - f * tiles;
+    if (F.frames > 1) select_frame(F, f);
+    const int P = F.P, p = tile * 256 + threadIdx.x;
+    const bool in = p < P;
+    const int pc = in ? p : P - 1;
+    const dm::Cam K = make_cam_r(F);
+    const double Mx = F.xyz[(size_t)pc * 3], My = F.xyz[(size_t)pc * 3 + 1], Mz = F.xyz[(size_t)pc * 3 + 2];
+    double u, v;
+    if (F.uv) {
+        u = F.uv[(size_t)pc * 2];
+        v = F.uv[(size_t)pc * 2 + 1];
+    } else {
+        const int row = pc / F.W;
+        u = (double)(float)(pc - row * F.W);
+        v = (double)(float)row;
+    }
+    double* gp = grad_xyz + ((size_t)f * P + pc) * 3;
+    double g[3] = {gp[0], gp[1], gp[2]};
+    bool touched = false;
+    __shared__ double s_rec[SOFT_SCATTER_TILE * SOFT_REC];
+    __shared__ int s_f[SOFT_SCATTER_TILE];
+    const int b0 = per_frame > 0 ? f * per_frame : 0, b1 = per_frame > 0 ? min(B, b0 + per_frame) : B;
+    for (int bb = b0; bb < b1; bb += SOFT_SCATTER_TILE) {
+        const int n = min(SOFT_SCATTER_TILE, b1 - bb);
+        __syncthreads();
+        for (int i = threadIdx.x; i < n * SOFT_REC; i += 256) {
+            const int k = i / SOFT_REC;
+            s_rec[i] = (rec_frame[bb + k] == f) ? rec[(size_t)bb * SOFT_REC + i] : 0.0;  // a problem without a result has no record
+        }
+        if ((int)threadIdx.x < n) s_f[threadIdx.x] = rec_frame[bb + threadIdx.x];
+        __syncthreads();
+        for (int k = 0; k < n; k++) {
+            if (s_f[k] != f) continue;
+            const double* r = s_rec + k * SOFT_REC;
+            SoftCell c;
+            const bool live = soft_cell(r, r + 9, K, Mx, My, Mz, u, v, tau, beta, cut, c) && in;
+            if (!live) continue;
+            const double* Q = r + 12;
+            const double q0 = Q[0] * Mx + Q[1] * My + Q[2] * Mz, q1 = Q[3] * Mx + Q[4] * My + Q[5] * Mz, q2 = Q[6] * Mx + Q[7] * My + Q[8] * Mz;
+            const double wu = -c.tu * c.x, wv = -c.tv * c.y;
+            const double su = c.tu * (q0 - c.x * q2) + c.tu * r[21] + wu * r[23];  // (J_p q)
+            const double sv = c.tv * (q1 - c.y * q2) + c.tv * r[22] + wv * r[23];
+            const double k_rr = soft_wprime_over_e(c, beta, fixed_w != 0), rs = c.eu * su + c.ev * sv;
+            const double vu = c.w * su + k_rr * c.eu * rs, vv = c.w * sv + k_rr * c.ev * rs;  // M_p J_p q
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) {
+                const double gu = c.tu * (r[ch] - c.x * r[6 + ch]), gv = c.tv * (r[3 + ch] - c.y * r[6 + ch]);
+                g[ch] -= r[24] * (vu * gu + vv * gv);
+            }
+            touched = true;
+        }
+    }
+    if (in && touched) { gp[0] = g[0]; gp[1] = g[1]; gp[2] = g[2]; }
+}
+
+hipError_t refine_soft(hipStream_t st, int B, const double* init_poses, const int32_t* frame_of, int per_frame, double tau, double beta, double cut, double min_soft,
+                       int max_iters, double step_tol, bool fused, const SoftGeom& geom, void* scratch, double* out_poses, double* soft_out, int32_t* iters_out,
+                       int32_t* status_out, const FrameDev& F) {
+    if (B < 1 || F.P < 1 || max_iters < 1 || (long long)B * geom.nchunks > 0x7fffffffll) return hipErrorInvalidValue;
+    if (fused) {
+        hipLaunchKernelGGL(k_soft_fused, dim3((unsigned)B), dim3(64 * SOFT_FUSED_WAVES), 0, st, B, init_poses, frame_of, per_frame, tau, beta, cut, min_soft, max_iters,
+                           step_tol, out_poses, soft_out, iters_out, status_out, F);
+        return hipGetLastError();
+    }
+    char* s = static_cast<char*>(scratch);
+    double* part = reinterpret_cast<double*>(s);
+    double* state = reinterpret_cast<double*>(s + soft_off_state(B, geom));
+    int32_t* done = reinterpret_cast<int32_t*>(s + soft_off_done(B, geom));
+    int32_t* iters = reinterpret_cast<int32_t*>(s + soft_off_iters(B, geom));
+    const unsigned grid = (unsigned)B * (unsigned)geom.nchunks;
+    for (int k = 0; k <= max_iters; k++) {
+        // pass k is taken at the start pose (k = 0) or at the trial pose the step before it wrote; finished problems return after one flag load
+        hipLaunchKernelGGL(k_soft_pass<false>, dim3(grid), dim3(64), 0, st, B, k == 0 ? init_poses : state + 6, k == 0 ? 6 : SOFT_STATE,
+                           k == 0 ? (const int32_t*)nullptr : done, frame_of, per_frame, geom.chunk, geom.nchunks, tau, beta, cut, 0, part, F);
+        hipLaunchKernelGGL(k_soft_step, dim3((unsigned)B), dim3(64), 0, st, B, k == 0 ? 1 : 0, init_poses, part, geom.nchunks, state, done, iters, min_soft, max_iters,
+                           step_tol, out_poses, soft_out, iters_out, status_out);
+    }
+    return hipGetLastError();
+}
+
+hipError_t refine_soft_backward(hipStream_t st, int B, const double* ref_poses, const int32_t* frame_of, int per_frame, double tau, double beta, double cut,
+                                double min_soft, const double* dL, const double* coef, unsigned flags, const SoftGeom& geom, void* scratch, double* grad_xyz,
+                                int32_t* ok_out, const FrameDev& F) {
+    if (B < 1 || F.P < 1 || !dL || !grad_xyz || (long long)B * geom.nchunks > 0x7fffffffll) return hipErrorInvalidValue;
+    const int frames = F.frames > 1 ? F.frames : 1, tiles = (F.P + 255) / 256;
+    if ((long long)frames * tiles > 0x7fffffffll) return hipErrorInvalidValue;
+    char* s = static_cast<char*>(scratch);
+    double* part = reinterpret_cast<double*>(s);
+    double* rec = reinterpret_cast<double*>(s + soft_off_rec(B, geom));
+    int32_t* recf = reinterpret_cast<int32_t*>(s + soft_off_recf(B, geom));
+    const int fixed_w = (flags & 1u) ? 1 : 0;
+    hipLaunchKernelGGL(k_soft_pass<true>, dim3((unsigned)B * (unsigned)geom.nchunks), dim3(64), 0, st, B, ref_poses, 6, (const int32_t*)nullptr, frame_of, per_frame,
+                       geom.chunk, geom.nchunks, tau, beta, cut, fixed_w, part, F);
+    hipLaunchKernelGGL(k_soft_bwd_solve, dim3((unsigned)B), dim3(64), 0, st, B, ref_poses, frame_of, per_frame, part, geom.nchunks, min_soft, dL, coef, rec, recf, ok_out,
+                       F);
+    hipLaunchKernelGGL(k_soft_scatter, dim3((unsigned)(frames * tiles)), dim3(256), 0, st, B, frame_of ? 0 : per_frame, tiles, rec, recf, tau, beta, cut, fixed_w, grad_xyz,
+                       F);
+    return hipGetLastError();
+}
+
 }  // namespace dk

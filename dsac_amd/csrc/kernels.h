@@ -287,6 +287,21 @@ hipError_t refine_fd_finish(hipStream_t st, const FdLists& L, const double* rep_
 hipError_t refine_gn(hipStream_t st, int B, const double* ref_poses, const int32_t* frame_of, int per_frame, const int32_t* perm, int steps, const int32_t* rows,
                      int max_inl, int min_inl, float thr, const double* dL, const double* coef, double* grad_xyz, int32_t* cells, double* J_obj, int32_t* n_out,
                      const FrameDev& F);
+// ---- soft-inlier refinement over the whole map (dsac_refine_soft / dsac_refine_soft_backward, include/dsac_hip.h) ----
+// chunk geometry of the split form's passes: computed once per call (it depends on the map alone) and handed to the scratch sizing and to the launch
+struct SoftGeom { int chunk, nchunks; };
+SoftGeom refine_soft_geom(int P);
+size_t refine_soft_scratch_bytes(int B, const SoftGeom& g);
+bool refine_soft_auto_fused(int P);  // what "refine_soft_form" -1 takes
+// fused: one launch of B workgroups; else max_iters + 1 pass and step launches.  soft_out / iters_out / status_out may be nullptr.  Problem b: frame frame_of[b]
+// (clamped) or b / per_frame (per_frame 0: frame 0)
+hipError_t refine_soft(hipStream_t st, int B, const double* init_poses, const int32_t* frame_of, int per_frame, double tau, double beta, double cut, double min_soft,
+                       int max_iters, double step_tol, bool fused, const SoftGeom& geom, void* scratch, double* out_poses, double* soft_out, int32_t* iters_out,
+                       int32_t* status_out, const FrameDev& F);
+// pass (H_b), solve (q_b), scatter (a lane per cell, the frame's problems in index order): three launches, no atomics.  flags bit 0: fixed weights
+hipError_t refine_soft_backward(hipStream_t st, int B, const double* ref_poses, const int32_t* frame_of, int per_frame, double tau, double beta, double cut,
+                                double min_soft, const double* dL, const double* coef, unsigned flags, const SoftGeom& geom, void* scratch, double* grad_xyz,
+                                int32_t* ok_out, const FrameDev& F);
 
 // ---- k_loss.hip ------------------------------------------------------------------------------------
 // gt_stride: 0 = one ground truth (6 doubles) for all estimates, 6 = one per estimate

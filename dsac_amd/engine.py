@@ -771,6 +771,39 @@ class Engine:
                                                      float(thr), ptr(dL), ptr(coef), ptr(grad), ptr(cells), ptr(J_obj), ptr(n)))
         return (grad, n, cells, J_obj) if want_jacobians else (grad, n)
 
+    @staticmethod
+    def _soft_cut(tau, beta, cut):
+        return min(100.0, float(tau) + 16.0 / float(beta)) if cut is None else float(cut)
+
+    def refineSoft(self, init_poses, frame_of=None, tau=10.0, beta=0.5, cut=None, min_soft=50.0, max_iters=20, step_tol=1e-6):
+        """dsac_refine_soft: Gauss-Newton re-weighted by the soft-inlier weights sigmoid(beta (tau - e)) over every cell of the map, from B start poses (cv, B x 6).
+        cut: the residual at and beyond which a cell has weight zero (default tau + 16 / beta, at most 100).  Returns (poses B x 6, soft B, iters B, status B);
+        status indexes capi.SOFT_STATUS.  A refined pose never scores below its start pose."""
+        init = np.ascontiguousarray(np.asarray(init_poses, dtype=np.float64).reshape(-1, 6))
+        B = int(init.shape[0])
+        frame_of = None if frame_of is None else np.ascontiguousarray(np.asarray(frame_of, dtype=np.int32).reshape(B))
+        out, soft = np.zeros((B, 6)), np.zeros(B)
+        iters, status = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        check(self._ctx, lib.dsac_refine_soft(self._ctx, B, ptr(init), ptr(frame_of), float(tau), float(beta), self._soft_cut(tau, beta, cut), float(min_soft),
+                                              int(max_iters), float(step_tol), ptr(out), ptr(soft), ptr(iters), ptr(status)))
+        return out, soft, iters, status
+
+    def dRefineSoft(self, ref_poses, dL, coef=None, frame_of=None, tau=10.0, beta=0.5, cut=None, min_soft=50.0, grad=None, fixed_weights=False):
+        """dsac_refine_soft_backward: sum_b coef[b] dL[b]^T d(jp pose b) / d(scene coordinates) from the linearised fixed-point condition of refineSoft, ADDED to
+        grad (frames * P x 3, zeros when not given).  dL: B x 6 (jp: maxLossBatch(..., want_grad=True)["grad"]).  fixed_weights: drop the derivative of the
+        weights (DSAC*).  Returns (grad, ok B); ok[b] = 0: problem b has no result and contributed nothing."""
+        ref = np.ascontiguousarray(np.asarray(ref_poses, dtype=np.float64).reshape(-1, 6))
+        B = int(ref.shape[0])
+        dL = np.ascontiguousarray(np.asarray(dL, dtype=np.float64).reshape(B, 6))
+        coef = None if coef is None else np.ascontiguousarray(np.asarray(coef, dtype=np.float64).reshape(B))
+        frame_of = None if frame_of is None else np.ascontiguousarray(np.asarray(frame_of, dtype=np.int32).reshape(B))
+        if grad is None:
+            grad = np.zeros((getattr(self, "frames", 1) * self.P, 3))
+        ok = np.zeros(B, np.int32)
+        check(self._ctx, lib.dsac_refine_soft_backward(self._ctx, B, ptr(ref), ptr(frame_of), float(tau), float(beta), self._soft_cut(tau, beta, cut), float(min_soft),
+                                                       ptr(dL), ptr(coef), 1 if fixed_weights else 0, ptr(grad), ptr(ok)))
+        return grad, ok
+
     def maxLossBatch(self, est_cv6, gt_jp6, want_grad=False):
         """maxLoss [+ dLossMax] of B estimates against one ground truth (losses of expectedMaxLoss, core/cnn.h:137-150)."""
         est = np.ascontiguousarray(np.asarray(est_cv6, dtype=np.float64).reshape(-1, 6))
@@ -806,18 +839,29 @@ class Engine:
         return int(idx[0]), float(e[0]), g
 
     def processImageDSAC(self, N=256, seed=1305, perm=None, gt_jp6=None, thr=10.0, inlierCount=100, minInliers=50, tau=10.0, beta=0.5, alpha=0.1,
-                         score_fn=None, draw_u=None, sets=None, max_tries=1 << 20):
+                         score_fn=None, draw_u=None, sets=None, max_tries=1 << 20, refine="walk", soft_iters=20, soft_step_tol=1e-6):
         """Forward pass of the DSAC variant's processImage (core/cnn.h:1000-1240): N hypotheses, scores (soft-inlier count or
-        score_fn on the error images), softmax, probabilistic selection, refinement of ALL hypotheses, expected loss."""
+        score_fn on the error images), softmax, probabilistic selection, refinement of ALL hypotheses, expected loss.
+        refine: "walk" = the reference's refinement (K6: permutation walk, hard threshold, at most inlierCount cells); "soft" = refineSoft over the whole map with
+        the score's tau and beta and min_soft = minInliers (no perm needed; refSteps holds the accepted steps, refStatus the statuses, inlierMaps is None)."""
+        if refine not in ("walk", "soft"):
+            raise ValueError("dsac_amd: refine is \"walk\" or \"soft\", got %r" % (refine,))
         poses, sets_out, ok = self.sample(N, seed=seed, thr=thr, max_tries=max_tries, sets=sets)
         err = np.zeros((N, self.P), np.float32) if score_fn is not None else None
         soft = np.zeros(N)
         self.reproject(poses, err=err, soft=soft, tau=tau, beta=beta)
         scores, scale = (np.ascontiguousarray(score_fn(err.reshape(N, self.H, self.W)), dtype=np.float64), 1.0) if score_fn is not None else (soft, alpha)
         w, ent, _ = self.softMax(scores, scale)
-        ref, sd, maps = self.refineAll(poses, perm, sets=sets_out, max_inl=inlierCount, min_inl=minInliers, thr=float(int(thr)), want_inlier_maps=True)
+        status = None
+        if refine == "soft":
+            ref, _, sd, status = self.refineSoft(poses, tau=tau, beta=beta, min_soft=float(minInliers), max_iters=soft_iters, step_tol=soft_step_tol)
+            maps = None
+        else:
+            ref, sd, maps = self.refineAll(poses, perm, sets=sets_out, max_inl=inlierCount, min_inl=minInliers, thr=float(int(thr)), want_inlier_maps=True)
         out = dict(hyps=poses, sampledPoints=sets_out, ok=ok, scores=scores, score_scale=scale, sfScores=w, sfEntropy=float(ent[0]), hypIdx=self.selectDSAC(w, np.zeros(N), draw_u, want_gradients=False)[0],
-                   refHyps=ref, refSteps=sd, inlierMaps=maps, pixelIdxs=np.ascontiguousarray(perm, dtype=np.int32), diffMaps=err)
+                   refHyps=ref, refSteps=sd, inlierMaps=maps, pixelIdxs=None if perm is None else np.ascontiguousarray(perm, dtype=np.int32), diffMaps=err)
+        if status is not None:
+            out["refStatus"] = status
         if gt_jp6 is not None:
             L = self.maxLossBatch(ref, gt_jp6)
             hyp_idx, e_loss, g = self.selectDSAC(w, L["loss"], draw_u)  # selection, expected loss and the score gradients: one device launch
@@ -866,9 +910,10 @@ class Engine:
         726-768), whose result the reference re-orders to row-major, i.e. no index quirk here.
         refine_grad: "fd" = the reference's finite differences of the refinement (every 1 / sub_sample-th inlier cell, times skip); "gn" = the Gauss-Newton
         linearisation of every hypothesis' last refinement step (dsac_refine_gn_backward: one launch, every cell of the step's list, no J_set term -- under
-        the linearisation the optimum does not depend on where the refinement started)."""
-        if refine_grad not in ("fd", "gn"):
-            raise ValueError("dsac_amd: refine_grad is \"fd\" or \"gn\", got %r" % (refine_grad,))
+        the linearisation the optimum does not depend on where the refinement started); "soft" = the linearised fixed point of the soft-inlier refinement
+        (dsac_refine_soft_backward with the score's tau and beta, min_soft = minInliers: every cell that carries weight, no permutation)."""
+        if refine_grad not in ("fd", "gn", "soft"):
+            raise ValueError("dsac_amd: refine_grad is \"fd\", \"gn\" or \"soft\", got %r" % (refine_grad,))
         w, sets, ref = fwd["sfScores"], fwd["sampledPoints"], fwd["refHyps"]
         N = len(w)
         grad = np.zeros((self.P, 3))
@@ -877,6 +922,8 @@ class Engine:
         if len(sel) and refine_grad == "gn":  # the list of a hypothesis' last step: the row that step walked
             rows = np.maximum(np.asarray(fwd["refSteps"], dtype=np.int64)[sel] - 1, 0)
             self.dRefineGN(ref[sel], fwd["pixelIdxs"], rows=rows, max_inl=inlierCount, min_inl=minInliers, thr=float(int(thr)), dL=dL[sel], coef=w[sel], grad=grad)
+        elif len(sel) and refine_grad == "soft":  # the fixed point of refineSoft, every cell that carries weight (processImageDSAC(refine="soft"))
+            self.dRefineSoft(ref[sel], dL[sel], coef=w[sel], tau=tau, beta=beta, min_soft=float(minInliers), grad=grad)
         elif len(sel):  # one batched launch for all hypotheses that carry weight (train_ransac.cpp:318)
             J_set, n_obj, px, J_obj = self.dRefineSets(sets[sel], fwd["pixelIdxs"], fwd["inlierMaps"][sel], max_inl=inlierCount, min_inl=minInliers,
                                                        thr=float(int(thr)), sub_sample=sub_sample)

@@ -139,6 +139,7 @@ DSAC_API int dsac_device_info(dsac_ctx* ctx, int* cus, int* clock_khz, uint64_t*
  *                 counts and poses bit for bit; 128 whole-map walks on 640 x 480 15.3 -> 5.4 ms (profiles/r06_k6_walk_v2.txt).  With 0, calls of >= 32 problems on a
  *                 map of >= 16 384 cells (and no perturbed cells / fused loss) run every step as a scan of the step's cells + one LM launch instead (0.65 ms for the
  *                 same 128 walks, bit-identical again; "k6_walk_exact", "k6_scan_tune" above; profiles/r06_k6_walk.txt); a non-zero value keeps the fused kernel
+ *   "refine_soft_form"  the loop of dsac_refine_soft: -1 (default) = fused up to 4 800 cells (the measured crossover, profiles/refine_soft_ab.txt), else split; 0 = split; 1 = fused (see dsac_refine_soft)
  *   "refstream_mode"  see dsac_sample_refstream
  *   "pi_refstream", "pi_refstream_discard0", "pi_refstream_attempts"   see dsac_sample_refstream_frames
  *   "k1_wpb", "k1_prio", "k1_hpw", "k1_minw"   K1 waves per workgroup (1), wave priority (3), hypotheses per wave (1), register budget in waves per SIMD (1)
@@ -606,6 +607,51 @@ DSAC_API int dsac_refine_fd_sets_frames(dsac_ctx* ctx, int M, const int32_t* set
 DSAC_API int dsac_refine_gn_backward(dsac_ctx* ctx, int B, const double* ref_poses, const int32_t* frame_of_or_null, const int32_t* perm, int steps,
                             const int32_t* rows_or_null, int max_inl, int min_inl, float thr, const double* dL_jp6_or_null, const double* coef_or_null,
                             double* grad_xyz_or_null, int32_t* cells_or_null, double* J_obj_or_null, int32_t* n_out_or_null);
+/* Soft-inlier refinement over the whole map: Gauss-Newton re-weighted by the weights of the library's own score, over ALL cells of the frame -- the refinement
+ * of DSAC++ / DSAC*.  No permutation, no cap on the number of cells, no hard threshold.  Definitions (shared with dsac_refine_soft_backward), for a cv pose h
+ * on frame f and a cell p, all in double with the formulas of the Levenberg-Marquardt solve (X_p widened from float):
+ *   E = R(h) X_p + t;  z = 1 / E_z if E_z != 0, else 1 (no depth rule, as in K2 and K6);  r_p = (fx E_x z + cx - u_p, fy E_y z + cy - v_p);  e_p = |r_p|
+ *   J_p = d r_p / d h (2 x 6) and G_p = d r_p / d X_p (2 x 3), exactly as in dsac_refine_gn_backward
+ *   weight    w_p = 1 / (1 + exp(-beta (tau - e_p))) evaluated in double; w_p = 0 exactly where e_p is not finite or e_p >= cut.  A cell of weight zero
+ *             contributes nothing anywhere
+ *   pass      at h: S(h) = sum w_p, A(h) = sum w_p J_p^T J_p, g(h) = sum w_p J_p^T r_p over all H*W cells of the frame (the uv table or the implicit grid)
+ * dsac_refine_soft, per problem b with start pose h0 = init_poses[b]:
+ *   1. a non-finite entry of h0: status DSAC_SOFT_NONFINITE, out = h0 (soft_out 0, iters_out 0)
+ *   2. a pass at h = h0; unless S >= min_soft: status DSAC_SOFT_FEW, out = h0
+ *   3. at most max_iters times: delta = A^-1 g by the L D L^T solve of the Levenberg-Marquardt code, a non-positive pivot: DSAC_SOFT_SINGULAR;
+ *      |delta| <= step_tol (|h| + DBL_EPSILON): DSAC_SOFT_CONVERGED, delta is not applied;  otherwise a pass at h' = h - delta: unless S(h') >= S(h) (a NaN
+ *      compares false) DSAC_SOFT_SCORE and h is kept, else h <- h' (the pass at h' is reused)
+ *   4. after max_iters accepted steps: DSAC_SOFT_MAXIT
+ *   5. out_poses[b] = h, soft_out[b] = S(h), iters_out[b] = accepted steps, status_out[b] = the status
+ * A refined pose therefore never scores below the pose it started from, and the output pose is always one at which a pass was taken.
+ * Frames, frame_of and per-frame cameras as in dsac_refine_gn_backward (without frame_of B % frames == 0 on a batch; fx != fy is allowed).  Host or device
+ * pointers; with device pointers the call only enqueues.  soft_out, iters_out and status_out may be NULL.
+ * Determinism is part of the contract: two calls give the same bits in every output.  Per-chunk (per-wave) partial sums are added in index order and no
+ * floating-point atomics are used.  dsac_set_option("refine_soft_form"): -1 (default) = by the map size, 0 = split (a pass kernel on cell chunks x problems and a
+ * one-wave step kernel per problem, max_iters + 1 launches of each, finished problems return after one flag load), 1 = fused (one workgroup per problem runs the
+ * whole loop in one launch; for small maps).  Both forms work at any map size; they agree to rounding (their sums have different orders), not bit for bit.
+ * DSAC_ERR_INVALID with nothing enqueued: B < 1, max_iters outside 1 .. 64, cut outside (0, 100], beta <= 0, a non-finite tau, beta, min_soft or step_tol,
+ * step_tol < 0, NULL poses, B % frames != 0 on a batch without frame_of.  DSAC_ERR_NO_FRAME without a frame. */
+enum dsac_soft_status { DSAC_SOFT_CONVERGED = 0, DSAC_SOFT_MAXIT = 1, DSAC_SOFT_SCORE = 2, DSAC_SOFT_FEW = 3, DSAC_SOFT_SINGULAR = 4, DSAC_SOFT_NONFINITE = 5 };
+DSAC_API int dsac_refine_soft(dsac_ctx* ctx, int B, const double* init_poses, const int32_t* frame_of_or_null, double tau, double beta, double cut, double min_soft,
+                     int max_iters, double step_tol, double* out_poses, double* soft_out_or_null, int32_t* iters_out_or_null, int32_t* status_out_or_null);
+/* Its backward: the linearisation of the fixed-point condition sum w(e_p) J_p^T r_p = 0 at h_b = ref_poses[b].  The derivatives of the weights are kept, the
+ * second derivatives of the projection are dropped.  With w' = -beta w (1 - w) and M_p = w_p I + (w'_p / e_p) r_p r_p^T (w_p I where e_p = 0):
+ *   H_b = sum J_p^T M_p J_p;   d h / d X_p = -H_b^-1 J_p^T M_p G_p;   the output is mapped through T_b = d cv_to_jp6 / d cv6 as in dsac_refine_gn_backward:
+ *   grad_xyz[f_b * H*W + p] += coef[b] * dL[b]^T T_b d h / d X_p for every cell with w_p > 0   (grad_xyz: frames x H*W x 3 doubles, ACCUMULATED into)
+ * flags bit 0, DSAC_SOFT_BWD_FIXED_WEIGHTS: M_p = w_p I, the convention of DSAC*.  Dropping the second-order term is part of the definition: against central
+ * differences of a converged re-weighted solve on a 40 x 40 map the result deviates, relative to the largest entry, by 2.6e-4 without noise and by 1.1 % / 1.3 % at
+ * 5 / 20 mm of noise with the weight derivatives (4.0e-4 / 5.7 % / 65 % with fixed weights; tests/test_refine_soft_ref_cpu.py).  With the weight derivatives H_b need not be positive definite.
+ * No result -- ok_out[b] = 0 and problem b contributes nothing: a non-finite entry of ref_poses[b], S(h_b) >= min_soft false, a non-positive pivot in the
+ * L D L^T factorisation of H_b.  Otherwise ok_out[b] = 1.  There is no per-cell Jacobian output; unit dL recover the rows.
+ * Three launches: a pass (H_b), a solve (q_b = H_b^-1 T_b^T dL_b), and a scatter in which one lane owns one cell of one frame and adds that frame's problems in
+ * index order: every cell of grad_xyz is read once and, where a problem gave it weight, written once.  No atomics: two calls give the same bits.
+ * dL is B x 6 (jp, dsac_loss_batch's J6), coef B or NULL for 1.  Host or device pointers; with device pointers the call only enqueues.
+ * DSAC_ERR_INVALID with nothing enqueued: as dsac_refine_soft (B, cut, beta, non-finite tau / beta / min_soft, NULL poses, B % frames), NULL dL or grad_xyz, flag bits
+ * other than bit 0.  DSAC_ERR_NO_FRAME without a frame. */
+#define DSAC_SOFT_BWD_FIXED_WEIGHTS 1u
+DSAC_API int dsac_refine_soft_backward(dsac_ctx* ctx, int B, const double* ref_poses, const int32_t* frame_of_or_null, double tau, double beta, double cut, double min_soft,
+                              const double* dL_jp6, const double* coef_or_null, unsigned flags, double* grad_xyz, int32_t* ok_out_or_null);
 /* maxLoss / dLossMax for B estimates against one ground truth: the losses[] of expectedMaxLoss core/cnn.h:137-150 and
  * the per-hypothesis dLossMax of core/train_ransac.cpp:345-349.  out4 is B x 4, J6 B x 6 (layouts of dsac_loss). */
 DSAC_API int dsac_loss_batch(dsac_ctx* ctx, int B, const double* est_cv6, const double* gt_jp6, double* out4, double* J6_or_null);
