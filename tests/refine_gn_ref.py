@@ -20,7 +20,24 @@ of these matrices is far from its worst case, kernel and restatement agree to ab
 """
 import numpy as np
 
-from dsac_amd import synth
+
+def _load_synth():
+    """dsac_amd.synth, the frame generator: plain numpy.  The package refuses to import without its built library, and the CPU tests of the restatements must run
+    without one: then the module is loaded from its file."""
+    try:
+        from dsac_amd import synth
+        return synth
+    except ImportError:
+        import importlib.util
+        import os
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dsac_amd", "synth.py")
+        spec = importlib.util.spec_from_file_location("dsac_amd_synth", path)
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        return mod
+
+
+synth = _load_synth()
 
 EPS = 2.0 ** -52
 COND_MAX = 1.4e8
@@ -126,7 +143,8 @@ def jacobians(h, X, uv, cam, variant=None):
     R = synth.rodrigues(h[:3])
     Jl = so3_left_jacobian(h[:3])
     Xc = X @ R.T + h[3:]
-    z = 1.0 / Xc[:, 2]
+    with np.errstate(divide="ignore"):
+        z = np.where(Xc[:, 2] != 0, 1.0 / Xc[:, 2], 1.0)  # no depth rule: a cell on the camera plane is projected with z = 1, as in K2 and K6
     x, y = Xc[:, 0] * z, Xc[:, 1] * z
     tu, tv = fx * z, fy * z
     r = np.stack([x * fx + cx - uv[:, 0].astype(np.float64), y * fy + cy - uv[:, 1].astype(np.float64)], -1)

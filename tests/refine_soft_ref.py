@@ -21,8 +21,7 @@ WRONG_VARIANTS are one-term mistakes that tests/test_refine_soft_ref_cpu.py show
 """
 import numpy as np
 
-from dsac_amd import synth
-from refine_gn_ref import cv_to_jp6_jacobian, grid_uv, inverse_ld, jacobians
+from refine_gn_ref import cv_to_jp6_jacobian, grid_uv, inverse_ld, jacobians, synth
 
 EPS = 2.0 ** -52
 COND_MAX = 1.4e8

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import refine_soft_ref as sr
-from dsac_amd import synth
+from refine_gn_ref import synth
 
 
 @pytest.fixture(scope="module")
