@@ -63,6 +63,10 @@ struct dsac_ctx {
     // guided sampling (dsac_set_sampling_weights): the table (frames x P uint64), the per-frame records (T, n, S, the maximum), the context's copy of the weights
     // (the gradient reads their values) and the build's per-tile scratch.  k1.guide_cdf / k1.guide_meta point at them while weights are active, else both are NULL
     DevBuf guide_cdf, guide_coarse, guide_meta, guide_w, guide_scratch;
+    // RGB-D (dsac_set_camera_points): the canonical copy of the measured camera-frame points (frames x P x 3, NaN in every cell that is not VALID) and per frame
+    // the VALID count and the first VALID cell.  have_cam: points are set for the current frames; every set-frame call clears it, as it clears the weights
+    DevBuf cam_xyz, cam_meta, rgbd_rec, rgbd_soft_part, rgbd_scratch;
+    bool have_cam = false;
 
     // scratch, one buffer per role so that calls can be chained without aliasing
     DevBuf rs_states, rs_scratch, rs_small, k6_scratch;  // the reference's random streams (dsac_refstream_init) and the scratch of a sampling window
@@ -626,6 +630,7 @@ void dsac_destroy(dsac_ctx* c) {
     if (c->aux2) (void)hipStreamSynchronize(c->aux2);
     c->frame_xyz.release(); c->frame_uv.release(); c->cams_d.release();
     c->guide_cdf.release(); c->guide_coarse.release(); c->guide_meta.release(); c->guide_w.release(); c->guide_scratch.release();
+    c->cam_xyz.release(); c->cam_meta.release(); c->rgbd_rec.release(); c->rgbd_soft_part.release(); c->rgbd_scratch.release();
     c->staged.release(); c->staged_lo.release(); c->staged_split.release(); c->rs_states.release(); c->rs_scratch.release(); c->rs_small.release(); c->k6_scratch.release(); c->soft_scratch.release(); c->soft_part.release(); c->bwd_staged.release(); c->dRdH.release();
     c->grad_part.release(); c->g12_part.release(); c->g6.release();
     for (auto& s : c->slots) s.release();
@@ -770,6 +775,7 @@ static int set_frames_common(dsac_ctx* c, int frames, const float* xyz, const fl
     }
     c->k1.guide_cdf = nullptr;  // the sampling weights belong to the frames they were set for
     c->k1.guide_meta = nullptr;
+    c->have_cam = false;        // ... and so do the camera points (dsac_set_camera_points)
     c->F.xyz = new_xyz;
     c->F.uv = new_uv;
     c->F.H = H; c->F.W = W; c->F.P = (int)P1;
@@ -1506,6 +1512,7 @@ int dsac_get_option(dsac_ctx* c, const char* key, int* value) {
     else if (k == "pi_defer_tail") *value = c->pi_defer_tail;
     else if (k == "k1_cus") *value = c->k1_cus;
     else if (k == "sampling_weights") *value = (c->have_frame && guided(c)) ? 1 : 0;  // read-only: sampling weights are active (dsac_set_sampling_weights)
+    else if (k == "camera_points") *value = (c->have_frame && c->have_cam) ? 1 : 0;  // read-only: camera points are set (dsac_set_camera_points)
     else if (k == "frame_cams") *value = (c->have_frame && c->F.cams) ? 1 : 0;  // read-only: the current frames carry one camera each (dsac_set_frames_cams)
     else return fail(c, DSAC_ERR_INVALID, "dsac_get_option: unknown key '%s'", key);
     return DSAC_OK;
@@ -2647,6 +2654,133 @@ int dsac_path1_and_softmax_backward(dsac_ctx* c, int N, const double* v6, const 
     ARG_TRY(out_arg(c, grad_xyz, (size_t)frames * P * 3, &d_grad, /*preload=*/true));
     ARG_TRY(out_arg(c, g, (size_t)N, &d_g));
     HIP_TRY(c, dk::path1_softmax_backward(c->stream, N / frames, c->F.P, d_v6, d_w, d_poses, d_sets, d_dpnp, d_grad, d_g, 1.0, frames));
+    return end_call(c);
+}
+
+// ---- RGB-D localisation: measured camera-frame points next to the scene coordinates (include/dsac_hip.h has the contract; k_rgbd.hip the kernels) ----------
+static int rgbd_check(dsac_ctx* c, const char* who) {
+    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "%s: ctx is NULL", who);
+    if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "%s: no frame set", who);
+    if (!c->have_cam) return fail(c, DSAC_ERR_INVALID, "%s: no camera points are set for the current frame(s) (dsac_set_camera_points)", who);
+    return DSAC_OK;
+}
+
+int dsac_set_camera_points(dsac_ctx* c, const float* cam_xyz_or_null) {
+    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_set_camera_points: ctx is NULL");
+    if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "dsac_set_camera_points: no frame set (the points belong to the frames currently set)");
+    if (!cam_xyz_or_null) {
+        c->have_cam = false;
+        return DSAC_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the copy is touched on the context's stream only; a host pointer goes through a staging slot like every host argument: the tail is joined then
+    begin_call(c, /*keep_tail=*/is_device_ptr(cam_xyz_or_null, c));
+    const int frames = c->F.frames > 1 ? c->F.frames : 1;
+    if (frames > 65535) return fail(c, DSAC_ERR_INVALID, "dsac_set_camera_points: at most 65 535 frames");
+    const size_t cells = (size_t)frames * (size_t)c->F.P;
+    const float* d_src;
+    ARG_TRY(in_arg(c, cam_xyz_or_null, cells * 3, &d_src));
+    // buffers that have to grow are replaced (hipFree waits for the device); a failed allocation leaves the points cleared
+    c->have_cam = false;
+    HIP_TRY(c, c->cam_xyz.reserve(cells * 3 * sizeof(float)));
+    HIP_TRY(c, c->cam_meta.reserve((size_t)frames * 2 * sizeof(int32_t)));
+    HIP_TRY(c, dk::rgbd_set_points(c->stream, d_src, c->F, c->cam_xyz.as<float>(), c->cam_meta.as<int32_t>()));
+    c->have_cam = true;
+    return DSAC_OK;
+}
+
+int dsac_get_camera_points(dsac_ctx* c, float* cam_xyz_out_or_null, int32_t* valid_out_or_null) {
+    ARG_TRY(rgbd_check(c, "dsac_get_camera_points"));
+    HIP_TRY(c, hipSetDevice(c->device));
+    begin_call(c);
+    const int frames = c->F.frames > 1 ? c->F.frames : 1;
+    const size_t cells = (size_t)frames * (size_t)c->F.P;
+    float* d_out;
+    int32_t* d_cnt;
+    ARG_TRY(out_arg(c, cam_xyz_out_or_null, cells * 3, &d_out));
+    ARG_TRY(out_arg(c, valid_out_or_null, (size_t)frames, &d_cnt));
+    if (d_out) HIP_TRY(c, hipMemcpyAsync(d_out, c->cam_xyz.p, cells * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    // the counts are the first int32 of every frame's record
+    if (d_cnt) HIP_TRY(c, hipMemcpy2DAsync(d_cnt, sizeof(int32_t), c->cam_meta.p, 2 * sizeof(int32_t), sizeof(int32_t), (size_t)frames, hipMemcpyDeviceToDevice, c->stream));
+    return end_call(c);
+}
+
+int dsac_sample_rgbd(dsac_ctx* c, int N, uint64_t seed, const int32_t* sets_or_null, float thr, int max_tries, double* poses, int32_t* sets_out, uint8_t* ok) {
+    const char* who = "dsac_sample_rgbd";
+    ARG_TRY(rgbd_check(c, who));
+    ARG_TRY(guide_refuse(c, who, "guided sampling with camera points is not built"));
+    const int frames = c->F.frames > 1 ? c->F.frames : 1;
+    if (frames > 1 && (sets_or_null || N % frames != 0))
+        return fail(c, DSAC_ERR_INVALID, "%s: with a frame batch N must be frames x (hypotheses per frame) and the sets are drawn here (given sets are evaluated frame by "
+                                         "frame: dsac_set_frame + dsac_set_camera_points + %s)", who, who);
+    if (N < 0 || !poses || !sets_out || !ok) return fail(c, DSAC_ERR_INVALID, "%s: N >= 0 and poses/sets_out/ok must be non-NULL", who);
+    if (N == 0) return DSAC_OK;
+    if (!sets_or_null && max_tries <= 0) return fail(c, DSAC_ERR_INVALID, "%s: max_tries must be > 0", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    begin_call(c);
+    const int32_t* d_sets_in;
+    double* d_poses;
+    int32_t* d_sets_out;
+    uint8_t* d_ok;
+    ARG_TRY(in_arg(c, sets_or_null, (size_t)N * 3, &d_sets_in));
+    ARG_TRY(out_arg(c, poses, (size_t)N * 6, &d_poses));
+    ARG_TRY(out_arg(c, sets_out, (size_t)N * 3, &d_sets_out));
+    ARG_TRY(out_arg(c, ok, (size_t)N, &d_ok));
+    HIP_TRY(c, dk::rgbd_sample(c->stream, N, seed, d_sets_in, c->F, c->cam_xyz.as<float>(), c->cam_meta.as<int32_t>(), (double)thr, max_tries, d_poses, d_sets_out, d_ok,
+                               frames > 1 ? N / frames : 0));
+    return end_call(c);
+}
+
+int dsac_score_rgbd(dsac_ctx* c, int N, const double* poses, float clampv, float* err_or_null, float tau, float beta, double* soft_or_null) {
+    const char* who = "dsac_score_rgbd";
+    ARG_TRY(rgbd_check(c, who));
+    const int frames = c->F.frames > 1 ? c->F.frames : 1;
+    if (N < 0 || !poses) return fail(c, DSAC_ERR_INVALID, "%s: N >= 0 and poses must be non-NULL", who);
+    if (frames > 1 && N % frames != 0) return fail(c, DSAC_ERR_INVALID, "%s: with a frame batch N must be frames x (hypotheses per frame), got %d for %d frames", who, N, frames);
+    if (N == 0 || (!err_or_null && !soft_or_null)) return DSAC_OK;
+    if (err_or_null && reinterpret_cast<uintptr_t>(err_or_null) % 4 != 0) return fail(c, DSAC_ERR_INVALID, "%s: err must lie on a 4-byte address", who);
+    if ((long long)c->F.P * 256 >= (1ll << 32)) return fail(c, DSAC_ERR_INVALID, "%s: maps beyond 2^24 cells are not supported", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    begin_call(c);
+    const size_t P = (size_t)c->F.P;
+    const double* d_poses;
+    float* d_err;
+    double* d_soft;
+    ARG_TRY(in_arg(c, poses, (size_t)N * 6, &d_poses));
+    ARG_TRY(out_arg(c, err_or_null, (size_t)N * P, &d_err));
+    ARG_TRY(out_arg(c, soft_or_null, (size_t)N, &d_soft));
+    HIP_TRY(c, c->rgbd_rec.reserve((size_t)N * dk::POSE_STRIDE * sizeof(float)));
+    if (d_soft) HIP_TRY(c, c->rgbd_soft_part.reserve((size_t)dk::rgbd_score_tiles(c->F.P) * (size_t)N * sizeof(float)));
+    HIP_TRY(c, dk::rgbd_score(c->stream, N, d_poses, c->rgbd_rec.as<float>(), c->F, c->cam_xyz.as<float>(), clampv, d_err, tau, beta, c->rgbd_soft_part.as<float>(), d_soft,
+                              frames > 1 ? N / frames : 0));
+    return end_call(c);
+}
+
+int dsac_refine_rgbd(dsac_ctx* c, int B, const double* init_poses, const int32_t* frame_of_or_null, double tau, double beta, double cut, double min_soft, int max_iters,
+                     double step_tol, double* out_poses, double* soft_out_or_null, int32_t* iters_out_or_null, int32_t* status_out_or_null) {
+    const char* who = "dsac_refine_rgbd";
+    ARG_TRY(refine_soft_check(c, who, B, init_poses, frame_of_or_null, tau, beta, cut, min_soft));
+    ARG_TRY(rgbd_check(c, who));
+    if (!out_poses) return fail(c, DSAC_ERR_INVALID, "%s: out_poses is NULL", who);
+    if (max_iters < 1 || max_iters > 64) return fail(c, DSAC_ERR_INVALID, "%s: max_iters must lie in 1 .. 64 (got %d)", who, max_iters);
+    if (!std::isfinite(step_tol) || step_tol < 0.0) return fail(c, DSAC_ERR_INVALID, "%s: step_tol must be finite and >= 0 (got %g)", who, step_tol);
+    const int frames = c->F.frames > 1 ? c->F.frames : 1;
+    HIP_TRY(c, hipSetDevice(c->device));
+    begin_call(c);
+    const double* d_init;
+    const int32_t* d_fof;
+    double *d_out, *d_soft;
+    int32_t *d_it, *d_status;
+    ARG_TRY(in_arg(c, init_poses, (size_t)B * 6, &d_init));
+    ARG_TRY(in_arg(c, frames > 1 ? frame_of_or_null : nullptr, (size_t)B, &d_fof));
+    ARG_TRY(out_arg(c, out_poses, (size_t)B * 6, &d_out));
+    ARG_TRY(out_arg(c, soft_out_or_null, (size_t)B, &d_soft));
+    ARG_TRY(out_arg(c, iters_out_or_null, (size_t)B, &d_it));
+    ARG_TRY(out_arg(c, status_out_or_null, (size_t)B, &d_status));
+    const dk::SoftGeom geom = dk::refine_soft_geom(c->F.P);
+    HIP_TRY(c, c->rgbd_scratch.reserve(dk::rgbd_refine_scratch_bytes(B, geom)));
+    HIP_TRY(c, dk::rgbd_refine(c->stream, B, d_init, d_fof, frames > 1 ? B / frames : 0, tau, beta, cut, min_soft, max_iters, step_tol, geom, c->rgbd_scratch.p, d_out, d_soft,
+                               d_it, d_status, c->F, c->cam_xyz.as<float>(), c->cam_meta.as<int32_t>()));
     return end_call(c);
 }
 

@@ -320,4 +320,23 @@ hipError_t dsac_select_frames(hipStream_t st, int frames, int N, const double* w
 // n patches of 3 x patch x patch floats (patch, channel, row, column) around sampling_xy[i] = (x, y) of an H x W x 3 BGR image
 hipError_t gather_patches(hipStream_t st, const uint8_t* bgr, int H, int W, const int32_t* sampling_xy, int n, int patch, float* out, int32_t* skipped);
 
+// ---- k_rgbd.hip ------------------------------------------------------------------------------------
+// RGB-D localisation (dsac_set_camera_points / dsac_sample_rgbd / dsac_score_rgbd / dsac_refine_rgbd, include/dsac_hip.h).  The measured camera-frame points
+// travel as arguments of their own: cam = the context's canonical copy (frames x P x 3, NaN in all three components of a cell that is not VALID), meta = per
+// frame the number of VALID cells and the first VALID cell (2 int32; 0x7fffffff: none).  No kernel of this group reads the camera intrinsics.
+// two launches: meta's reset, then the copy that canonicalises, counts and finds the first VALID cell.  src: frames x P x 3 (device)
+hipError_t rgbd_set_points(hipStream_t st, const float* src, const FrameDev& F, float* cam_copy, int32_t* meta);
+// sets N x 3.  sets_in: evaluated once each (one frame); else drawn from K1's counter stream, Nf > 0: hypothesis h belongs to frame h / Nf
+hipError_t rgbd_sample(hipStream_t st, int N, uint64_t seed, const int32_t* sets_in, const FrameDev& F, const float* cam, const int32_t* meta, double thr,
+                       int max_tries, double* poses, int32_t* sets_out, uint8_t* ok, int Nf = 0);
+// rec: N x POSE_STRIDE floats (written here); err (N x P) and / or soft (N doubles; soft_part then holds rgbd_score_tiles(P) x N floats), either may be nullptr
+int rgbd_score_tiles(int P);
+hipError_t rgbd_score(hipStream_t st, int N, const double* poses, float* rec, const FrameDev& F, const float* cam, float clampv, float* err, float tau, float beta,
+                      float* soft_part, double* soft, int Nf = 0);
+// the split loop of refine_soft with the RGB-D pass and step (chunks: refine_soft_geom)
+size_t rgbd_refine_scratch_bytes(int B, const SoftGeom& g);
+hipError_t rgbd_refine(hipStream_t st, int B, const double* init_poses, const int32_t* frame_of, int per_frame, double tau, double beta, double cut, double min_soft,
+                       int max_iters, double step_tol, const SoftGeom& geom, void* scratch, double* out_poses, double* soft_out, int32_t* iters_out,
+                       int32_t* status_out, const FrameDev& F, const float* cam, const int32_t* meta);
+
 }  // namespace dk

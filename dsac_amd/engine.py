@@ -175,6 +175,7 @@ class Engine:
         check(self._ctx, lib.dsac_set_frame(self._ctx, ptr(xyz), ptr(uv), int(H), int(W), fx, fy, cx, cy, flags))
         self.H, self.W, self.P, self.frames = int(H), int(W), int(H) * int(W), 1
         self._keep = (xyz, uv) if borrow else None
+        self._frame_uv, self._frame_cam = uv, (fx, fy, cx, cy)  # what set_depth back-projects through
 
     def set_frames(self, xyz, uv=None, H=None, W=None, cam=(525.0, 525.0, 320.0, 240.0), uv_per_frame=False, borrow=False):
         """A batch of frames of the same geometry: xyz F x H*W x 3 float32 (contiguous), uv shared (H*W x 2), per frame (F x H*W x 2)
@@ -192,6 +193,7 @@ class Engine:
             check(self._ctx, lib.dsac_set_frames(self._ctx, F, ptr(xyz), ptr(uv), 1 if uv_per_frame else 0, int(H), int(W), fx, fy, cx, cy, flags))
         self.H, self.W, self.P, self.frames = int(H), int(W), int(H) * int(W), F
         self._keep = (xyz, uv) if borrow else None
+        self._frame_uv, self._frame_cam = uv, (shared if table is None else table)
 
     # ---- guided sampling (dsac_set_sampling_weights) ------------------------------------------------------------------------------------
     def set_sampling_weights(self, w):
@@ -803,6 +805,154 @@ class Engine:
         check(self._ctx, lib.dsac_refine_soft_backward(self._ctx, B, ptr(ref), ptr(frame_of), float(tau), float(beta), self._soft_cut(tau, beta, cut), float(min_soft),
                                                        ptr(dL), ptr(coef), 1 if fixed_weights else 0, ptr(grad), ptr(ok)))
         return grad, ok
+
+    # ---- RGB-D: measured camera-frame points next to the scene coordinates (dsac_set_camera_points ... dsac_refine_rgbd) -------------------------
+    def set_camera_points(self, cam_xyz):
+        """The measured camera-frame points of the frame(s) currently set: F x H*W x 3 mm (any shape with that many values), numpy or torch, converted to
+        float32; None clears them.  A cell is VALID when its point is finite with z > 0 and its scene coordinate is finite; set_frame / set_frames clear the
+        points.  A torch device tensor only enqueues the copy."""
+        if cam_xyz is None:
+            check(self._ctx, lib.dsac_set_camera_points(self._ctx, None))
+            return
+        if hasattr(cam_xyz, "data_ptr"):  # torch
+            import torch
+            cam_xyz = cam_xyz.detach().to(torch.float32).contiguous()
+        else:
+            cam_xyz = np.ascontiguousarray(np.asarray(cam_xyz), dtype=np.float32)
+        n = int(cam_xyz.numel()) if hasattr(cam_xyz, "numel") else int(cam_xyz.size)
+        cells = getattr(self, "frames", 1) * self.P
+        if n != cells * 3:
+            raise ValueError("dsac_amd: camera points hold %d values, the frames currently set have %d cells x 3" % (n, cells))
+        check(self._ctx, lib.dsac_set_camera_points(self._ctx, ptr(cam_xyz)))
+        self._keep_cam = cam_xyz  # a device tensor is read in stream order, after this call has returned
+
+    def camera_points(self):
+        """The context's canonical copy (F x H*W x 3 float32, NaN in every cell that is not VALID) and the VALID count of every frame (F int32)."""
+        F = getattr(self, "frames", 1)
+        cam, n = np.zeros((F, self.P, 3), np.float32), np.zeros(F, np.int32)
+        check(self._ctx, lib.dsac_get_camera_points(self._ctx, ptr(cam), ptr(n)))
+        return cam, n
+
+    def set_depth(self, depth_mm, cam=None):
+        """Back-project a depth image (F x H*W mm, numpy or torch) through the cells' pixel positions -- the frame's own uv or the implicit grid -- and set the
+        result as camera points: C = ((u - cx) / fx d, (v - cy) / fy d, d); d <= 0 or non-finite gives NaN.  cam: (fx, fy, cx, cy) or F x 4, default the
+        camera(s) of the frame(s).  The arithmetic runs on the caller's side (numpy, or torch on the tensor's device)."""
+        F, P = getattr(self, "frames", 1), self.P
+        cam = self._frame_cam if cam is None else cam
+        uv = self._frame_uv
+        if hasattr(depth_mm, "data_ptr"):
+            import torch
+            d = depth_mm.detach().to(torch.float32).reshape(F, P)
+            k = torch.as_tensor(np.asarray(cam, dtype=np.float32).reshape(-1, 4), device=d.device)
+            if uv is None:
+                idx = torch.arange(P, device=d.device)
+                u, v = (idx % self.W).to(torch.float32)[None], (idx // self.W).to(torch.float32)[None]
+            else:
+                uvt = (uv if hasattr(uv, "data_ptr") else torch.as_tensor(np.asarray(uv, dtype=np.float32))).to(d.device).reshape(-1, P, 2)
+                u, v = uvt[..., 0], uvt[..., 1]
+            d = torch.where(torch.isfinite(d) & (d > 0), d, torch.full_like(d, float("nan")))
+            pts = torch.stack(((u - k[:, 2:3]) / k[:, 0:1] * d, (v - k[:, 3:4]) / k[:, 1:2] * d, d), dim=-1).contiguous()
+        else:
+            d = np.asarray(depth_mm, dtype=np.float32).reshape(F, P)
+            k = np.asarray(cam, dtype=np.float32).reshape(-1, 4)
+            if uv is None:
+                idx = np.arange(P)
+                u, v = (idx % self.W).astype(np.float32)[None], (idx // self.W).astype(np.float32)[None]
+            else:
+                uvn = np.asarray(uv.detach().cpu().numpy() if hasattr(uv, "detach") else uv, dtype=np.float32).reshape(-1, P, 2)
+                u, v = uvn[..., 0], uvn[..., 1]
+            with np.errstate(invalid="ignore"):
+                d = np.where(np.isfinite(d) & (d > 0), d, np.float32(np.nan)).astype(np.float32)
+                pts = np.stack(((u - k[:, 2:3]) / k[:, 0:1] * d, (v - k[:, 3:4]) / k[:, 1:2] * d, d), axis=-1).astype(np.float32)
+        self.set_camera_points(pts)
+        return pts
+
+    def sampleRGBD(self, N, seed=1305, thr=100.0, max_tries=1 << 20, sets=None, out=None):
+        """dsac_sample_rgbd: three-cell minimal sets from K1's counter stream (or `sets`, N x 3, evaluated once each), Horn's three-point alignment, the 3D check
+        |R X + t - C| < thr mm on the three cells.  Returns (poses N x 6, sets N x 3, ok N)."""
+        if out is None:
+            out = (np.zeros((N, 6)), np.zeros((N, 3), np.int32), np.zeros(N, np.uint8))
+        poses, sets_out, ok = out
+        sets = _np(sets, np.int32) if sets is not None else None
+        check(self._ctx, lib.dsac_sample_rgbd(self._ctx, int(N), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(sets), float(thr), int(max_tries), ptr(poses), ptr(sets_out),
+                                              ptr(ok)))
+        return poses, sets_out, ok
+
+    def scoreRGBD(self, poses, err=None, soft=None, tau=100.0, beta=0.05, clamp=1000.0, N=None):
+        """dsac_score_rgbd: err[h][p] = min(|R_h X_p + t_h - C_p|, clamp) mm (N x H*W float32) and / or soft[h] = sum over the VALID cells of
+        sigmoid(beta (tau - err)) (N float64).  Returns (err, soft)."""
+        poses = _np(poses, np.float64)
+        if N is None:
+            N = int(poses.shape[0])
+        check(self._ctx, lib.dsac_score_rgbd(self._ctx, int(N), ptr(poses), float(clamp), ptr(err), float(tau), float(beta), ptr(soft)))
+        return err, soft
+
+    def refineRGBD(self, init_poses, frame_of=None, tau=100.0, beta=0.05, cut=None, min_soft=50.0, max_iters=20, step_tol=1e-6):
+        """dsac_refine_rgbd: Horn's alignment re-weighted by sigmoid(beta (tau - |R X + t - C|)) over every VALID cell of the map, from B start poses (cv, B x 6).
+        cut: the distance at and beyond which a cell has weight zero (default through _soft_cut: tau + 16 / beta, at most 100).  Returns (poses B x 6, soft B,
+        iters B, status B); status indexes capi.SOFT_STATUS.  A refined pose never scores below its start pose."""
+        init = np.ascontiguousarray(np.asarray(init_poses, dtype=np.float64).reshape(-1, 6))
+        B = int(init.shape[0])
+        frame_of = np.ascontiguousarray(frame_of, dtype=np.int32).reshape(B) if frame_of is not None else None
+        out = np.zeros((B, 6))
+        soft, iters, status = np.zeros(B), np.zeros(B, np.int32), np.zeros(B, np.int32)
+        check(self._ctx, lib.dsac_refine_rgbd(self._ctx, B, ptr(init), ptr(frame_of), float(tau), float(beta), self._soft_cut(tau, beta, cut), float(min_soft),
+                                              int(max_iters), float(step_tol), ptr(out), ptr(soft), ptr(iters), ptr(status)))
+        return out, soft, iters, status
+
+    def processImageRGBD(self, N=256, seed=1305, gt_jp6=None, thr=100.0, tau=100.0, beta=0.05, alpha=0.1, select="argmax", max_tries=1 << 20, min_soft=50.0,
+                         max_iters=20, step_tol=1e-6):
+        """Test-time RGB-D localisation of the frame set with set_frame + set_camera_points: sample -> score -> softMax -> the most probable hypothesis
+        (select="argmax", DSAC*'s test-time rule) or the soft-argmax pose ("softargmax") -> refineRGBD -> maxLoss.  A dict in the shape of processImage's."""
+        if select not in ("argmax", "softargmax"):
+            raise ValueError("dsac_amd: select is \"argmax\" or \"softargmax\", got %r" % (select,))
+        poses, sets, ok = self.sampleRGBD(N, seed=seed, thr=thr, max_tries=max_tries)
+        soft = np.zeros(N)
+        self.scoreRGBD(poses, soft=soft, tau=tau, beta=beta)
+        w, ent, avg = self.softMax(soft, alpha, poses)
+        hyp_idx = self.draw(w)
+        start = poses[hyp_idx] if select == "argmax" else avg
+        ref, rsoft, iters, status = self.refineRGBD(start, tau=tau, beta=beta, min_soft=min_soft, max_iters=max_iters, step_tol=step_tol)
+        out = dict(hyps=poses, sampledPoints=sets, ok=ok, scores=soft, score_scale=alpha, sfScores=w, sfEntropy=float(ent[0]), avgHyp=avg, hypIdx=hyp_idx,
+                   diffMaps=None, soft=soft, refAvgHyp=ref[0], refSteps=int(iters[0]), refStatus=int(status[0]), refSoft=float(rsoft[0]), inlierMap=None, pixelIdxs=None)
+        if gt_jp6 is not None:
+            out.update(self.maxLoss(out["refAvgHyp"], gt_jp6))
+        return out
+
+    def processImagesRGBD(self, hyps_per_frame, gt_jp6=None, seed=1305, thr=100.0, tau=100.0, beta=0.05, alpha=0.1, select="argmax", max_tries=1 << 20,
+                          min_soft=50.0, max_iters=20, step_tol=1e-6):
+        """processImageRGBD for EVERY frame set with set_frames + set_camera_points, device-resident, one launch sequence per stage and no host round trip
+        between the stages.  gt_jp6: F x 6 (array or device tensor) or None.  Returns a dict of torch device tensors."""
+        import torch
+        if select not in ("argmax", "softargmax"):
+            raise ValueError("dsac_amd: select is \"argmax\" or \"softargmax\", got %r" % (select,))
+        F, N = getattr(self, "frames", 1), int(hyps_per_frame)
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.stream(torch.cuda.ExternalStream(int(self.stream), device=dev)):
+            f64 = dict(dtype=torch.float64, device=dev)
+            i32 = dict(dtype=torch.int32, device=dev)
+            hyps, sets, ok = torch.zeros(F * N, 6, **f64), torch.zeros(F * N, 3, **i32), torch.zeros(F * N, dtype=torch.uint8, device=dev)
+            soft, w, ent, avg = torch.zeros(F * N, **f64), torch.zeros(F * N, **f64), torch.zeros(F, **f64), torch.zeros(F, 6, **f64)
+            ref, rsoft, iters, status = torch.zeros(F, 6, **f64), torch.zeros(F, **f64), torch.zeros(F, **i32), torch.zeros(F, **i32)
+            ctx = self._ctx
+            check(ctx, lib.dsac_sample_rgbd(ctx, F * N, int(seed) & 0xFFFFFFFFFFFFFFFF, None, float(thr), int(max_tries), ptr(hyps), ptr(sets), ptr(ok)))
+            check(ctx, lib.dsac_score_rgbd(ctx, F * N, ptr(hyps), 1000.0, None, float(tau), float(beta), ptr(soft)))
+            check(ctx, lib.dsac_softmax_frames(ctx, F, N, ptr(soft), float(alpha), ptr(w), ptr(ent), ptr(hyps), ptr(avg)))
+            idx = torch.argmax(w.view(F, N), dim=1)  # on the stream: the most probable hypothesis of every frame
+            start = (hyps.view(F, N, 6)[torch.arange(F, device=dev), idx] if select == "argmax" else avg).contiguous()
+            check(ctx, lib.dsac_refine_rgbd(ctx, F, ptr(start), None, float(tau), float(beta), self._soft_cut(tau, beta, None), float(min_soft), int(max_iters),
+                                            float(step_tol), ptr(ref), ptr(rsoft), ptr(iters), ptr(status)))
+            out = dict(hyps=hyps, sampledPoints=sets, ok=ok, scores=soft, score_scale=alpha, sfScores=w, sfEntropy=ent, avgHyp=avg, hypIdx=idx.to(torch.int32),
+                       refAvgHyp=ref, refSteps=iters, refStatus=status, refSoft=rsoft)
+            if gt_jp6 is not None:
+                gt_d = gt_jp6 if hasattr(gt_jp6, "data_ptr") else torch.as_tensor(np.ascontiguousarray(np.asarray(gt_jp6, dtype=np.float64).reshape(F, 6)), device=dev)
+                out4 = torch.zeros(F, 4, **f64)
+                check(ctx, lib.dsac_loss_frames(ctx, F, ptr(ref), ptr(gt_d), ptr(out4), None))
+                out["out4"] = out4
+                self._keep_rgbd = (gt_d, start)
+            else:
+                self._keep_rgbd = (start,)
+        return out
 
     def maxLossBatch(self, est_cv6, gt_jp6, want_grad=False):
         """maxLoss [+ dLossMax] of B estimates against one ground truth (losses of expectedMaxLoss, core/cnn.h:137-150)."""

@@ -83,6 +83,30 @@ def chess_like_frame(H=480, W=640, seed=1305, cam=CAM_7SCENES, noise_mm=20.0, ou
                 cam=tuple(float(c) for c in cam), inlier_mask=~out)
 
 
+def chess_like_frame_rgbd(H=480, W=640, seed=1305, depth_noise_mm=5.0, missing_frac=0.1, **kw):
+    """chess_like_frame(H, W, seed, **kw) plus the measured side of an RGB-D frame: cam_xyz (P,3) f32 mm, the camera-frame point every cell was generated
+    from with depth noise along its viewing ray, NaN in missing_frac of the cells; depth (P,) f32 mm, its z (0 where missing: Engine.set_depth back-projects it
+    through uv).  xyz, uv and gt_pose are chess_like_frame's own for the same arguments; the extra randomness comes from a generator of its own."""
+    fr = chess_like_frame(H, W, seed, **kw)
+    fx, fy, cx, cy = fr["cam"]
+    # the depths chess_like_frame drew: the same generator walked through the same draws
+    rng = np.random.default_rng(seed)
+    rng.normal(size=3)
+    rng.uniform(0, 30)
+    rng.uniform(-1, 1, size=3)
+    uv = pixel_grid(H, W, H, W) if kw.get("grid_uv", False) else pixel_grid(H, W, stratified_rng=rng if kw.get("stratified", True) else None)
+    P = H * W
+    depth = rng.uniform(800.0, 3500.0, size=P)
+    rng2 = np.random.default_rng([int(seed), 0x5247])
+    d = depth + rng2.normal(scale=depth_noise_mm, size=P) if depth_noise_mm > 0 else depth.copy()
+    missing = rng2.uniform(size=P) < missing_frac
+    cam_xyz = np.stack([(uv[:, 0] - cx) / fx * d, (uv[:, 1] - cy) / fy * d, d], -1)
+    cam_xyz[missing] = np.nan
+    d = np.where(missing, 0.0, d)
+    fr.update(cam_xyz=cam_xyz.astype(np.float32), depth=d.astype(np.float32), missing_mask=missing)
+    return fr
+
+
 def roofline_frame(H=480, W=640, seed=7):
     """Config 3 of BASELINE.json: random coordinates, no structure (kernel-only runs)."""
     rng = np.random.default_rng(seed)

@@ -652,6 +652,73 @@ DSAC_API int dsac_refine_soft(dsac_ctx* ctx, int B, const double* init_poses, co
 #define DSAC_SOFT_BWD_FIXED_WEIGHTS 1u
 DSAC_API int dsac_refine_soft_backward(dsac_ctx* ctx, int B, const double* ref_poses, const int32_t* frame_of_or_null, double tau, double beta, double cut, double min_soft,
                               const double* dL_jp6, const double* coef_or_null, unsigned flags, double* grad_xyz, int32_t* ok_out_or_null);
+/* ---- RGB-D localisation -------------------------------------------------------------------------------------------------------------------------
+ * When a frame comes with a depth image, every cell p has a MEASURED camera-frame point C_p next to its predicted scene coordinate X_p.  A hypothesis is then
+ * the rigid alignment of THREE correspondences (Kabsch / Horn; the reference carries this solver as dead code, core/Hypothesis.cpp:145-217), an error is the 3D
+ * distance |R X_p + t - C_p| in millimetres, and the refinement is Horn's alignment re-weighted over the whole map (the RGB-D mode of DSAC*).  Conventions as
+ * everywhere in this header: cv poses (Rodrigues | translation in mm), C = R X + t in OpenCV's camera frame (x right, y down, z forward), host or device
+ * pointers detected per argument, device pointers only enqueue.  The camera intrinsics play no part in any RGB-D call: they work the same after dsac_set_frame,
+ * dsac_set_frames and dsac_set_frames_cams.  dsac_softmax*, dsac_select*, dsac_loss* read poses and scores only and serve RGB-D unchanged.
+ * NOT part of the RGB-D calls: the backward of any RGB-D stage, guided sampling with camera points, the reference-stream sampler and the pipelined pair,
+ * 16-bit error images, the C++ host shim and the driver programs, sharding (shard.ShardRunner), e2e.py, bench.py.
+ *
+ * dsac_set_camera_points: cam_xyz is frames x H*W x 3 float32 millimetres, laid out like xyz, for the frame(s) currently set.  The context copies it and owns
+ * the copy.  A cell is VALID when all three components of C_p are finite, C_p.z > 0, and all three components of X_p are finite; the copy holds NaN in all
+ * three components of every cell that is not VALID (no later kernel needs a mask), and the number of VALID cells of every frame, n_f, is counted on the device by
+ * the same launch.  NULL clears the points; so do dsac_set_frame, dsac_set_frames and dsac_set_frames_cams, exactly as they clear sampling weights.
+ * dsac_get_option("camera_points") reads 1 while points are set.  DSAC_ERR_NO_FRAME without a frame.
+ * dsac_get_camera_points reads the canonical copy (frames x H*W x 3) and / or n_f (frames int32) back; either may be NULL.  DSAC_ERR_INVALID without points. */
+DSAC_API int dsac_set_camera_points(dsac_ctx* ctx, const float* cam_xyz_or_null);
+DSAC_API int dsac_get_camera_points(dsac_ctx* ctx, float* cam_xyz_out_or_null, int32_t* valid_out_or_null);
+/* Sampling: sets are N x 3 int32 cell indices; the rule is the counter stream of dsac_sample ("Sampling RNG" above: key(h), v(h,a,k), cell(h,a,k)) with three
+ * cells instead of four.  On a frame batch frame f uses seed + f * seed_stride and N = frames x (hypotheses per frame).
+ *   attempt a takes the candidates k = 0, 1, 2, ...: a candidate that is not VALID or is already in the set is skipped; the attempt has its set at three cells;
+ *     more than 32 candidates: the attempt fails
+ *   pose    (R, t) = Horn's least-squares alignment of the three pairs in closed form (C_k ~= R X_k + t, floats widened to double), rvec = Rodrigues(R)
+ *   accepted iff all six pose entries are finite and |R X_k + t - C_k| < thr for each of the three cells, in double, thr in millimetres widened (NOT truncated
+ *     to an integer as dsac_sample's pixel threshold is; DSAC* uses 100); a NaN compares false.  A degenerate (collinear) triple that yields a non-finite pose
+ *     is thereby rejected; there is no separate area test
+ *   the first accepted attempt a < max_tries wins; otherwise ok = 0, a zero pose, and sets_out = the set of attempt max_tries - 1 if that attempt drew three
+ *     cells, else zeros (the rule of guided sampling).  A frame with n_f < 3 returns ok = 0 (zero poses, zero sets) for all its hypotheses at once, without
+ *     walking max_tries
+ *   given sets (sets_or_null != NULL, one frame only) are evaluated once each; a repeated, out-of-range or non-VALID cell gives ok = 0, a zero pose and
+ *     sets_out = the given cells.  The drawn and the given path give the same pose bit for bit for the same set.
+ * DSAC_ERR_INVALID with nothing enqueued: no camera points, sampling weights active (dsac_set_sampling_weights), given sets or N % frames != 0 on a frame
+ * batch, NULL outputs, max_tries <= 0 when drawing.  "pi_refstream" has no meaning here and is ignored.  DSAC_ERR_NO_FRAME without a frame. */
+DSAC_API int dsac_sample_rgbd(dsac_ctx* ctx, int N, uint64_t seed, const int32_t* sets_or_null, float thr, int max_tries, double* poses, int32_t* sets_out,
+                              uint8_t* ok);
+/* Scoring: err[h][p] = min(|R_h X_p + t_h - C_p|, clamp) in mm, N x H*W float32, hypothesis-major (the layout of dsac_reproject); a cell that is not VALID
+ * stores clamp.  soft[h] = sum_p sigmoid(beta (tau - err[h][p])) over the VALID cells; a cell that is not VALID contributes exactly 0.  Either output may be
+ * NULL.  On a frame batch N = frames x (hypotheses per frame), frame-major.  Any N and any H x W: the map need not be a multiple of anything and err may be any
+ * 4-byte-aligned address (a slice of a larger buffer included); one kernel, one arithmetic.  fp32: the pose as a float record (R | t from the fp64 Rodrigues),
+ * R X + t - C as one fused-multiply-add chain per component, one square root; per pair |err - exact| <= 2^-24 [12 (|X|_1 + |t|_1 + |C|_1) + 8 err].  Per-tile
+ * partial sums of soft are added in a fixed order: two calls give the same bits.
+ * DSAC_ERR_INVALID with nothing enqueued: no camera points, NULL poses, N < 0, N % frames != 0 on a frame batch, err off a 4-byte address, a map beyond 2^24
+ * cells.  DSAC_ERR_NO_FRAME without a frame. */
+DSAC_API int dsac_score_rgbd(dsac_ctx* ctx, int N, const double* poses, float clamp, float* err_or_null, float tau, float beta, double* soft_or_null);
+/* Refinement: Horn's alignment re-weighted by the score's own weights over all cells -- the RGB-D twin of dsac_refine_soft, with the same loop, the same
+ * statuses (enum dsac_soft_status) and the same determinism contract (ordered partial sums, no floating-point atomics: two calls give the same bits).  All in
+ * double, floats widened.
+ *   pass at h: for every VALID cell D = R(h) X_p + t - C_p, d = |D|, w_p = 1 / (1 + exp(-beta (tau - d))), w_p = 0 exactly where d is not finite or d >= cut;
+ *     S = sum w, sum w X, sum w C, sum w X C^T (16 sums; taken about the frame's first VALID cell, which changes nothing in exact arithmetic)
+ *   step from the sums at h: Xm = sum w X / S, Cm = sum w C / S, K = sum w (X - Xm)(C - Cm)^T / S, Horn's symmetric 4 x 4 matrix N(K) with eigenvalues
+ *     l1 >= l2 >= ... (cyclic Jacobi), q the unit eigenvector of l1, R' = R(q), t' = Cm - R' Xm, h' = (Rodrigues(R'), t').
+ *     DSAC_SOFT_SINGULAR when h' has a non-finite entry or l1 - l2 <= 1e-9 l1 (rank-deficient correspondences: the weighted cells on a line, a single cell)
+ *   loop per problem b, h0 = init_poses[b]:
+ *     1. a non-finite entry of h0: DSAC_SOFT_NONFINITE, out = h0 (soft_out 0, iters_out 0)
+ *     2. a pass at h0; unless S >= min_soft: DSAC_SOFT_FEW, out = h0
+ *     3. at most max_iters times: the step (singular: DSAC_SOFT_SINGULAR); |h' - h| <= step_tol (|h| + DBL_EPSILON) (Euclidean norms over the six entries):
+ *        DSAC_SOFT_CONVERGED, h' is not applied; otherwise a pass at h': unless S(h') >= S(h) (a NaN compares false) DSAC_SOFT_SCORE and h is kept, else
+ *        h <- h' (the pass at h' is reused)
+ *     4. after max_iters accepted steps: DSAC_SOFT_MAXIT
+ *     5. outputs as dsac_refine_soft: the output pose is always one at which a pass was taken, and never scores below its start pose
+ * Rotation angles near pi, where the Rodrigues vector jumps, are outside what this call promises for DSAC_SOFT_CONVERGED (the step test compares Rodrigues
+ * vectors).  One form: a pass kernel on cell chunks x problems and a one-wave step kernel per problem, max_iters + 1 launches of each, no host round trip.
+ * Frames, frame_of and B % frames == 0 on a batch without frame_of as in dsac_refine_soft.
+ * DSAC_ERR_INVALID with nothing enqueued: the conditions of dsac_refine_soft (cut in (0, 100] included, here in mm), and no camera points. */
+DSAC_API int dsac_refine_rgbd(dsac_ctx* ctx, int B, const double* init_poses, const int32_t* frame_of_or_null, double tau, double beta, double cut, double min_soft,
+                              int max_iters, double step_tol, double* out_poses, double* soft_out_or_null, int32_t* iters_out_or_null,
+                              int32_t* status_out_or_null);
 /* maxLoss / dLossMax for B estimates against one ground truth: the losses[] of expectedMaxLoss core/cnn.h:137-150 and
  * the per-hypothesis dLossMax of core/train_ransac.cpp:345-349.  out4 is B x 4, J6 B x 6 (layouts of dsac_loss). */
 DSAC_API int dsac_loss_batch(dsac_ctx* ctx, int B, const double* est_cv6, const double* gt_jp6, double* out4, double* J6_or_null);
