@@ -9,6 +9,8 @@
     distances / soft_sums     float64 distances and soft-inlier sums
     score_bound               the per-pair bound of dsac_score_rgbd
     refine                    the refinement loop with sums and the eigen-solve in np.longdouble
+    refine_f64                the same loop in plain float64 from the kernels' 16 sums, about the first VALID cell or about the origin
+    score_case / refine_case / refine_corpus / late_first_case / far_origin_case   the corpora the CPU and GPU tests share
 No GPU, no library call."""
 import numpy as np
 
@@ -233,7 +235,8 @@ def refine(h0, xyz, cam, tau, beta, cut, min_soft, max_iters, step_tol):
         if not np.isfinite(hn).all() or not (l1 - l2 > 1e-9 * l1):
             return h, float(S), it, 4, margin
         step, ref = np.linalg.norm(hn - h), step_tol * (np.linalg.norm(h) + 2.220446049250313e-16)
-        margin = min(margin, abs(step - ref) / (1e-9 * max(ref, 1e-300)))
+        with np.errstate(over="ignore"):  # step_tol = 0: the step is never within reach of its tolerance
+            margin = min(margin, abs(step - ref) / (1e-9 * max(ref, 1e-300)))
         if step <= ref:
             return h, float(S), it, 0, margin
         wn = _pass(hn, X, C, v, tau, beta, cut)
@@ -316,7 +319,12 @@ def sampled_poses(xyz, cam, n, seed):
 FAR_POSE = np.array([0.3, -0.2, 0.1, 30000.0, -30000.0, 26457.513110645905])  # |t| = 50 m
 SCORE_CASES = (  # name, H, W, frames, hypotheses per frame
     ("40x40", 40, 40, 1, 256), ("53x37", 37, 53, 1, 129), ("641x3", 3, 641, 1, 65), ("15", 3, 5, 1, 63), ("257", 1, 257, 1, 1),
-    ("3x64", 40, 40, 3, 64), ("2x65", 37, 53, 2, 65))
+    ("3x64", 40, 40, 3, 64), ("2x65", 37, 53, 2, 65),
+    # more than 32 cell tiles of 256: the scoring kernel's block decode has a second tile group (PT = tiles, PTG = groups of 32)
+    ("149x55", 55, 149, 2, 65),   # 8 195 cells: PT 33, PTG 2, the last tile holds 3 cells; two hypothesis tiles per frame, the second of one row; two frames
+    ("129x64", 64, 129, 1, 65),   # 8 256 cells: PT 33, the last tile is one full chunk of 64
+    ("129x129", 129, 129, 1, 3))  # 16 641 cells: PT 66, PTG 3, the last tile holds 1 cell
+SCORE_TILE = 256  # cells of one scoring tile; 32 tiles make a group
 
 
 def score_case(name):
@@ -345,3 +353,110 @@ def refine_case(H=40, W=40, frames=2, per_frame=12, seed=900):
         p[-3, 4] = np.nan
         init.append(p)
     return H, W, xyz, cam, gt, np.concatenate(init)
+
+
+# ---- refinement off the 256-cell chunk: corpora and parameter sets (CPU and GPU) -----------------------------------------------------------------------
+# the refinement's chunks are 256 cells up to 65 536 cells and whole 64-lane trips beyond:
+#   164 x 401 = 65 764 cells: 206 chunks of 320, the last of 164 cells (two full trips and one of 36 lanes)
+#   64 x 129  =  8 256 cells: 33 chunks of 256, the last of 64 cells
+#   1 x 63: one partial trip
+REFINE_CORPORA = ((164, 401), (64, 129), (1, 63))  # each 2 frames x 6 start poses, seed 901
+REFINE_PARAMS = ((50.0, 20, 1e-6, 100.0), (5.0, 2, 0.0, 60.0), (5.0, 1, 0.0, 100.0))  # min_soft, max_iters, step_tol, cut
+_REFINE_CACHE = {}
+
+
+def refine_corpus(H, W):
+    return refine_case(H, W, frames=2, per_frame=6, seed=901)
+
+
+def refine_reference(xyz, cam, init, tau, beta, cut, min_soft, max_iters, step_tol, loop=None, key=None):
+    """the loop (default: the long-double one) on every problem of a corpus, problem b on frame b // (B / F); cam as given.  key: cache the result under it"""
+    if key is not None and key in _REFINE_CACHE:
+        return _REFINE_CACHE[key]
+    loop = refine if loop is None else loop
+    canon = canonical(xyz, cam)[0]
+    per = len(init) // xyz.shape[0]
+    out = [loop(init[b], xyz[b // per], canon[b // per], tau, beta, cut, min_soft, max_iters, step_tol) for b in range(len(init))]
+    if key is not None:
+        _REFINE_CACHE[key] = out
+    return out
+
+
+def refine_f64(h0, xyz, cam, tau, beta, cut, min_soft, max_iters, step_tol, centred=True):
+    """the loop of `refine` in plain float64 from the 16 sums the kernels take -- S, sum w x, sum w c, sum w x c^T about the first VALID cell (x = X - X0,
+    c = C - C0; centred=False: about the origin) -- with K = sum w x c^T / S - xm cm^T and t = (C0 + cm) - R (X0 + xm).  Returns (pose, S, iters, status)."""
+    h = np.asarray(h0, np.float64).copy()
+    if not np.isfinite(h).all():
+        return h, 0.0, 0, 5
+    v = valid_cells(xyz, cam)
+    X = np.where(v[:, None], np.asarray(xyz, np.float64), 0.0)
+    C = np.where(v[:, None], np.asarray(cam, np.float64), 0.0)
+    first = int(np.argmax(v)) if v.any() else -1
+    X0 = X[first].copy() if centred and first >= 0 else np.zeros(3)
+    C0 = C[first].copy() if centred and first >= 0 else np.zeros(3)
+    x, c = X - X0, C - C0
+
+    def sums(pose):
+        D = X @ rodrigues(pose[:3]).T + pose[3:] - C
+        d = np.sqrt((D * D).sum(-1))
+        with np.errstate(invalid="ignore", over="ignore"):
+            w = 1 / (1 + np.exp(-beta * (tau - d)))
+            w = np.where(v & np.isfinite(d) & (d < cut), w, 0.0)
+        wx = w[:, None] * x
+        return w.sum(), wx.sum(0), (w[:, None] * c).sum(0), wx.T @ c
+
+    S, sx, sc, sxc = sums(h)
+    if not S >= min_soft:
+        return h, float(S), 0, 3
+    it = 0
+    while True:
+        with np.errstate(invalid="ignore", divide="ignore"):
+            xm, cm = sx / S, sc / S
+            K = sxc / S - np.outer(xm, cm)
+        if not np.isfinite(K).all():
+            return h, float(S), it, 4
+        R, l1, l2 = _horn(K)
+        hn = np.concatenate([rodrigues_inv(R), (C0 + cm) - R @ (X0 + xm)])
+        if not np.isfinite(hn).all() or not (l1 - l2 > 1e-9 * l1):
+            return h, float(S), it, 4
+        if np.linalg.norm(hn - h) <= step_tol * (np.linalg.norm(h) + 2.220446049250313e-16):
+            return h, float(S), it, 0
+        Sn, sxn, scn, sxcn = sums(hn)
+        if not Sn >= S:
+            return h, float(S), it, 2
+        h, S, sx, sc, sxc = hn, Sn, sxn, scn, sxcn
+        it += 1
+        if it >= max_iters:
+            return h, float(S), it, 1
+
+
+FAR_SHIFT = np.array([2e5, -3e5, 1e5])  # mm
+
+
+def late_first_case():
+    """the 2 x 40 x 40 refinement corpus with the first 300 cells of frame 1 not VALID (camera point NaN): that frame's first VALID cell lies in the second
+    workgroup of the canonical copy's kernel; frame 0 is untouched"""
+    H, W, xyz, cam, gt, init = refine_case()
+    cam = cam.copy()
+    cam[1, :300] = np.nan
+    return H, W, xyz, cam, gt, init
+
+
+def far_origin_case(late=False):
+    """the 2 x 40 x 40 refinement corpus in a scene frame whose origin is FAR_SHIFT away: float32 coordinates X + shift, camera points regenerated as
+    R X' + t' (the ground truth in the shifted frame, t' = t - R shift) in float64 from those float32 coordinates and rounded to float32 -- cells that were not
+    VALID keep their values -- and every start pose moved to the shifted frame the same way, so it sees the distances it saw before.
+    late: frame 1 loses its first 300 cells as in late_first_case."""
+    H, W, xyz, cam, gt, init = late_first_case() if late else refine_case()
+    per = len(init) // xyz.shape[0]
+    xyz_f = (xyz.astype(np.float64) + FAR_SHIFT).astype(np.float32)
+    cam_f, gt_f, init_f = cam.copy(), gt.copy(), init.copy()
+    for f in range(xyz.shape[0]):
+        R = rodrigues(gt[f][:3])
+        gt_f[f][3:] = gt[f][3:] - R @ FAR_SHIFT
+        v = valid_cells(xyz_f[f], cam[f])
+        cam_f[f][v] = (xyz_f[f][v].astype(np.float64) @ R.T + gt_f[f][3:]).astype(np.float32)
+    for b in range(len(init)):
+        if np.isfinite(init[b]).all():
+            init_f[b][3:] = init[b][3:] - rodrigues(init[b][:3]) @ FAR_SHIFT
+    return H, W, xyz_f, cam_f, gt_f, init_f
