@@ -55,6 +55,7 @@ EXPORTS = [
     "dsac_refine_gn_backward",
     "dsac_refine_soft", "dsac_refine_soft_backward",
     "dsac_set_camera_points", "dsac_get_camera_points", "dsac_sample_rgbd", "dsac_score_rgbd", "dsac_refine_rgbd",
+    "dsac_set_sampling_weights_rgbd", "dsac_sampling_table_rgbd", "dsac_sampling_weights_backward_rgbd",
 ]
 DSAC_SOFT_BWD_FIXED_WEIGHTS = 1
 SOFT_STATUS = ("CONVERGED", "MAXIT", "SCORE", "FEW", "SINGULAR", "NONFINITE")  # enum dsac_soft_status
@@ -147,6 +148,9 @@ def _load():
     lib.dsac_set_camera_points.argtypes = [vp, vp]
     lib.dsac_get_camera_points.argtypes = [vp, vp, vp]
     lib.dsac_sample_rgbd.argtypes = [vp, i32, u64, vp, f32, i32, vp, vp, vp]
+    lib.dsac_set_sampling_weights_rgbd.argtypes = [vp, vp]
+    lib.dsac_sampling_table_rgbd.argtypes = [vp, vp]
+    lib.dsac_sampling_weights_backward_rgbd.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.dsac_score_rgbd.argtypes = [vp, i32, vp, f32, vp, f32, f32, vp]
     lib.dsac_refine_rgbd.argtypes = [vp, i32, vp, vp, f64, f64, f64, f64, i32, f64, vp, vp, vp, vp]
     lib.dsac_loss_batch_frames.argtypes =[vp, i32, i32, vp, vp, vp, vp]

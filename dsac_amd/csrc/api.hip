@@ -67,6 +67,12 @@ struct dsac_ctx {
     // the VALID count and the first VALID cell.  have_cam: points are set for the current frames; every set-frame call clears it, as it clears the weights
     DevBuf cam_xyz, cam_meta, rgbd_rec, rgbd_soft_part, rgbd_scratch;
     bool have_cam = false;
+    // guided RGB-D sampling (dsac_set_sampling_weights_rgbd): a second table of its own -- table, coarse level, per-frame records and the context's copy of the
+    // MASKED weights w' (rgbd_guide_wm: where the mask launch writes them, rgbd_guide_w: the build's copy, which the gradient reads).  The build's per-tile
+    // scratch is guide_scratch, shared with the 2D table (builds are ordered by the stream).  have_rgbd_guide: those weights are active; they belong to the
+    // camera points they were masked with, so every dsac_set_camera_points call and every set-frame call clears it.  No 2D call reads any of this
+    DevBuf rgbd_guide_cdf, rgbd_guide_coarse, rgbd_guide_meta, rgbd_guide_w, rgbd_guide_wm;
+    bool have_rgbd_guide = false;
 
     // scratch, one buffer per role so that calls can be chained without aliasing
     DevBuf rs_states, rs_scratch, rs_small, k6_scratch;  // the reference's random streams (dsac_refstream_init) and the scratch of a sampling window
@@ -631,6 +637,7 @@ void dsac_destroy(dsac_ctx* c) {
     c->frame_xyz.release(); c->frame_uv.release(); c->cams_d.release();
     c->guide_cdf.release(); c->guide_coarse.release(); c->guide_meta.release(); c->guide_w.release(); c->guide_scratch.release();
     c->cam_xyz.release(); c->cam_meta.release(); c->rgbd_rec.release(); c->rgbd_soft_part.release(); c->rgbd_scratch.release();
+    c->rgbd_guide_cdf.release(); c->rgbd_guide_coarse.release(); c->rgbd_guide_meta.release(); c->rgbd_guide_w.release(); c->rgbd_guide_wm.release();
     c->staged.release(); c->staged_lo.release(); c->staged_split.release(); c->rs_states.release(); c->rs_scratch.release(); c->rs_small.release(); c->k6_scratch.release(); c->soft_scratch.release(); c->soft_part.release(); c->bwd_staged.release(); c->dRdH.release();
     c->grad_part.release(); c->g12_part.release(); c->g6.release();
     for (auto& s : c->slots) s.release();
@@ -776,6 +783,7 @@ static int set_frames_common(dsac_ctx* c, int frames, const float* xyz, const fl
     c->k1.guide_cdf = nullptr;  // the sampling weights belong to the frames they were set for
     c->k1.guide_meta = nullptr;
     c->have_cam = false;        // ... and so do the camera points (dsac_set_camera_points)
+    c->have_rgbd_guide = false; // ... and the RGB-D sampling weights masked with them (dsac_set_sampling_weights_rgbd)
     c->F.xyz = new_xyz;
     c->F.uv = new_uv;
     c->F.H = H; c->F.W = W; c->F.P = (int)P1;
@@ -1512,6 +1520,7 @@ int dsac_get_option(dsac_ctx* c, const char* key, int* value) {
     else if (k == "pi_defer_tail") *value = c->pi_defer_tail;
     else if (k == "k1_cus") *value = c->k1_cus;
     else if (k == "sampling_weights") *value = (c->have_frame && guided(c)) ? 1 : 0;  // read-only: sampling weights are active (dsac_set_sampling_weights)
+    else if (k == "sampling_weights_rgbd") *value = (c->have_frame && c->have_cam && c->have_rgbd_guide) ? 1 : 0;  // read-only: RGB-D sampling weights are active (dsac_set_sampling_weights_rgbd)
     else if (k == "camera_points") *value = (c->have_frame && c->have_cam) ? 1 : 0;  // read-only: camera points are set (dsac_set_camera_points)
     else if (k == "frame_cams") *value = (c->have_frame && c->F.cams) ? 1 : 0;  // read-only: the current frames carry one camera each (dsac_set_frames_cams)
     else return fail(c, DSAC_ERR_INVALID, "dsac_get_option: unknown key '%s'", key);
@@ -2668,6 +2677,7 @@ static int rgbd_check(dsac_ctx* c, const char* who) {
 int dsac_set_camera_points(dsac_ctx* c, const float* cam_xyz_or_null) {
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_set_camera_points: ctx is NULL");
     if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "dsac_set_camera_points: no frame set (the points belong to the frames currently set)");
+    c->have_rgbd_guide = false;  // the RGB-D sampling weights were masked with the points this call replaces or clears
     if (!cam_xyz_or_null) {
         c->have_cam = false;
         return DSAC_OK;
@@ -2689,6 +2699,83 @@ int dsac_set_camera_points(dsac_ctx* c, const float* cam_xyz_or_null) {
     return DSAC_OK;
 }
 
+// ---- guided RGB-D sampling: dsac_sample_rgbd draws its three-cell sets from per-cell weights masked with the camera points ------------------------------
+int dsac_set_sampling_weights_rgbd(dsac_ctx* c, const float* weights_or_null) {
+    const char* who = "dsac_set_sampling_weights_rgbd";
+    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "%s: ctx is NULL", who);
+    if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "%s: no frame set (the weights belong to the frames currently set)", who);
+    if (!c->have_cam) return fail(c, DSAC_ERR_INVALID, "%s: no camera points are set for the current frame(s) (dsac_set_camera_points): the weights are masked with them", who);
+    if (!weights_or_null) {
+        c->have_rgbd_guide = false;
+        return DSAC_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    // as dsac_set_sampling_weights: the table is touched on the context's stream only, a host pointer goes through a staging slot (the tail is joined then)
+    begin_call(c, /*keep_tail=*/is_device_ptr(weights_or_null, c));
+    const int frames = c->F.frames > 1 ? c->F.frames : 1, P = c->F.P;
+    const size_t cells = (size_t)frames * (size_t)P;
+    const float* d_w;
+    ARG_TRY(in_arg(c, weights_or_null, cells, &d_w));
+    // buffers that have to grow are replaced (hipFree waits for the device); a failed allocation leaves the weights cleared, never half a table
+    c->have_rgbd_guide = false;
+    HIP_TRY(c, c->rgbd_guide_cdf.reserve(cells * sizeof(uint64_t)));
+    HIP_TRY(c, c->rgbd_guide_coarse.reserve((size_t)frames * (size_t)dk::guide_coarse_entries(P) * sizeof(uint64_t)));
+    HIP_TRY(c, c->rgbd_guide_w.reserve(cells * sizeof(float)));
+    HIP_TRY(c, c->rgbd_guide_wm.reserve(cells * sizeof(float)));
+    HIP_TRY(c, c->rgbd_guide_meta.reserve((size_t)frames * sizeof(dk::GuideMeta)));
+    HIP_TRY(c, c->guide_scratch.reserve(dk::guide_scratch_bytes(frames, P)));
+    // the first launch reads the caller's weights and the canonical copy and writes w'; the 2D build then runs on w', in stream order
+    HIP_TRY(c, dk::rgbd_mask_weights(c->stream, frames, P, d_w, c->cam_xyz.as<float>(), c->rgbd_guide_wm.as<float>()));
+    HIP_TRY(c, dk::guide_build(c->stream, frames, P, c->rgbd_guide_wm.as<float>(), c->rgbd_guide_w.as<float>(), c->rgbd_guide_cdf.as<uint64_t>(),
+                               c->rgbd_guide_coarse.as<uint64_t>(), c->rgbd_guide_meta.as<dk::GuideMeta>(), c->guide_scratch.p));
+    c->have_rgbd_guide = true;
+    return DSAC_OK;
+}
+
+// the RGB-D weights are active only together with the camera points they were masked with
+static int rgbd_guide_check(dsac_ctx* c, const char* who) {
+    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "%s: ctx is NULL", who);
+    if (!c->have_frame || !c->have_cam || !c->have_rgbd_guide)
+        return fail(c, DSAC_ERR_INVALID, "%s: no RGB-D sampling weights are active (dsac_set_sampling_weights_rgbd)", who);
+    return DSAC_OK;
+}
+
+int dsac_sampling_table_rgbd(dsac_ctx* c, uint64_t* cdf_out) {
+    const char* who = "dsac_sampling_table_rgbd";
+    ARG_TRY(rgbd_guide_check(c, who));
+    if (!cdf_out) return fail(c, DSAC_ERR_INVALID, "%s: cdf_out is NULL (frames x H*W uint64)", who);
+    HIP_TRY(c, hipSetDevice(c->device));
+    begin_call(c);
+    const size_t cells = (size_t)(c->F.frames > 1 ? c->F.frames : 1) * (size_t)c->F.P;
+    uint64_t* d_out;
+    ARG_TRY(out_arg(c, cdf_out, cells, &d_out));
+    HIP_TRY(c, hipMemcpyAsync(d_out, c->rgbd_guide_cdf.p, cells * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
+    return end_call(c);
+}
+
+int dsac_sampling_weights_backward_rgbd(dsac_ctx* c, int N, const int32_t* sets, const uint8_t* ok, const double* g, double* grad_w) {
+    const char* who = "dsac_sampling_weights_backward_rgbd";
+    ARG_TRY(rgbd_guide_check(c, who));
+    const int frames = c->F.frames > 1 ? c->F.frames : 1;
+    if (N <= 0 || N % frames != 0 || !sets || !ok || !g || !grad_w)
+        return fail(c, DSAC_ERR_INVALID, "%s: N > 0, a multiple of the %d frame(s), and sets / ok / g / grad_w must be non-NULL", who, frames);
+    HIP_TRY(c, hipSetDevice(c->device));
+    begin_call(c);
+    const size_t cells = (size_t)frames * (size_t)c->F.P;
+    const int32_t* d_sets;
+    const uint8_t* d_ok;
+    const double* d_g;
+    double* d_grad;
+    ARG_TRY(in_arg(c, sets, (size_t)N * 3, &d_sets));
+    ARG_TRY(in_arg(c, ok, (size_t)N, &d_ok));
+    ARG_TRY(in_arg(c, g, (size_t)N, &d_g));
+    ARG_TRY(out_arg(c, grad_w, cells, &d_grad, /*preload=*/true));  // accumulated into, like grad_xyz
+    // the context's copy holds the masked weights: a cell that is not VALID has weight 0 there and receives nothing
+    HIP_TRY(c, dk::guide_backward(c->stream, frames, c->F.P, N / frames, c->rgbd_guide_w.as<float>(), c->rgbd_guide_meta.as<dk::GuideMeta>(), d_sets, d_ok, d_g, d_grad,
+                                  /*set_cells=*/3));
+    return end_call(c);
+}
+
 int dsac_get_camera_points(dsac_ctx* c, float* cam_xyz_out_or_null, int32_t* valid_out_or_null) {
     ARG_TRY(rgbd_check(c, "dsac_get_camera_points"));
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2708,7 +2795,7 @@ int dsac_get_camera_points(dsac_ctx* c, float* cam_xyz_out_or_null, int32_t* val
 int dsac_sample_rgbd(dsac_ctx* c, int N, uint64_t seed, const int32_t* sets_or_null, float thr, int max_tries, double* poses, int32_t* sets_out, uint8_t* ok) {
     const char* who = "dsac_sample_rgbd";
     ARG_TRY(rgbd_check(c, who));
-    ARG_TRY(guide_refuse(c, who, "guided sampling with camera points is not built"));
+    ARG_TRY(guide_refuse(c, who, "the RGB-D calls draw from the weights of dsac_set_sampling_weights_rgbd, which are masked with the camera points, never from these"));
     const int frames = c->F.frames > 1 ? c->F.frames : 1;
     if (frames > 1 && (sets_or_null || N % frames != 0))
         return fail(c, DSAC_ERR_INVALID, "%s: with a frame batch N must be frames x (hypotheses per frame) and the sets are drawn here (given sets are evaluated frame by "
@@ -2726,8 +2813,10 @@ int dsac_sample_rgbd(dsac_ctx* c, int N, uint64_t seed, const int32_t* sets_or_n
     ARG_TRY(out_arg(c, poses, (size_t)N * 6, &d_poses));
     ARG_TRY(out_arg(c, sets_out, (size_t)N * 3, &d_sets_out));
     ARG_TRY(out_arg(c, ok, (size_t)N, &d_ok));
+    // drawn sets come from the masked table while RGB-D sampling weights are active; given sets never look at it
+    const dk::RgbdGuide guide{c->rgbd_guide_cdf.as<uint64_t>(), c->rgbd_guide_meta.as<dk::GuideMeta>(), c->rgbd_guide_coarse.as<uint64_t>()};
     HIP_TRY(c, dk::rgbd_sample(c->stream, N, seed, d_sets_in, c->F, c->cam_xyz.as<float>(), c->cam_meta.as<int32_t>(), (double)thr, max_tries, d_poses, d_sets_out, d_ok,
-                               frames > 1 ? N / frames : 0));
+                               frames > 1 ? N / frames : 0, c->have_rgbd_guide ? &guide : nullptr));
     return end_call(c);
 }
 

@@ -659,5 +659,41 @@ DM_INLINE int draw_cell(uint64_t key, uint32_t attempt, uint32_t k, uint32_t W, 
     return (int)(y * W + x);
 }
 DM_INLINE uint64_t hyp_key(uint64_t seed, uint32_t hyp) { return mix64(seed ^ mix64((uint64_t)hyp)); }
+// the guided siblings of draw_cell: the cells of M values t < T in a frame's table C (P inclusive uint64 sums, C[P - 1] = T), the smallest p with C[p] > t[j].
+// Two branch-free upper bounds whose trip counts depend on K and shift alone, so the M searches walk their dependent loads side by side: over the coarse level
+// L (the last entry of every block of 2^shift cells, K = ceil(P / 2^shift) of them; the callers keep it in LDS), then over the one block that holds the cell
+// (reads beyond P - 1 see C[P - 1] = T > t)
+template <int M>
+DM_INLINE void table_cells(const uint64_t* L, int K, const uint64_t* C, int P, int shift, const uint64_t t[M], int32_t cell[M]) {
+    uint32_t base[M];
+    uint64_t c[M];
+#pragma unroll
+    for (int j = 0; j < M; j++) base[j] = 0;
+    for (uint32_t len = (uint32_t)K; len > 1;) {
+        const uint32_t half = len >> 1;
+#pragma unroll
+        for (int j = 0; j < M; j++) c[j] = L[base[j] + half - 1];
+#pragma unroll
+        for (int j = 0; j < M; j++) base[j] += (c[j] <= t[j]) ? half : 0u;
+        len -= half;
+    }
+#pragma unroll
+    for (int j = 0; j < M; j++) c[j] = L[base[j]];
+#pragma unroll
+    for (int j = 0; j < M; j++) base[j] = (base[j] + ((c[j] <= t[j]) ? 1u : 0u)) << shift;  // L[K - 1] = T > t: the block index stays below K
+    const uint32_t last = (uint32_t)P - 1u;
+    for (uint32_t len = 1u << shift; len > 1;) {
+        const uint32_t half = len >> 1;
+#pragma unroll
+        for (int j = 0; j < M; j++) c[j] = C[min(base[j] + half - 1, last)];
+#pragma unroll
+        for (int j = 0; j < M; j++) base[j] += (c[j] <= t[j]) ? half : 0u;
+        len -= half;
+    }
+#pragma unroll
+    for (int j = 0; j < M; j++) c[j] = C[min(base[j], last)];
+#pragma unroll
+    for (int j = 0; j < M; j++) cell[j] = (int32_t)(base[j] + ((c[j] <= t[j]) ? 1u : 0u));
+}
 
 }  // namespace dm

@@ -263,13 +263,85 @@ DM_INLINE bool rgbd_draw3(uint64_t key, uint32_t attempt, uint32_t W, uint32_t H
     return n == 3;
 }
 
+// The draw is a policy of the kernel (template parameter DRAW), as it is of k_sample: where the three cells of an attempt come from is all that differs
+// between the uniform build and the guided one (dsac_set_sampling_weights_rgbd); the evaluation, the ballot and the failure rows are one text.
+//   bind(P, frame): once per wave, drawn sets only;  empty(cam_meta, frame): no attempt of this frame can draw three cells;  draw(): the set of an attempt.
+struct DrawUniform3 {
+    DM_INLINE void bind(int, int) {}
+    DM_INLINE bool empty(const int32_t* __restrict__ cam_meta, int frame) const { return cam_meta[2 * frame] < 3; }
+    DM_INLINE bool draw(uint64_t key, uint32_t attempt, uint32_t W, uint32_t H, const float* __restrict__ cam, int& c0, int& c1, int& c2) const {
+        return rgbd_draw3(key, attempt, W, H, cam, c0, c1, c2);
+    }
+};
+
+// Guided draw: candidate k is the cell of t = floor(v * T' / 2^64) in the frame's table of the MASKED weights (DrawGuided in k_sample.hip has the rule and
+// the measurements; dm::table_cells the search).  The table holds no mass on a cell that is not VALID, so no candidate needs a VALID load.  The first three
+// candidates are searched side by side -- their dependent loads overlap --; only when two of them coincide does the walk go on candidate by candidate, from
+// k = 0 with the three cells already found, so the set is the sequential walk's.  One wave per workgroup: it holds ONE frame's coarse level in LDS.
+struct DrawGuided3 {
+    const uint64_t* cdf;     // frames x P
+    const GuideMeta* meta;   // frames
+    const uint64_t* coarse;  // frames x K, K = ceil(P / 2^shift)
+    int shift;
+    const uint64_t* C;
+    const uint64_t* L;       // the frame's coarse level in LDS
+    uint64_t T;
+    int P, n, K;
+    DM_INLINE void bind(int P_, int frame) {
+        __shared__ uint64_t s_coarse[GUIDE_COARSE_MAX];
+        frame = __builtin_amdgcn_readfirstlane(frame);  // one hypothesis per wave: the table's rows are scalar loads
+        P = P_;
+        K = (P + (1 << shift) - 1) >> shift;
+        C = cdf + (size_t)frame * (size_t)P;
+        T = meta[frame].T;
+        n = meta[frame].n;
+        L = s_coarse;
+        if (n >= 3) {  // uniform over the workgroup
+            const uint64_t* cf = coarse + (size_t)frame * (size_t)K;
+            for (int i = threadIdx.x; i < K; i += blockDim.x) s_coarse[i] = cf[i];
+            __syncthreads();
+        }
+    }
+    DM_INLINE bool empty(const int32_t*, int) const { return n < 3; }
+    DM_INLINE uint64_t target(uint64_t key, uint32_t attempt, uint32_t k) const { return __umul64hi(dm::mix64(key + (((uint64_t)attempt << 16) | k)), T); }
+    DM_INLINE bool draw(uint64_t key, uint32_t attempt, uint32_t, uint32_t, const float*, int& c0, int& c1, int& c2) const {
+        uint64_t t[3];
+        int32_t c[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) t[j] = target(key, attempt, (uint32_t)j);
+        dm::table_cells<3>(L, K, C, P, shift, t, c);
+        c0 = c[0]; c1 = c[1]; c2 = c[2];
+        if (c0 != c1 && c0 != c2 && c1 != c2) return true;
+        int m = 0, s0 = 0, s1 = 0, s2 = 0;
+        for (uint32_t k = 0; k < 32 && m < 3; k++) {
+            int32_t cell = k == 0 ? c[0] : k == 1 ? c[1] : c[2];
+            if (k >= 3) {
+                const uint64_t tk = target(key, attempt, k);
+                dm::table_cells<1>(L, K, C, P, shift, &tk, &cell);
+            }
+            const bool take = !((m > 0 && cell == s0) || (m > 1 && cell == s1));
+            s0 = (take && m == 0) ? cell : s0;
+            s1 = (take && m == 1) ? cell : s1;
+            s2 = (take && m == 2) ? cell : s2;
+            m += take ? 1 : 0;
+        }
+        c0 = s0; c1 = s1; c2 = s2;
+        return m == 3;
+    }
+};
+
 // One kernel for both paths, ONE evaluation site: a lane evaluates one candidate set per round.
 //   drawn sets (sets_in == nullptr): workgroup = one wave = hypothesis blockIdx.x; lane l of round r evaluates attempt 64 r + l; the lowest accepted lane of
 //   the first round that has one wins (ballot).
 //   given sets: lane l of workgroup w evaluates the set of hypothesis 64 w + l, once.
+// DRAW / TAB: the draw policy and what it is built from -- nothing for the uniform build, whose argument list is the one it always had, and the table (cdf,
+// per-frame records, coarse level, its shift) for the guided one, which is launched on drawn sets only.
+template <class DRAW = DrawUniform3, class... TAB>
 __global__ __launch_bounds__(64) void k_sample_rgbd(int N, int Nf, uint64_t seed, int seed_stride, const int32_t* __restrict__ sets_in, const float* __restrict__ xyz,
                                                     long long xyz_stride, const float* __restrict__ cam, const int32_t* __restrict__ meta, int P, int W, int H,
-                                                    double thr, int max_tries, double* __restrict__ poses, int32_t* __restrict__ sets_out, uint8_t* __restrict__ ok) {
+                                                    double thr, int max_tries, double* __restrict__ poses, int32_t* __restrict__ sets_out, uint8_t* __restrict__ ok,
+                                                    TAB... tab) {
+    DRAW D{tab...};
     const int lane = threadIdx.x & 63;
     const bool given = sets_in != nullptr;
     const int h = given ? blockIdx.x * 64 + lane : blockIdx.x;
@@ -281,7 +353,8 @@ __global__ __launch_bounds__(64) void k_sample_rgbd(int N, int Nf, uint64_t seed
         xyz += (long long)frame * xyz_stride;
         cam += (size_t)frame * (size_t)P * 3;
         key = dm::hyp_key(seed + (uint64_t)frame * (uint64_t)seed_stride, (uint32_t)hl);
-        if (meta[2 * frame] < 3) {  // no attempt of this frame can draw three cells
+        D.bind(P, frame);
+        if (D.empty(meta, frame)) {  // no attempt of this frame can draw three cells
             if (lane == 0) {
 #pragma unroll
                 for (int i = 0; i < 6; i++) poses[(size_t)h * 6 + i] = 0.0;
@@ -304,7 +377,7 @@ __global__ __launch_bounds__(64) void k_sample_rgbd(int N, int Nf, uint64_t seed
             }
         } else {
             const int a = round * 64 + lane;
-            have = a < max_tries && rgbd_draw3(key, (uint32_t)a, (uint32_t)W, (uint32_t)H, cam, c0, c1, c2);
+            have = a < max_tries && D.draw(key, (uint32_t)a, (uint32_t)W, (uint32_t)H, cam, c0, c1, c2);
         }
         // the evaluation (lanes without a set evaluate cell 0 three times and are not accepted)
         const int e0 = have ? c0 : 0, e1 = have ? c1 : 0, e2 = have ? c2 : 0;
@@ -346,12 +419,21 @@ __global__ __launch_bounds__(64) void k_sample_rgbd(int N, int Nf, uint64_t seed
     // drawn sets, no attempt accepted: the set of the last attempt if it drew three cells, else zeros
     if (lane == 0) {
         int c0, c1, c2;
-        if (!rgbd_draw3(key, (uint32_t)(max_tries - 1), (uint32_t)W, (uint32_t)H, cam, c0, c1, c2)) c0 = c1 = c2 = 0;
+        if (!D.draw(key, (uint32_t)(max_tries - 1), (uint32_t)W, (uint32_t)H, cam, c0, c1, c2)) c0 = c1 = c2 = 0;
 #pragma unroll
         for (int i = 0; i < 6; i++) poses[(size_t)h * 6 + i] = 0.0;
         sets_out[(size_t)h * 3] = c0; sets_out[(size_t)h * 3 + 1] = c1; sets_out[(size_t)h * 3 + 2] = c2;
         ok[h] = 0;
     }
+}
+
+// the masked weights of guided RGB-D sampling (dsac_set_sampling_weights_rgbd): w' = w where the cell is VALID, 0 elsewhere; the table build of
+// dsac_set_sampling_weights (k_sample.hip, guide_build) then runs on w'.  A lane per cell over all frames
+__global__ __launch_bounds__(256) void k_rgbd_mask_weights(long long cells, const float* __restrict__ w, const float* __restrict__ cam, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= cells) return;
+    const float c = cam[(size_t)i * 3];
+    out[i] = (c == c) ? w[i] : 0.0f;  // the canonical copy: a cell that is not VALID holds NaN
 }
 
 // ---- refinement: Horn's alignment over the whole map, re-weighted by the score's sigmoid ---------------------------------------------------------
@@ -579,11 +661,26 @@ hipError_t rgbd_set_points(hipStream_t st, const float* src, const FrameDev& F, 
 }
 
 hipError_t rgbd_sample(hipStream_t st, int N, uint64_t seed, const int32_t* sets_in, const FrameDev& F, const float* cam, const int32_t* meta, double thr,
-                       int max_tries, double* poses, int32_t* sets_out, uint8_t* ok, int Nf) {
+                       int max_tries, double* poses, int32_t* sets_out, uint8_t* ok, int Nf, const RgbdGuide* guide) {
     if (N <= 0) return hipSuccess;
     const unsigned grid = sets_in ? (unsigned)((N + 63) / 64) : (unsigned)N;
-    hipLaunchKernelGGL(k_sample_rgbd, dim3(grid), dim3(64), 0, st, N, Nf, seed, F.seed_stride, sets_in, F.xyz, F.xyz_stride, cam, meta, F.P, F.W, F.H, thr, max_tries,
-                       poses, sets_out, ok);
+    if (guide && !sets_in) {  // given sets are evaluated by the uniform build: the weights do not touch them
+        if (!guide->cdf || !guide->meta || !guide->coarse) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((k_sample_rgbd<DrawGuided3, const uint64_t*, const GuideMeta*, const uint64_t*, int>), dim3(grid), dim3(64), 0, st, N, Nf, seed, F.seed_stride,
+                           sets_in, F.xyz, F.xyz_stride, cam, meta, F.P, F.W, F.H, thr, max_tries, poses, sets_out, ok, guide->cdf, guide->meta, guide->coarse,
+                           guide_coarse_shift(F.P));
+    } else {
+        hipLaunchKernelGGL((k_sample_rgbd<>), dim3(grid), dim3(64), 0, st, N, Nf, seed, F.seed_stride, sets_in, F.xyz, F.xyz_stride, cam, meta, F.P, F.W, F.H, thr,
+                           max_tries, poses, sets_out, ok);
+    }
+    return hipGetLastError();
+}
+
+hipError_t rgbd_mask_weights(hipStream_t st, int frames, int P, const float* w, const float* cam, float* out) {
+    const long long cells = (long long)frames * P;
+    if (cells <= 0) return hipSuccess;
+    if ((cells + 255) / 256 > 0x7fffffffll) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_rgbd_mask_weights, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, cells, w, cam, out);
     return hipGetLastError();
 }
 

@@ -99,6 +99,7 @@ struct DrawUniform {
 // gain only where the tables (39 MB for 16 frames) no longer sit in L2, and still 2 - 2.9 x the uniform K1 (14.3 / 41.4 / 46.2 us): every step is a gather
 // of 64 x 4 scattered 8-byte entries per wave, and the waves of a CU share one address unit.  What would shorten it further is fewer, wider steps; not built.
 // A workgroup holds ONE frame's coarse level: the guided builds are one hypothesis per wave and one wave per workgroup.
+// The search itself is dm::table_cells (dmath.h): the guided build of k_sample_rgbd (k_rgbd.hip, DrawGuided3) walks the same one with three candidates.
 struct DrawGuided {
     static constexpr bool ZERO_UNDRAWN = true;
     const uint64_t* cdf;     // frames x P
@@ -127,37 +128,7 @@ struct DrawGuided {
     DM_INLINE static uint64_t value(uint64_t key, uint32_t attempt, uint32_t k) { return dm::mix64(key + (((uint64_t)attempt << 16) | k)); }
     // the cells of M values t < T
     template <int M>
-    DM_INLINE void search(const uint64_t t[M], int32_t cell[M]) const {
-        uint32_t base[M];
-        uint64_t c[M];
-#pragma unroll
-        for (int j = 0; j < M; j++) base[j] = 0;
-        for (uint32_t len = (uint32_t)K; len > 1;) {
-            const uint32_t half = len >> 1;
-#pragma unroll
-            for (int j = 0; j < M; j++) c[j] = L[base[j] + half - 1];
-#pragma unroll
-            for (int j = 0; j < M; j++) base[j] += (c[j] <= t[j]) ? half : 0u;
-            len -= half;
-        }
-#pragma unroll
-        for (int j = 0; j < M; j++) c[j] = L[base[j]];
-#pragma unroll
-        for (int j = 0; j < M; j++) base[j] = (base[j] + ((c[j] <= t[j]) ? 1u : 0u)) << shift;  // L[K - 1] = T > t: the block index stays below K
-        const uint32_t last = (uint32_t)P - 1u;
-        for (uint32_t len = 1u << shift; len > 1;) {
-            const uint32_t half = len >> 1;
-#pragma unroll
-            for (int j = 0; j < M; j++) c[j] = C[min(base[j] + half - 1, last)];
-#pragma unroll
-            for (int j = 0; j < M; j++) base[j] += (c[j] <= t[j]) ? half : 0u;
-            len -= half;
-        }
-#pragma unroll
-        for (int j = 0; j < M; j++) c[j] = C[min(base[j], last)];
-#pragma unroll
-        for (int j = 0; j < M; j++) cell[j] = (int32_t)(base[j] + ((c[j] <= t[j]) ? 1u : 0u));
-    }
+    DM_INLINE void search(const uint64_t t[M], int32_t cell[M]) const { dm::table_cells<M>(L, K, C, P, shift, t, cell); }
     DM_INLINE void first4(const FrameDev&, uint64_t key, uint32_t attempt, int32_t set4[4]) const {
         uint64_t t[4];
 #pragma unroll
@@ -771,9 +742,9 @@ hipError_t guide_build(hipStream_t st, int frames, int P, const float* w, float*
 }
 
 // The score-function gradient of guided training, one launch.  Workgroup (b, f) forms G_f = sum of g[h] over the accepted hypotheses of frame f -- in
-// double-double, so that every workgroup holds the same, correctly rounded value whatever signs g carries --, adds the uniform term -4 G_f / S_f to the valid
+// double-double, so that every workgroup holds the same, correctly rounded value whatever signs g carries --, adds the uniform term -NC G_f / S_f to the valid
 // cells of its tile and scatters g[h] / w_c to the set cells of its share of the hypotheses.  Both go through fp64 atomics: a cell may receive them from
-// several workgroups at once.
+// several workgroups at once.  NC: cells per minimal set -- 4 (dsac_sampling_weights_backward) or 3 (the RGB-D sets, dsac_sampling_weights_backward_rgbd).
 DM_INLINE void guide_two_sum(double& hi, double& lo, double b_hi, double b_lo) {
     const double s = hi + b_hi;
     const double bb = s - hi;
@@ -781,6 +752,7 @@ DM_INLINE void guide_two_sum(double& hi, double& lo, double b_hi, double b_lo) {
     hi = s;
     lo += err + b_lo;
 }
+template <int NC>
 __global__ __launch_bounds__(GUIDE_THREADS) void k_guide_backward(int P, int Nf, const float* __restrict__ w_copy, const GuideMeta* __restrict__ meta,
                                                                   const int32_t* __restrict__ sets, const uint8_t* __restrict__ ok, const double* __restrict__ g,
                                                                   double* __restrict__ grad_w) {
@@ -802,7 +774,7 @@ __global__ __launch_bounds__(GUIDE_THREADS) void k_guide_backward(int P, int Nf,
     }
     const double G = s_hi[0] + s_lo[0];
     const double S = meta[f].S;
-    const double uni = -4.0 * G / S;
+    const double uni = -(double)NC * G / S;
     const long long p0 = (long long)blockIdx.x * GUIDE_TILE + 4 * tid;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -813,8 +785,8 @@ __global__ __launch_bounds__(GUIDE_THREADS) void k_guide_backward(int P, int Nf,
         if (!ok[h0 + j]) continue;
         const double gh = g[h0 + j];
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int p = sets[(h0 + j) * 4 + k];
+        for (int k = 0; k < NC; k++) {
+            const int p = sets[(h0 + j) * NC + k];
             if (p < 0 || p >= P) continue;
             const float wp = w_copy[row + p];
             if (guide_valid(wp)) atomicAdd(&grad_w[row + p], gh / (double)wp);
@@ -823,9 +795,12 @@ __global__ __launch_bounds__(GUIDE_THREADS) void k_guide_backward(int P, int Nf,
 }
 
 hipError_t guide_backward(hipStream_t st, int frames, int P, int Nf, const float* w_copy, const GuideMeta* meta, const int32_t* sets, const uint8_t* ok,
-                          const double* g, double* grad_w) {
+                          const double* g, double* grad_w, int set_cells) {
     if (frames <= 0 || P <= 0 || Nf <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_guide_backward, dim3((unsigned)guide_tiles(P), (unsigned)frames), dim3(GUIDE_THREADS), 0, st, P, Nf, w_copy, meta, sets, ok, g, grad_w);
+    if (set_cells != 3 && set_cells != 4) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)guide_tiles(P), (unsigned)frames);
+    if (set_cells == 3) hipLaunchKernelGGL(k_guide_backward<3>, grid, dim3(GUIDE_THREADS), 0, st, P, Nf, w_copy, meta, sets, ok, g, grad_w);
+    else hipLaunchKernelGGL(k_guide_backward<4>, grid, dim3(GUIDE_THREADS), 0, st, P, Nf, w_copy, meta, sets, ok, g, grad_w);
     return hipGetLastError();
 }
 

@@ -137,9 +137,10 @@ inline size_t guide_scratch_bytes(int frames, int P) { return (size_t)frames * g
 // scan of the tile sums (which records T, n and S), the inclusive uint64 scan.  w: frames x P floats (device); w_copy: the context's copy of them (the build's
 // first launch writes it; every later launch reads the copy, so the caller may overwrite w in stream order)
 hipError_t guide_build(hipStream_t st, int frames, int P, const float* w, float* w_copy, uint64_t* cdf, uint64_t* coarse, GuideMeta* meta, void* scratch);
-// grad_w[f * P + p] += sum over the accepted hypotheses h of frame f of g[h] * ([p in set_h] / w_p - 4 / S_f), valid cells only; one launch
+// grad_w[f * P + p] += sum over the accepted hypotheses h of frame f of g[h] * ([p in set_h] / w_p - set_cells / S_f), valid cells only; one launch.
+// set_cells: cells per minimal set, 4 (sets N x 4) or 3 (the RGB-D sets, N x 3)
 hipError_t guide_backward(hipStream_t st, int frames, int P, int Nf, const float* w_copy, const GuideMeta* meta, const int32_t* sets, const uint8_t* ok,
-                          const double* g, double* grad_w);
+                          const double* g, double* grad_w, int set_cells = 4);
 struct K1Opts {
     int wpb = 1, prio = 3, hpw = 1, minw = 1;  // minw: minimum waves per SIMD of the register allocation (DSAC_K1_MINW)
     bool share_always = false;  // share beyond 1024 hypotheses as well (DSAC_K1_SHARE < 0)
@@ -327,8 +328,12 @@ hipError_t gather_patches(hipStream_t st, const uint8_t* bgr, int H, int W, cons
 // two launches: meta's reset, then the copy that canonicalises, counts and finds the first VALID cell.  src: frames x P x 3 (device)
 hipError_t rgbd_set_points(hipStream_t st, const float* src, const FrameDev& F, float* cam_copy, int32_t* meta);
 // sets N x 3.  sets_in: evaluated once each (one frame); else drawn from K1's counter stream, Nf > 0: hypothesis h belongs to frame h / Nf
+// guide: the table of dsac_set_sampling_weights_rgbd while those weights are active (drawn sets then come from it: the guided build), else nullptr
+struct RgbdGuide { const uint64_t* cdf; const GuideMeta* meta; const uint64_t* coarse; };
 hipError_t rgbd_sample(hipStream_t st, int N, uint64_t seed, const int32_t* sets_in, const FrameDev& F, const float* cam, const int32_t* meta, double thr,
-                       int max_tries, double* poses, int32_t* sets_out, uint8_t* ok, int Nf = 0);
+                       int max_tries, double* poses, int32_t* sets_out, uint8_t* ok, int Nf = 0, const RgbdGuide* guide = nullptr);
+// the masked weights of guided RGB-D sampling, one launch: out[f * P + p] = w[f * P + p] where the cell is VALID in the canonical copy, 0 elsewhere
+hipError_t rgbd_mask_weights(hipStream_t st, int frames, int P, const float* w, const float* cam, float* out);
 // rec: N x POSE_STRIDE floats (written here); err (N x P) and / or soft (N doubles; soft_part then holds rgbd_score_tiles(P) x N floats), either may be nullptr
 int rgbd_score_tiles(int P);
 hipError_t rgbd_score(hipStream_t st, int N, const double* poses, float* rec, const FrameDev& F, const float* cam, float clampv, float* err, float tau, float beta,

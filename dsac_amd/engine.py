@@ -867,9 +867,50 @@ class Engine:
         self.set_camera_points(pts)
         return pts
 
+    # ---- guided RGB-D sampling (dsac_set_sampling_weights_rgbd): weights of their own, masked with the camera points ---------------------------------
+    def set_sampling_weights_rgbd(self, w):
+        """Per-cell sampling weights of the RGB-D sampler for the frame(s) currently set: F x H*W (any shape with that many values), numpy or torch, any float
+        dtype, converted to float32; None clears them.  Needs camera points: a cell that is not VALID gets weight 0 before the table is built.  While they
+        are active sampleRGBD / processImageRGBD / processImagesRGBD draw cell p of frame f with probability m_p / T'_f (include/dsac_hip.h has the rule);
+        set_frame / set_frames and every set_camera_points clear them.  A torch device tensor only enqueues the table build.  With a table whose mass sits on
+        one or two cells pass max_tries explicitly: nearly every attempt fails to draw, and the default is 2^20."""
+        if w is None:
+            check(self._ctx, lib.dsac_set_sampling_weights_rgbd(self._ctx, None))
+            return
+        if hasattr(w, "data_ptr"):  # torch
+            import torch
+            w = w.detach().to(torch.float32).contiguous()
+        else:
+            w = np.ascontiguousarray(np.asarray(w), dtype=np.float32)
+        n = int(w.numel()) if hasattr(w, "numel") else int(w.size)
+        cells = getattr(self, "frames", 1) * self.P
+        if n != cells:
+            raise ValueError("dsac_amd: RGB-D sampling weights hold %d values, the frames currently set have %d cells" % (n, cells))
+        check(self._ctx, lib.dsac_set_sampling_weights_rgbd(self._ctx, ptr(w)))
+        self._keep_w_rgbd = w  # a device tensor is read in stream order, after this call has returned
+
+    def sampling_table_rgbd(self, out=None):
+        """The table the guided RGB-D draw uses (dsac_sampling_table_rgbd): F x H*W uint64, the inclusive sums of the quantised masses of the masked weights.
+        out: a preallocated buffer (numpy uint64, or a torch tensor of 8-byte integers), else a fresh numpy array."""
+        if out is None:
+            out = np.zeros((getattr(self, "frames", 1), self.P), np.uint64)
+        check(self._ctx, lib.dsac_sampling_table_rgbd(self._ctx, ptr(out)))
+        return out
+
+    def sampling_weights_backward_rgbd(self, sets, ok, g, grad=None):
+        """The score-function gradient of guided RGB-D training (dsac_sampling_weights_backward_rgbd): grad[f, p] += sum over the accepted hypotheses h of
+        frame f of g[h] * ([p in set_h] / w_p - 3 / S'_f) for every cell with mass.  sets F*N x 3 int32, ok F*N uint8, g F*N float64; grad F x H*W float64 is
+        accumulated into (fresh zeros without it) and returned."""
+        sets, ok, g = _np(sets, np.int32), _np(ok, np.uint8), _np(g, np.float64)
+        if grad is None:
+            grad = np.zeros((getattr(self, "frames", 1), self.P))
+        check(self._ctx, lib.dsac_sampling_weights_backward_rgbd(self._ctx, int(ok.shape[0]), ptr(sets), ptr(ok), ptr(g), ptr(grad)))
+        return grad
+
     def sampleRGBD(self, N, seed=1305, thr=100.0, max_tries=1 << 20, sets=None, out=None):
         """dsac_sample_rgbd: three-cell minimal sets from K1's counter stream (or `sets`, N x 3, evaluated once each), Horn's three-point alignment, the 3D check
-        |R X + t - C| < thr mm on the three cells.  Returns (poses N x 6, sets N x 3, ok N)."""
+        |R X + t - C| < thr mm on the three cells.  Drawn sets come from the masked table while set_sampling_weights_rgbd is active.  Returns (poses N x 6,
+        sets N x 3, ok N)."""
         if out is None:
             out = (np.zeros((N, 6)), np.zeros((N, 3), np.int32), np.zeros(N, np.uint8))
         poses, sets_out, ok = out

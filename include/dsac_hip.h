@@ -312,7 +312,8 @@ DSAC_API int dsac_sample(dsac_ctx* ctx, int N, uint64_t seed, const int32_t* set
  *   - dsac_sample_ahead: a slot keeps its frame across later set calls, the table has no such lifetime (the camera table's reason);
  *   - "k1_horn" = 1 in any call that draws: the Jacobi-sweep alignment has no guided build.
  * Not part of this: the C++ host shim and the driver programs; shard.ShardRunner; bench.py; e2e.ScoredFrameBatch; the reference stream and the pipelined
- * pair; weighting the soft-inlier score itself. */
+ * pair; weighting the soft-inlier score itself.  The RGB-D calls never read these weights: dsac_sample_rgbd draws from weights of its own, masked with the
+ * camera points (dsac_set_sampling_weights_rgbd, "RGB-D localisation" below), and refuses to run while these are active. */
 DSAC_API int dsac_set_sampling_weights(dsac_ctx* ctx, const float* weights_or_null);
 /* The table as built: cdf_out receives frames x H*W uint64 (C_f of every frame; host or device pointer) -- for tests and for a caller who wants to see what
  * was quantised.  DSAC_ERR_INVALID without active weights. */
@@ -659,8 +660,9 @@ DSAC_API int dsac_refine_soft_backward(dsac_ctx* ctx, int B, const double* ref_p
  * everywhere in this header: cv poses (Rodrigues | translation in mm), C = R X + t in OpenCV's camera frame (x right, y down, z forward), host or device
  * pointers detected per argument, device pointers only enqueue.  The camera intrinsics play no part in any RGB-D call: they work the same after dsac_set_frame,
  * dsac_set_frames and dsac_set_frames_cams.  dsac_softmax*, dsac_select*, dsac_loss* read poses and scores only and serve RGB-D unchanged.
- * NOT part of the RGB-D calls: the backward of any RGB-D stage, guided sampling with camera points, the reference-stream sampler and the pipelined pair,
- * 16-bit error images, the C++ host shim and the driver programs, sharding (shard.ShardRunner), e2e.py, bench.py.
+ * NOT part of the RGB-D calls: the backward of scoring, of the Kabsch hypotheses and of the refinement (the sampling weights do have their gradient:
+ * dsac_sampling_weights_backward_rgbd), the reference-stream sampler and the pipelined pair, 16-bit error images, the C++ host shim and the driver programs,
+ * sharding (shard.ShardRunner), e2e.py, bench.py.
  *
  * dsac_set_camera_points: cam_xyz is frames x H*W x 3 float32 millimetres, laid out like xyz, for the frame(s) currently set.  The context copies it and owns
  * the copy.  A cell is VALID when all three components of C_p are finite, C_p.z > 0, and all three components of X_p are finite; the copy holds NaN in all
@@ -683,10 +685,46 @@ DSAC_API int dsac_get_camera_points(dsac_ctx* ctx, float* cam_xyz_out_or_null, i
  *     walking max_tries
  *   given sets (sets_or_null != NULL, one frame only) are evaluated once each; a repeated, out-of-range or non-VALID cell gives ok = 0, a zero pose and
  *     sets_out = the given cells.  The drawn and the given path give the same pose bit for bit for the same set.
- * DSAC_ERR_INVALID with nothing enqueued: no camera points, sampling weights active (dsac_set_sampling_weights), given sets or N % frames != 0 on a frame
+ * DSAC_ERR_INVALID with nothing enqueued: no camera points, sampling weights active (dsac_set_sampling_weights: the 2D weights are not masked with the camera
+ * points; the RGB-D calls draw from dsac_set_sampling_weights_rgbd below, and the refusal holds whatever else is set), given sets or N % frames != 0 on a frame
  * batch, NULL outputs, max_tries <= 0 when drawing.  "pi_refstream" has no meaning here and is ignored.  DSAC_ERR_NO_FRAME without a frame. */
 DSAC_API int dsac_sample_rgbd(dsac_ctx* ctx, int N, uint64_t seed, const int32_t* sets_or_null, float thr, int max_tries, double* poses, int32_t* sets_out,
                               uint8_t* ok);
+/* GUIDED RGB-D SAMPLING: dsac_sample_rgbd draws its three-cell sets from per-cell weights -- a dynamic-object mask, a learned confidence, cells kept out of the
+ * minimal sets while scoring and refinement still use them.  A state of its own next to dsac_set_sampling_weights: the 2D table is untouched, 2D calls never
+ * read these weights, and the RGB-D calls never read the 2D ones.
+ * weights: frames x H*W float32 for the frame(s) currently set, host or device pointer; with a device pointer the call only enqueues (one masking launch, then
+ * the table build of dsac_set_sampling_weights) and returns, and the first launch copies the weights: the caller may overwrite the buffer afterwards in stream
+ * order.  Needs a frame (DSAC_ERR_NO_FRAME) and camera points (DSAC_ERR_INVALID).  NULL clears the weights; so do dsac_set_frame, dsac_set_frames,
+ * dsac_set_frames_cams and EVERY dsac_set_camera_points call, NULL or not: the mask belongs to the points it was built from.
+ * dsac_get_option("sampling_weights_rgbd") reads 1 while the weights are active (read-only, as "sampling_weights").
+ *   effective weight: w'_p = w_p where cell p is VALID in the sense of dsac_set_camera_points (read from the canonical copy), 0 elsewhere -- the mask is applied
+ *     before anything else, so a weight that is large only on depth holes does not shrink the masses of the measured cells
+ *   table of frame f: exactly the rule of dsac_set_sampling_weights applied to w': a cell has mass iff w'_p is finite and > 0, wmax'_f is the largest such w'_p,
+ *     m_p = floor((double) w'_p / (double) wmax'_f * 2^24), C'_f the inclusive uint64 sums, T'_f = C'_f[H*W - 1], n'_f the number of cells with mass, S'_f the
+ *     double sum of those w'_p.  The context owns this second table, its coarse level, its per-frame records and its copy of w'
+ *   dsac_sample_rgbd with sets_or_null == NULL while these weights are active (and no 2D weights are set): candidate k of attempt a of hypothesis h takes the
+ *     same 64-bit value as everywhere, v = mix64(key(h) + ((a << 16) | k)) with key(h) from seed + f * seed_stride, forms t = floor(v * T'_f / 2^64) and is the
+ *     smallest cell p with C'_f[p] > t: never a cell without mass, hence never one that is not VALID.  Candidates k = 0, 1, 2, ... are taken in order, one that is
+ *     already in the set is skipped, the attempt has its set at three cells, more than 32 candidates fail the attempt.  Everything after the draw is the uniform
+ *     call's: Horn's closed form, the finite check, the three residuals below thr in double, the first accepted attempt a < max_tries wins, else ok = 0, a zero
+ *     pose and sets_out = the set of attempt max_tries - 1 if it drew three cells, else zeros.  A frame with n'_f < 3 returns ok = 0, zero poses and zero sets for
+ *     all its hypotheses at once, without walking max_tries.  One evaluation site: the drawn and the given path give the same pose bit for bit for the same set
+ *   untouched by the weights: given sets, dsac_score_rgbd, dsac_refine_rgbd
+ * CAUTION: on a table whose mass sits almost entirely on one or two cells nearly every attempt fails to draw, and the kernel then walks up to max_tries attempts
+ * of 32 searches each: choose max_tries accordingly with such weights (the Python default is 2^20). */
+DSAC_API int dsac_set_sampling_weights_rgbd(dsac_ctx* ctx, const float* weights_or_null);
+/* The masked table as built: cdf_out receives frames x H*W uint64 (C'_f of every frame; host or device pointer).  DSAC_ERR_INVALID without active RGB-D
+ * weights. */
+DSAC_API int dsac_sampling_table_rgbd(dsac_ctx* ctx, uint64_t* cdf_out);
+/* The score-function gradient of guided RGB-D training: the gradient of sum_h g[h] * log p(set_h) under p(set) = prod_k w'_{c_k} / S'_f over the three cells.
+ * For every cell p of frame f with mass (w'_p finite and > 0)
+ *   grad_w[f * H*W + p] += sum over the hypotheses h of frame f with ok[h] of g[h] * ([p in set_h] / w_p - 3 / S'_f);
+ * cells without mass receive nothing and stay exactly as they were, cells named inside a set included.  sets is N x 3, N = frames x hypotheses per frame,
+ * frame-major, N > 0 and a multiple of the frame count, all pointers non-NULL (DSAC_ERR_INVALID otherwise); grad_w is frames x H*W doubles and is ACCUMULATED
+ * into.  One launch (fp64 atomics); the uniform term uses one correctly rounded sum of the accepted g per frame.  Needs active RGB-D weights (it reads w' from
+ * the context's copy): DSAC_ERR_INVALID otherwise. */
+DSAC_API int dsac_sampling_weights_backward_rgbd(dsac_ctx* ctx, int N, const int32_t* sets, const uint8_t* ok, const double* g, double* grad_w);
 /* Scoring: err[h][p] = min(|R_h X_p + t_h - C_p|, clamp) in mm, N x H*W float32, hypothesis-major (the layout of dsac_reproject); a cell that is not VALID
  * stores clamp.  soft[h] = sum_p sigmoid(beta (tau - err[h][p])) over the VALID cells; a cell that is not VALID contributes exactly 0.  Either output may be
  * NULL.  On a frame batch N = frames x (hypotheses per frame), frame-major.  Any N and any H x W: the map need not be a multiple of anything and err may be any
