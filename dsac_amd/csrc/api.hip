@@ -43,6 +43,29 @@ struct DevBuf {
     template <typename T> T* as() { return reinterpret_cast<T*>(p); }
 };
 
+// A guided-sampling table (dsac_set_sampling_weights / dsac_set_sampling_weights_rgbd): the table (frames x P uint64), its coarse level, the per-frame records
+// (T, n, S, the maximum) and the context's copy of the weights it was built from (the gradient reads their values).  active: weights are set for the current
+// frames; the buffers outlive it
+struct GuideTable {
+    DevBuf cdf, coarse, meta, w;
+    bool active = false;
+    // buffers that have to grow are replaced (hipFree waits for the device)
+    hipError_t reserve(int frames, int P) {
+        const size_t cells = (size_t)frames * (size_t)P;
+        hipError_t e = cdf.reserve(cells * sizeof(uint64_t));
+        if (e == hipSuccess) e = coarse.reserve((size_t)frames * (size_t)dk::guide_coarse_entries(P) * sizeof(uint64_t));
+        if (e == hipSuccess) e = w.reserve(cells * sizeof(float));
+        if (e == hipSuccess) e = meta.reserve((size_t)frames * sizeof(dk::GuideMeta));
+        v = dk::GuideView{cdf.as<uint64_t>(), meta.as<dk::GuideMeta>(), coarse.as<uint64_t>()};
+        return e;
+    }
+    void release() { cdf.release(); coarse.release(); meta.release(); w.release(); active = false; }
+    // what a sampler is handed: the table while the weights are active, else NULL
+    const dk::GuideView* view() const { return active ? &v : nullptr; }
+private:
+    dk::GuideView v{};
+};
+
 }  // namespace
 
 struct dsac_ctx {
@@ -60,19 +83,16 @@ struct dsac_ctx {
     // device table the kernels read; F.cams_h / F.cams point at them while the current frames carry per-frame cameras, else both are NULL
     std::vector<float> cams_h;
     DevBuf cams_d;
-    // guided sampling (dsac_set_sampling_weights): the table (frames x P uint64), the per-frame records (T, n, S, the maximum), the context's copy of the weights
-    // (the gradient reads their values) and the build's per-tile scratch.  k1.guide_cdf / k1.guide_meta point at them while weights are active, else both are NULL
-    DevBuf guide_cdf, guide_coarse, guide_meta, guide_w, guide_scratch;
     // RGB-D (dsac_set_camera_points): the canonical copy of the measured camera-frame points (frames x P x 3, NaN in every cell that is not VALID) and per frame
     // the VALID count and the first VALID cell.  have_cam: points are set for the current frames; every set-frame call clears it, as it clears the weights
     DevBuf cam_xyz, cam_meta, rgbd_rec, rgbd_soft_part, rgbd_scratch;
     bool have_cam = false;
-    // guided RGB-D sampling (dsac_set_sampling_weights_rgbd): a second table of its own -- table, coarse level, per-frame records and the context's copy of the
-    // MASKED weights w' (rgbd_guide_wm: where the mask launch writes them, rgbd_guide_w: the build's copy, which the gradient reads).  The build's per-tile
-    // scratch is guide_scratch, shared with the 2D table (builds are ordered by the stream).  have_rgbd_guide: those weights are active; they belong to the
-    // camera points they were masked with, so every dsac_set_camera_points call and every set-frame call clears it.  No 2D call reads any of this
-    DevBuf rgbd_guide_cdf, rgbd_guide_coarse, rgbd_guide_meta, rgbd_guide_w, rgbd_guide_wm;
-    bool have_rgbd_guide = false;
+    // guided sampling: the 2D table (dsac_set_sampling_weights) and a second one of the weights MASKED with the camera points (dsac_set_sampling_weights_rgbd;
+    // rgbd_guide_wm: where the mask launch writes them, the build's copy in the table is what the gradient reads), and the build's per-tile scratch, shared
+    // (builds are ordered by the stream).  Every set-frame call clears both; the RGB-D weights belong to the camera points they were masked with, so every
+    // dsac_set_camera_points call clears them too.  No 2D call reads the RGB-D table and no RGB-D call the 2D one
+    GuideTable guide, rgbd_guide;
+    DevBuf guide_scratch, rgbd_guide_wm;
 
     // scratch, one buffer per role so that calls can be chained without aliasing
     DevBuf rs_states, rs_scratch, rs_small, k6_scratch;  // the reference's random streams (dsac_refstream_init) and the scratch of a sampling window
@@ -421,7 +441,7 @@ int k2_soft_part(dsac_ctx* c, int N, bool want_err, bool want_soft, float* tau, 
 // for the shared camera.
 // Guided sampling: what a call must refuse while weights are active (dsac_set_sampling_weights), by the caller's name and before anything is enqueued.
 // guide_draw_check: a call that draws from K1's counter stream -- "k1_horn" has no guided build;  guide_refuse: a call whose draw cannot be guided at all
-bool guided(const dsac_ctx* c) { return c->k1.guide_cdf != nullptr; }
+bool guided(const dsac_ctx* c) { return c->guide.active; }
 int guide_draw_check(dsac_ctx* c, const char* who) {
     if (guided(c) && c->k1.horn)
         return fail(c, DSAC_ERR_INVALID, "%s: sampling weights are active (dsac_set_sampling_weights) and \"k1_horn\" is 1: the Jacobi-sweep alignment has no guided build "
@@ -635,9 +655,8 @@ void dsac_destroy(dsac_ctx* c) {
     if (c->aux) (void)hipStreamSynchronize(c->aux);
     if (c->aux2) (void)hipStreamSynchronize(c->aux2);
     c->frame_xyz.release(); c->frame_uv.release(); c->cams_d.release();
-    c->guide_cdf.release(); c->guide_coarse.release(); c->guide_meta.release(); c->guide_w.release(); c->guide_scratch.release();
+    c->guide.release(); c->rgbd_guide.release(); c->guide_scratch.release(); c->rgbd_guide_wm.release();
     c->cam_xyz.release(); c->cam_meta.release(); c->rgbd_rec.release(); c->rgbd_soft_part.release(); c->rgbd_scratch.release();
-    c->rgbd_guide_cdf.release(); c->rgbd_guide_coarse.release(); c->rgbd_guide_meta.release(); c->rgbd_guide_w.release(); c->rgbd_guide_wm.release();
     c->staged.release(); c->staged_lo.release(); c->staged_split.release(); c->rs_states.release(); c->rs_scratch.release(); c->rs_small.release(); c->k6_scratch.release(); c->soft_scratch.release(); c->soft_part.release(); c->bwd_staged.release(); c->dRdH.release();
     c->grad_part.release(); c->g12_part.release(); c->g6.release();
     for (auto& s : c->slots) s.release();
@@ -780,10 +799,9 @@ static int set_frames_common(dsac_ctx* c, int frames, const float* xyz, const fl
         c->F.cams = nullptr;
         c->F.cams_h = nullptr;
     }
-    c->k1.guide_cdf = nullptr;  // the sampling weights belong to the frames they were set for
-    c->k1.guide_meta = nullptr;
-    c->have_cam = false;        // ... and so do the camera points (dsac_set_camera_points)
-    c->have_rgbd_guide = false; // ... and the RGB-D sampling weights masked with them (dsac_set_sampling_weights_rgbd)
+    c->guide.active = false;       // the sampling weights belong to the frames they were set for
+    c->have_cam = false;           // ... and so do the camera points (dsac_set_camera_points)
+    c->rgbd_guide.active = false;  // ... and the RGB-D sampling weights masked with them (dsac_set_sampling_weights_rgbd)
     c->F.xyz = new_xyz;
     c->F.uv = new_uv;
     c->F.H = H; c->F.W = W; c->F.P = (int)P1;
@@ -906,57 +924,47 @@ int dsac_set_frames_cams(dsac_ctx* c, int frames, const float* xyz, const float*
 }
 
 // ---- guided sampling: K1 draws its minimal sets from per-cell weights (include/dsac_hip.h has the contract) ----------------------------------
-int dsac_set_sampling_weights(dsac_ctx* c, const float* weights_or_null) {
-    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_set_sampling_weights: ctx is NULL");
-    if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "dsac_set_sampling_weights: no frame set (the weights belong to the frames currently set)");
-    if (!weights_or_null) {
-        c->k1.guide_cdf = nullptr;
-        c->k1.guide_meta = nullptr;
-        return DSAC_OK;
-    }
+// The bodies of the 2D and the RGB-D calls (the RGB-D ones: further down, with the camera points); the public calls check their preconditions and name the table.
+// set: mask = the RGB-D table's first launch, w' = w where the cell is VALID in the canonical copy and 0 elsewhere; the build then runs on w', in stream order
+static int guide_set(dsac_ctx* c, GuideTable& t, const float* weights, bool mask) {
     HIP_TRY(c, hipSetDevice(c->device));
-    // The table is touched on the context's stream only (the build here, K1, the gradient): a build is ordered behind every earlier K1 launch by the stream
-    // itself, and a deferred refinement tail reads none of it.  A host pointer goes through a staging slot like every host argument: the tail is joined then
-    begin_call(c, /*keep_tail=*/is_device_ptr(weights_or_null, c));
+    // The table is touched on the context's stream only (the build here, the sampler, the gradient): a build is ordered behind every earlier sampling launch by the
+    // stream itself, and a deferred refinement tail reads none of it.  A host pointer goes through a staging slot like every host argument: the tail is joined then
+    begin_call(c, /*keep_tail=*/is_device_ptr(weights, c));
     const int frames = c->F.frames > 1 ? c->F.frames : 1, P = c->F.P;
     const size_t cells = (size_t)frames * (size_t)P;
     const float* d_w;
-    ARG_TRY(in_arg(c, weights_or_null, cells, &d_w));
-    // buffers that have to grow are replaced (hipFree waits for the device); a failed allocation leaves the weights cleared, never half a table
-    c->k1.guide_cdf = nullptr;
-    c->k1.guide_meta = nullptr;
-    HIP_TRY(c, c->guide_cdf.reserve(cells * sizeof(uint64_t)));
-    HIP_TRY(c, c->guide_coarse.reserve((size_t)frames * (size_t)dk::guide_coarse_entries(P) * sizeof(uint64_t)));
-    HIP_TRY(c, c->guide_w.reserve(cells * sizeof(float)));
-    HIP_TRY(c, c->guide_meta.reserve((size_t)frames * sizeof(dk::GuideMeta)));
+    ARG_TRY(in_arg(c, weights, cells, &d_w));
+    // a failed allocation leaves the weights cleared, never half a table
+    t.active = false;
+    HIP_TRY(c, t.reserve(frames, P));
     HIP_TRY(c, c->guide_scratch.reserve(dk::guide_scratch_bytes(frames, P)));
-    HIP_TRY(c, dk::guide_build(c->stream, frames, P, d_w, c->guide_w.as<float>(), c->guide_cdf.as<uint64_t>(), c->guide_coarse.as<uint64_t>(),
-                               c->guide_meta.as<dk::GuideMeta>(), c->guide_scratch.p));
-    c->k1.guide_cdf = c->guide_cdf.as<uint64_t>();
-    c->k1.guide_meta = c->guide_meta.as<dk::GuideMeta>();
-    c->k1.guide_coarse = c->guide_coarse.as<uint64_t>();
+    if (mask) {
+        HIP_TRY(c, c->rgbd_guide_wm.reserve(cells * sizeof(float)));
+        HIP_TRY(c, dk::rgbd_mask_weights(c->stream, frames, P, d_w, c->cam_xyz.as<float>(), c->rgbd_guide_wm.as<float>()));
+        d_w = c->rgbd_guide_wm.as<float>();
+    }
+    HIP_TRY(c, dk::guide_build(c->stream, frames, P, d_w, t.w.as<float>(), t.cdf.as<uint64_t>(), t.coarse.as<uint64_t>(), t.meta.as<dk::GuideMeta>(), c->guide_scratch.p));
+    t.active = true;
     return DSAC_OK;
 }
 
-int dsac_sampling_table(dsac_ctx* c, uint64_t* cdf_out) {
-    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_sampling_table: ctx is NULL");
-    if (!c->have_frame || !guided(c)) return fail(c, DSAC_ERR_INVALID, "dsac_sampling_table: no sampling weights are active (dsac_set_sampling_weights)");
-    if (!cdf_out) return fail(c, DSAC_ERR_INVALID, "dsac_sampling_table: cdf_out is NULL (frames x H*W uint64)");
+static int guide_read(dsac_ctx* c, GuideTable& t, const char* who, uint64_t* cdf_out) {
+    if (!cdf_out) return fail(c, DSAC_ERR_INVALID, "%s: cdf_out is NULL (frames x H*W uint64)", who);
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c);
     const size_t cells = (size_t)(c->F.frames > 1 ? c->F.frames : 1) * (size_t)c->F.P;
     uint64_t* d_out;
     ARG_TRY(out_arg(c, cdf_out, cells, &d_out));
-    HIP_TRY(c, hipMemcpyAsync(d_out, c->k1.guide_cdf, cells * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_out, t.cdf.p, cells * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
     return end_call(c);
 }
 
-int dsac_sampling_weights_backward(dsac_ctx* c, int N, const int32_t* sets, const uint8_t* ok, const double* g, double* grad_w) {
-    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_sampling_weights_backward: ctx is NULL");
-    if (!c->have_frame || !guided(c)) return fail(c, DSAC_ERR_INVALID, "dsac_sampling_weights_backward: no sampling weights are active (dsac_set_sampling_weights)");
+// set_cells: cells per minimal set, 4 or 3 (RGB-D, whose copy holds the masked weights: a cell that is not VALID has weight 0 there and receives nothing)
+static int guide_backward(dsac_ctx* c, GuideTable& t, const char* who, int set_cells, int N, const int32_t* sets, const uint8_t* ok, const double* g, double* grad_w) {
     const int frames = c->F.frames > 1 ? c->F.frames : 1;
     if (N <= 0 || N % frames != 0 || !sets || !ok || !g || !grad_w)
-        return fail(c, DSAC_ERR_INVALID, "dsac_sampling_weights_backward: N > 0, a multiple of the %d frame(s), and sets / ok / g / grad_w must be non-NULL", frames);
+        return fail(c, DSAC_ERR_INVALID, "%s: N > 0, a multiple of the %d frame(s), and sets / ok / g / grad_w must be non-NULL", who, frames);
     HIP_TRY(c, hipSetDevice(c->device));
     begin_call(c);
     const size_t cells = (size_t)frames * (size_t)c->F.P;
@@ -964,12 +972,38 @@ int dsac_sampling_weights_backward(dsac_ctx* c, int N, const int32_t* sets, cons
     const uint8_t* d_ok;
     const double* d_g;
     double* d_grad;
-    ARG_TRY(in_arg(c, sets, (size_t)N * 4, &d_sets));
+    ARG_TRY(in_arg(c, sets, (size_t)N * set_cells, &d_sets));
     ARG_TRY(in_arg(c, ok, (size_t)N, &d_ok));
     ARG_TRY(in_arg(c, g, (size_t)N, &d_g));
     ARG_TRY(out_arg(c, grad_w, cells, &d_grad, /*preload=*/true));  // accumulated into, like grad_xyz
-    HIP_TRY(c, dk::guide_backward(c->stream, frames, c->F.P, N / frames, c->guide_w.as<float>(), c->k1.guide_meta, d_sets, d_ok, d_g, d_grad));
+    HIP_TRY(c, dk::guide_backward(c->stream, frames, c->F.P, N / frames, t.w.as<float>(), t.meta.as<dk::GuideMeta>(), d_sets, d_ok, d_g, d_grad, set_cells));
     return end_call(c);
+}
+
+int dsac_set_sampling_weights(dsac_ctx* c, const float* weights_or_null) {
+    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_set_sampling_weights: ctx is NULL");
+    if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "dsac_set_sampling_weights: no frame set (the weights belong to the frames currently set)");
+    if (!weights_or_null) {
+        c->guide.active = false;
+        return DSAC_OK;
+    }
+    return guide_set(c, c->guide, weights_or_null, /*mask=*/false);
+}
+
+static int guide_check(dsac_ctx* c, const char* who) {
+    if (!c) return fail(nullptr, DSAC_ERR_INVALID, "%s: ctx is NULL", who);
+    if (!c->have_frame || !guided(c)) return fail(c, DSAC_ERR_INVALID, "%s: no sampling weights are active (dsac_set_sampling_weights)", who);
+    return DSAC_OK;
+}
+
+int dsac_sampling_table(dsac_ctx* c, uint64_t* cdf_out) {
+    ARG_TRY(guide_check(c, "dsac_sampling_table"));
+    return guide_read(c, c->guide, "dsac_sampling_table", cdf_out);
+}
+
+int dsac_sampling_weights_backward(dsac_ctx* c, int N, const int32_t* sets, const uint8_t* ok, const double* g, double* grad_w) {
+    ARG_TRY(guide_check(c, "dsac_sampling_weights_backward"));
+    return guide_backward(c, c->guide, "dsac_sampling_weights_backward", 4, N, sets, ok, g, grad_w);
 }
 
 int dsac_sample(dsac_ctx* c, int N, uint64_t seed, const int32_t* sets_or_null, float thr, int max_tries, double* poses, int32_t* sets_out,
@@ -996,7 +1030,7 @@ int dsac_sample(dsac_ctx* c, int N, uint64_t seed, const int32_t* sets_or_null, 
     ARG_TRY(out_arg(c, poses, (size_t)N * 6, &d_poses));
     ARG_TRY(out_arg(c, sets_out, (size_t)N * 4, &d_sets_out));
     ARG_TRY(out_arg(c, ok, (size_t)N, &d_ok));
-    HIP_TRY(c, dk::sample(c->stream, N, seed, d_sets_in, c->F, (int)thr, max_tries, d_poses, d_sets_out, d_ok, nullptr, frames > 1 ? N / frames : 0, c->k1));
+    HIP_TRY(c, dk::sample(c->stream, N, seed, d_sets_in, c->F, (int)thr, max_tries, d_poses, d_sets_out, d_ok, nullptr, frames > 1 ? N / frames : 0, c->k1, c->guide.view()));
     return end_call(c);
 }
 
@@ -1246,7 +1280,7 @@ static int score_hypotheses_common(dsac_ctx* c, int N, int Nf, uint64_t seed, co
         const int tk = pi_tail_index(2, b, N, (long long)P);
         ARG_TRY(pi_tail_setup(c, 2, tk));
         if (c->pi_scored_rec[b]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->pi_scored[b], 0));  // K3 of the call two back read this half's arrays
-        HIP_TRY(c, dk::sample(c->stream, N, seed, nullptr, c->F, (int)thr, max_tries, d_poses, d_sets_out, d_ok, c->staged.as<float>(), Nf, c->k1));
+        HIP_TRY(c, dk::sample(c->stream, N, seed, nullptr, c->F, (int)thr, max_tries, d_poses, d_sets_out, d_ok, c->staged.as<float>(), Nf, c->k1, c->guide.view()));
         int used_d = 0;
         hipEvent_t k2_done = nullptr;
         // the tail's start rides on K2's own dispatch packet (pi_k2done as its stop event): no record between K2 and the next K1
@@ -1260,7 +1294,7 @@ static int score_hypotheses_common(dsac_ctx* c, int N, int Nf, uint64_t seed, co
     }
     HIP_TRY(c, c->soft_part.reserve((size_t)tiles * N * sizeof(float)));
     // K1 writes the poses AND their staged K2 records (no separate pose_prep launch)
-    HIP_TRY(c, dk::sample(c->stream, N, seed, d_sets_in, c->F, (int)thr, max_tries, d_poses, d_sets_out, d_ok, c->staged.as<float>(), Nf, c->k1));
+    HIP_TRY(c, dk::sample(c->stream, N, seed, d_sets_in, c->F, (int)thr, max_tries, d_poses, d_sets_out, d_ok, c->staged.as<float>(), Nf, c->k1, c->guide.view()));
     int used = 0;
     ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, dk::K2_ELEM_F32, c->soft_part.as<float>(), /*gated=*/true, nullptr, &used));
     HIP_TRY(c, score_tail(c->stream, Nf > 0 ? Nf : N, frames, used, c->soft_part.as<float>(), d_scores, scale, d_w, d_ent, avg6_or_null ? d_poses : nullptr,
@@ -1343,7 +1377,7 @@ int dsac_sample_ahead(dsac_ctx* c, int slot, int N, uint64_t seed, const int32_t
     if (c->slot_done_recorded[slot]) HIP_TRY(c, hipStreamWaitEvent(c->aux, c->slot_done[slot], 0));
     HIP_TRY(c, hipStreamWaitEvent(c->aux, c->frame_ready, 0));  // a frame copy enqueued on the main stream has landed
     c->slot_F[slot] = c->F;  // the slot scores against the frame it was sampled from, whatever is current at score time
-    HIP_TRY(c, dk::sample(c->aux, N, seed, sets_or_null, c->F, (int)thr, max_tries, poses, sets_out, ok, c->slot_staged[slot].as<float>(), Nf, c->k1));
+    HIP_TRY(c, dk::sample(c->aux, N, seed, sets_or_null, c->F, (int)thr, max_tries, poses, sets_out, ok, c->slot_staged[slot].as<float>(), Nf, c->k1, c->guide.view()));
     HIP_TRY(c, hipEventRecord(c->slot_ready[slot], c->aux));
     c->slot_N[slot] = N;
     c->slot_pending[slot] = true;
@@ -1520,7 +1554,7 @@ int dsac_get_option(dsac_ctx* c, const char* key, int* value) {
     else if (k == "pi_defer_tail") *value = c->pi_defer_tail;
     else if (k == "k1_cus") *value = c->k1_cus;
     else if (k == "sampling_weights") *value = (c->have_frame && guided(c)) ? 1 : 0;  // read-only: sampling weights are active (dsac_set_sampling_weights)
-    else if (k == "sampling_weights_rgbd") *value = (c->have_frame && c->have_cam && c->have_rgbd_guide) ? 1 : 0;  // read-only: RGB-D sampling weights are active (dsac_set_sampling_weights_rgbd)
+    else if (k == "sampling_weights_rgbd") *value = (c->have_frame && c->have_cam && c->rgbd_guide.active) ? 1 : 0;  // read-only: RGB-D sampling weights are active (dsac_set_sampling_weights_rgbd)
     else if (k == "camera_points") *value = (c->have_frame && c->have_cam) ? 1 : 0;  // read-only: camera points are set (dsac_set_camera_points)
     else if (k == "frame_cams") *value = (c->have_frame && c->F.cams) ? 1 : 0;  // read-only: the current frames carry one camera each (dsac_set_frames_cams)
     else return fail(c, DSAC_ERR_INVALID, "dsac_get_option: unknown key '%s'", key);
@@ -2455,7 +2489,7 @@ int dsac_process_images(dsac_ctx* c, int hyps_per_frame, uint64_t seed, float th
     //   K1 sample + P3P (:1010-1060)  ->  K2 error images + soft-inlier sums (:1067-1072)  ->  scores  ->  K3 softmax / entropy / soft-argmax
     //   (:1078-1094)  ->  K6 the refinement loop, one wave per frame (:1099-1154)  ->  K7 maxLoss against each frame's ground truth (:1160-1179)
     if (c->pi_refstream) ARG_TRY(pi_refstream_k1(c, "dsac_process_images", hyps_per_frame, thr, d_poses, d_sets, d_ok));
-    else HIP_TRY(c, dk::sample(c->stream, N, seed, nullptr, c->F, (int)thr, max_tries, d_poses, d_sets, d_ok, c->staged.as<float>(), Nf, c->k1));
+    else HIP_TRY(c, dk::sample(c->stream, N, seed, nullptr, c->F, (int)thr, max_tries, d_poses, d_sets, d_ok, c->staged.as<float>(), Nf, c->k1, c->guide.view()));
     int used = 0;
     // mode 2: the tail starts behind K2.  The event it waits for rides on K2's own dispatch packet (hipExtLaunchKernelGGL's stop event) -- an event
     // RECORD between K2 and the next call's K1 is a packet of its own and a ~7 us bubble on the stream that bounds the loop (rank step of configs[3]:
@@ -2527,7 +2561,7 @@ static int pi_begin_call(dsac_ctx* c, const char* who, int hyps_per_frame, uint6
     float* d_part = nullptr;
     ARG_TRY(k2_soft_part(c, N, d_err != nullptr, d_soft != nullptr, &tau, &beta, &d_part));
     if (c->pi_refstream) ARG_TRY(pi_refstream_k1(c, who, hyps_per_frame, thr, d_poses, d_sets, d_ok));
-    else HIP_TRY(c, dk::sample(c->stream, N, seed, nullptr, c->F, (int)thr, max_tries, d_poses, d_sets, d_ok, c->staged.as<float>(), Nf, c->k1));
+    else HIP_TRY(c, dk::sample(c->stream, N, seed, nullptr, c->F, (int)thr, max_tries, d_poses, d_sets, d_ok, c->staged.as<float>(), Nf, c->k1, c->guide.view()));
     int used = 0;
     ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, elem, d_part, /*gated=*/true, nullptr, &used));
     if (d_soft) HIP_TRY(c, dk::reduce_soft(c->stream, N, used, d_part, d_soft));
@@ -2677,7 +2711,7 @@ static int rgbd_check(dsac_ctx* c, const char* who) {
 int dsac_set_camera_points(dsac_ctx* c, const float* cam_xyz_or_null) {
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "dsac_set_camera_points: ctx is NULL");
     if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "dsac_set_camera_points: no frame set (the points belong to the frames currently set)");
-    c->have_rgbd_guide = false;  // the RGB-D sampling weights were masked with the points this call replaces or clears
+    c->rgbd_guide.active = false;  // the RGB-D sampling weights were masked with the points this call replaces or clears
     if (!cam_xyz_or_null) {
         c->have_cam = false;
         return DSAC_OK;
@@ -2706,74 +2740,28 @@ int dsac_set_sampling_weights_rgbd(dsac_ctx* c, const float* weights_or_null) {
     if (!c->have_frame) return fail(c, DSAC_ERR_NO_FRAME, "%s: no frame set (the weights belong to the frames currently set)", who);
     if (!c->have_cam) return fail(c, DSAC_ERR_INVALID, "%s: no camera points are set for the current frame(s) (dsac_set_camera_points): the weights are masked with them", who);
     if (!weights_or_null) {
-        c->have_rgbd_guide = false;
+        c->rgbd_guide.active = false;
         return DSAC_OK;
     }
-    HIP_TRY(c, hipSetDevice(c->device));
-    // as dsac_set_sampling_weights: the table is touched on the context's stream only, a host pointer goes through a staging slot (the tail is joined then)
-    begin_call(c, /*keep_tail=*/is_device_ptr(weights_or_null, c));
-    const int frames = c->F.frames > 1 ? c->F.frames : 1, P = c->F.P;
-    const size_t cells = (size_t)frames * (size_t)P;
-    const float* d_w;
-    ARG_TRY(in_arg(c, weights_or_null, cells, &d_w));
-    // buffers that have to grow are replaced (hipFree waits for the device); a failed allocation leaves the weights cleared, never half a table
-    c->have_rgbd_guide = false;
-    HIP_TRY(c, c->rgbd_guide_cdf.reserve(cells * sizeof(uint64_t)));
-    HIP_TRY(c, c->rgbd_guide_coarse.reserve((size_t)frames * (size_t)dk::guide_coarse_entries(P) * sizeof(uint64_t)));
-    HIP_TRY(c, c->rgbd_guide_w.reserve(cells * sizeof(float)));
-    HIP_TRY(c, c->rgbd_guide_wm.reserve(cells * sizeof(float)));
-    HIP_TRY(c, c->rgbd_guide_meta.reserve((size_t)frames * sizeof(dk::GuideMeta)));
-    HIP_TRY(c, c->guide_scratch.reserve(dk::guide_scratch_bytes(frames, P)));
-    // the first launch reads the caller's weights and the canonical copy and writes w'; the 2D build then runs on w', in stream order
-    HIP_TRY(c, dk::rgbd_mask_weights(c->stream, frames, P, d_w, c->cam_xyz.as<float>(), c->rgbd_guide_wm.as<float>()));
-    HIP_TRY(c, dk::guide_build(c->stream, frames, P, c->rgbd_guide_wm.as<float>(), c->rgbd_guide_w.as<float>(), c->rgbd_guide_cdf.as<uint64_t>(),
-                               c->rgbd_guide_coarse.as<uint64_t>(), c->rgbd_guide_meta.as<dk::GuideMeta>(), c->guide_scratch.p));
-    c->have_rgbd_guide = true;
-    return DSAC_OK;
+    return guide_set(c, c->rgbd_guide, weights_or_null, /*mask=*/true);
 }
 
 // the RGB-D weights are active only together with the camera points they were masked with
 static int rgbd_guide_check(dsac_ctx* c, const char* who) {
     if (!c) return fail(nullptr, DSAC_ERR_INVALID, "%s: ctx is NULL", who);
-    if (!c->have_frame || !c->have_cam || !c->have_rgbd_guide)
+    if (!c->have_frame || !c->have_cam || !c->rgbd_guide.active)
         return fail(c, DSAC_ERR_INVALID, "%s: no RGB-D sampling weights are active (dsac_set_sampling_weights_rgbd)", who);
     return DSAC_OK;
 }
 
 int dsac_sampling_table_rgbd(dsac_ctx* c, uint64_t* cdf_out) {
-    const char* who = "dsac_sampling_table_rgbd";
-    ARG_TRY(rgbd_guide_check(c, who));
-    if (!cdf_out) return fail(c, DSAC_ERR_INVALID, "%s: cdf_out is NULL (frames x H*W uint64)", who);
-    HIP_TRY(c, hipSetDevice(c->device));
-    begin_call(c);
-    const size_t cells = (size_t)(c->F.frames > 1 ? c->F.frames : 1) * (size_t)c->F.P;
-    uint64_t* d_out;
-    ARG_TRY(out_arg(c, cdf_out, cells, &d_out));
-    HIP_TRY(c, hipMemcpyAsync(d_out, c->rgbd_guide_cdf.p, cells * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
-    return end_call(c);
+    ARG_TRY(rgbd_guide_check(c, "dsac_sampling_table_rgbd"));
+    return guide_read(c, c->rgbd_guide, "dsac_sampling_table_rgbd", cdf_out);
 }
 
 int dsac_sampling_weights_backward_rgbd(dsac_ctx* c, int N, const int32_t* sets, const uint8_t* ok, const double* g, double* grad_w) {
-    const char* who = "dsac_sampling_weights_backward_rgbd";
-    ARG_TRY(rgbd_guide_check(c, who));
-    const int frames = c->F.frames > 1 ? c->F.frames : 1;
-    if (N <= 0 || N % frames != 0 || !sets || !ok || !g || !grad_w)
-        return fail(c, DSAC_ERR_INVALID, "%s: N > 0, a multiple of the %d frame(s), and sets / ok / g / grad_w must be non-NULL", who, frames);
-    HIP_TRY(c, hipSetDevice(c->device));
-    begin_call(c);
-    const size_t cells = (size_t)frames * (size_t)c->F.P;
-    const int32_t* d_sets;
-    const uint8_t* d_ok;
-    const double* d_g;
-    double* d_grad;
-    ARG_TRY(in_arg(c, sets, (size_t)N * 3, &d_sets));
-    ARG_TRY(in_arg(c, ok, (size_t)N, &d_ok));
-    ARG_TRY(in_arg(c, g, (size_t)N, &d_g));
-    ARG_TRY(out_arg(c, grad_w, cells, &d_grad, /*preload=*/true));  // accumulated into, like grad_xyz
-    // the context's copy holds the masked weights: a cell that is not VALID has weight 0 there and receives nothing
-    HIP_TRY(c, dk::guide_backward(c->stream, frames, c->F.P, N / frames, c->rgbd_guide_w.as<float>(), c->rgbd_guide_meta.as<dk::GuideMeta>(), d_sets, d_ok, d_g, d_grad,
-                                  /*set_cells=*/3));
-    return end_call(c);
+    ARG_TRY(rgbd_guide_check(c, "dsac_sampling_weights_backward_rgbd"));
+    return guide_backward(c, c->rgbd_guide, "dsac_sampling_weights_backward_rgbd", 3, N, sets, ok, g, grad_w);
 }
 
 int dsac_get_camera_points(dsac_ctx* c, float* cam_xyz_out_or_null, int32_t* valid_out_or_null) {
@@ -2814,9 +2802,8 @@ int dsac_sample_rgbd(dsac_ctx* c, int N, uint64_t seed, const int32_t* sets_or_n
     ARG_TRY(out_arg(c, sets_out, (size_t)N * 3, &d_sets_out));
     ARG_TRY(out_arg(c, ok, (size_t)N, &d_ok));
     // drawn sets come from the masked table while RGB-D sampling weights are active; given sets never look at it
-    const dk::RgbdGuide guide{c->rgbd_guide_cdf.as<uint64_t>(), c->rgbd_guide_meta.as<dk::GuideMeta>(), c->rgbd_guide_coarse.as<uint64_t>()};
     HIP_TRY(c, dk::rgbd_sample(c->stream, N, seed, d_sets_in, c->F, c->cam_xyz.as<float>(), c->cam_meta.as<int32_t>(), (double)thr, max_tries, d_poses, d_sets_out, d_ok,
-                               frames > 1 ? N / frames : 0, c->have_rgbd_guide ? &guide : nullptr));
+                               frames > 1 ? N / frames : 0, c->rgbd_guide.view()));
     return end_call(c);
 }
 

@@ -22,6 +22,7 @@
 #include "kernels.h"
 #include "dmath.h"
 #include "loss_math.h"
+#include "soft_loop.h"
 
 namespace dk {
 
@@ -70,12 +71,6 @@ constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_HALF_MIRROR = 0x141, DPP_MIR
 // value of lane (l ^ 4): lanes with bit 2 clear read from l + 4, the others from l - 4 (bank masks pick the lanes that take each move)
 DM_INLINE double dxor4(double v) { return ddpp<DPP_SHR4, 0xA>(ddpp<DPP_SHL4, 0x5>(v, v), v); }
 
-DM_INLINE void wave_sync_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // one value, result in every lane (the same bits everywhere: each stage adds the same two partial sums in both partners)
 DM_INLINE double wave_allsum(double v) {
     v += ddpp<DPP_XOR1>(v, v);
@@ -118,9 +113,9 @@ DM_INLINE void wave_allsum32(double (&v)[32], double* s_out) {
     const int idx = ((lane >> 3) & 1) + 2 * ((lane >> 1) & 1) + 4 * (lane & 1) + 8 * ((lane >> 4) & 1) + 16 * ((lane >> 5) & 1);
     // one wave per workgroup: its LDS operations execute in order, so a wave barrier (no counter wait: global loads may stay in
     // flight) is all that separates the readers of the previous result, this write, and the readers of this one
-    wave_sync_lds();
+    wave_lds_sync();
     s_out[idx] = r;
-    wave_sync_lds();
+    wave_lds_sync();
 }
 
 // Solve of the symmetric positive definite 6x6 system A x = b (upper triangle of A, row-major 6x6) by L D L^T: six reciprocals and no
@@ -574,7 +569,7 @@ __global__ __launch_bounds__(64 * S) void k_refine(int B, const int32_t* __restr
         }
         // the head of the next step's walk does not depend on the pose: its loads fly under the LM solve
         if (step + 1 < steps) load_walk_cells(pidx + P, 0, lane, F, cells);
-        wave_sync_lds();
+        wave_lds_sync();
         const int n = min(cnt, max_inl);
         if (n < min_inl) break;  // abort for stability: too few inliers (core/cnn_softam.h:700, 1136)
         double upd[6];
@@ -900,7 +895,7 @@ __global__ __launch_bounds__(64) void k_refine_lm(int B, double* __restrict__ po
         run += __builtin_amdgcn_readlane(incl, 63);
         used = min(j0 + 64, nchunks);
     }
-    wave_sync_lds();
+    wave_lds_sync();
     const int n = min(run, max_inl);
     for (int e = lane; e < n; e += 64) {
         int lo = 0, hi = used - 1;  // the last chunk whose first entry is at or before e (empty chunks share their successor's start and lose to it)
@@ -914,7 +909,7 @@ __global__ __launch_bounds__(64) void k_refine_lm(int B, double* __restrict__ po
         if (inlier_map && (map_stride > 0 || b == 0)) atomicAdd(&inlier_map[(size_t)b * map_stride + __float_as_int(r[3])], 1);
     }
     if (n < min_inl) { if (lane == 0) alive[b] = 0; return; }  // abort for stability: too few inliers (core/cnn_softam.h:700, 1136)
-    wave_sync_lds();
+    wave_lds_sync();
     const dm::Cam K = make_cam_r(F);
     double upd[6];
 #pragma unroll
@@ -958,7 +953,6 @@ __global__ void k_refine_split_init(int B, int Bp, FrameDev F, const double* __r
 }
 
 static int g_scan_tune = 0;  // A/B ("k6_scan_tune"): bits 0-7 problems per wave (1, 2, 4; 0 = by the problem count), bits 8-23 chunk cells (multiple of 256; 0 = auto), bit 24: no skip check
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 // chunk of the scan: 2 048 cells (eight reads of 256), smaller on maps that would not give the chip 8 192 waves otherwise
 static int scan_chunk_cells(int B, int P) {
     int c = 2048;
@@ -1520,7 +1514,7 @@ __global__ __launch_bounds__(64) void k_refine_gn(int B, const double* __restric
             cnt += __popcll(m);
         }
     }
-    wave_sync_lds();
+    wave_lds_sync();
     const int n = min(cnt, max_inl);
     if (n < min_inl) {
         if (lane == 0 && n_out) n_out[b] = 0;
@@ -1570,7 +1564,7 @@ __global__ __launch_bounds__(64) void k_refine_gn(int B, const double* __restric
                 s_M[30 + j] = -Ai[30 + j];
             }
         }
-        wave_sync_lds();
+        wave_lds_sync();
     }
     if (!ok) {  // a non-positive pivot: A is not positive definite to working precision
         if (lane == 0 && n_out) n_out[b] = 0;
@@ -1638,17 +1632,16 @@ hipError_t refine_gn(hipStream_t st, int B, const double* ref_poses, const int32
 // A = sum w J^T J, g = sum w J^T r.  Two forms of the forward loop: split (a pass kernel on cell chunks x problems whose per-chunk sums go to scratch, and a
 // one-wave step kernel that adds them in index order, decides and moves the pose; the host enqueues max_iters + 1 of each with no round trip) and fused (one
 // workgroup per problem runs the whole loop).  Both call soft_cell / soft_accumulate per cell and soft_decide per iteration.  No floating-point atomics
-// anywhere: every sum has one order, so two calls give the same bits.
+// anywhere: every sum has one order, so two calls give the same bits.  The loop itself -- statuses, state and scratch, ordered sum, decision, step kernel,
+// host loop -- is soft_loop.h's, shared with dsac_refine_rgbd; Soft2D below is this path's policy.
 constexpr int SOFT_NACC = 28;      // 21 of A (packed upper triangle, lm_eval's order), 6 of g, S
-constexpr int SOFT_STATE = 16;     // doubles per problem between the launches of the split form: pose (6), trial pose (6), S, 3 unused
-constexpr int SOFT_REC = 26;       // doubles per problem between solve and scatter of the backward: R (9), t (3), sum_j q_j dR / d rho_j (9), q[3..5], coef, 1 unused
+constexpr int SOFT_REC = 26;      // doubles per problem between solve and scatter of the backward: R (9), t (3), sum_j q_j dR / d rho_j (9), q[3..5], coef, 1 unused
 constexpr int SOFT_FUSED_WAVES = 4;
 constexpr int SOFT_SCATTER_TILE = 32;  // records staged in LDS at a time (6.5 KB)
 // auto takes the fused form up to this many cells.  Measured (profiles/refine_soft_ab.txt, whole calls of 20 steps, split / fused in us): B = 64: 1 600 cells 237 / 136,
 // 4 800 cells 360 / 292, 12 288 cells 572 / 668; 16 x 256 on 1 600 cells 1 530 / 1 250; B = 1: 1 600 cells 141 / 70, 4 800 cells 227 / 249.  The crossover lies between
 // 4 800 and 12 288 cells with many problems and near 4 800 with one
 constexpr int SOFT_FUSED_MAX_CELLS = 4800;
-enum { SOFT_CONVERGED = 0, SOFT_MAXIT = 1, SOFT_SCORE = 2, SOFT_FEW = 3, SOFT_SINGULAR = 4, SOFT_NONFINITE = 5 };
 
 SoftGeom refine_soft_geom(int P) {
     // at most 256 chunks per problem (the step kernel adds them one after the other), at least 256 cells each, whole 64-lane trips
@@ -1657,11 +1650,8 @@ SoftGeom refine_soft_geom(int P) {
     return SoftGeom{chunk, (P + chunk - 1) / chunk};
 }
 bool refine_soft_auto_fused(int P) { return P <= SOFT_FUSED_MAX_CELLS; }
-// scratch: per-chunk sums | state | done | iters | records | record frames
-static size_t soft_off_state(int B, const SoftGeom& g) { return align256((size_t)B * g.nchunks * SOFT_NACC * 8); }
-static size_t soft_off_done(int B, const SoftGeom& g) { return soft_off_state(B, g) + align256((size_t)B * SOFT_STATE * 8); }
-static size_t soft_off_iters(int B, const SoftGeom& g) { return soft_off_done(B, g) + align256((size_t)B * 4); }
-static size_t soft_off_rec(int B, const SoftGeom& g) { return soft_off_iters(B, g) + align256((size_t)B * 4); }
+// scratch: the loop's (per-chunk sums | state | done | iters) | records | record frames
+static size_t soft_off_rec(int B, const SoftGeom& g) { return soft_loop_bytes(SOFT_NACC, B, g); }
 static size_t soft_off_recf(int B, const SoftGeom& g) { return soft_off_rec(B, g) + align256((size_t)B * SOFT_REC * 8); }
 size_t refine_soft_scratch_bytes(int B, const SoftGeom& g) { return soft_off_recf(B, g) + align256((size_t)B * 4); }
 
@@ -1765,60 +1755,40 @@ DM_INLINE void soft_pass_cells(const FrameDev& F, const dm::Cam& K, const double
     }
 }
 
-DM_INLINE int soft_problem_frame(FrameDev& F, const int32_t* frame_of, int per_frame, int b) {
+// the problem's frame (soft_loop.h) selected in F: maps, uv and the frame's own camera
+DM_INLINE int soft_select_frame(FrameDev& F, const int32_t* frame_of, int per_frame, int b) {
     if (F.frames <= 1) return 0;
-    const int f = uniform_frame(clamp_frame(frame_of ? frame_of[b] : (per_frame > 0 ? b / per_frame : 0), F));
+    const int f = soft_problem_frame(F.frames, frame_of, per_frame, b);
     select_frame(F, f);
     return f;
 }
 
-// One decision of the loop, after the pass at `trial` gave tot[]: -1 = go on (h, S, it updated, trial = the next pose to take a pass at), else the status
-// (h, S, it are the problem's output).  first: the pass at the start pose.  The same bits in every lane.
-DM_INLINE int soft_decide(bool first, const double* tot, double h[6], double trial[6], double& S, int& it, double min_soft, int max_iters, double step_tol) {
-    const double Sn = tot[27];
-    if (first) {
-        bool finite = true;
+// The 2D path's policy of the loop: 28 sums, a Gauss-Newton step h' = h - A^-1 g by the L D L^T solve, its length the norm of the solved delta.  The step
+// needs nothing of the problem but its sums.  Host side: what the pass launch takes
+struct Soft2D {
+    static constexpr int NACC = SOFT_NACC, S_AT = 27;
+    struct Src {};
+    static DM_INLINE Src load(const Src& s, int) { return s; }
+    static DM_INLINE bool step(const double* tot, const double h[6], const Src&, double next[6], double& len2) {
+        double A[36], d[6];
+        int q = 0;
 #pragma unroll
-        for (int i = 0; i < 6; i++) {
-            h[i] = trial[i];
-            finite = finite && (trial[i] - trial[i] == 0.0);
-        }
-        it = 0;
-        S = finite ? Sn : 0.0;
-        if (!finite) return SOFT_NONFINITE;
-        if (!(Sn >= min_soft)) return SOFT_FEW;
-    } else {
-        if (!(Sn >= S)) return SOFT_SCORE;
-        S = Sn;
-        it++;
+        for (int a = 0; a < 6; a++)
 #pragma unroll
-        for (int i = 0; i < 6; i++) h[i] = trial[i];
-        if (it >= max_iters) return SOFT_MAXIT;
+            for (int c = a; c < 6; c++) { A[a * 6 + c] = tot[q]; A[c * 6 + a] = tot[q]; q++; }
+        if (!solve6_spd(A, tot + 21, d)) return false;
+        len2 = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; i++) { len2 += d[i] * d[i]; next[i] = h[i] - d[i]; }
+        return true;
     }
-    double A[36], d[6];
-    int q = 0;
-#pragma unroll
-    for (int a = 0; a < 6; a++)
-#pragma unroll
-        for (int c = a; c < 6; c++) { A[a * 6 + c] = tot[q]; A[c * 6 + a] = tot[q]; q++; }
-    if (!solve6_spd(A, tot + 21, d)) return SOFT_SINGULAR;
-    double num = 0.0, den = 0.0;
-#pragma unroll
-    for (int i = 0; i < 6; i++) { num += d[i] * d[i]; den += h[i] * h[i]; }
-    if (sqrt(num) <= step_tol * (sqrt(den) + 2.220446049250313e-16)) return SOFT_CONVERGED;
-#pragma unroll
-    for (int i = 0; i < 6; i++) trial[i] = h[i] - d[i];
-    return -1;
-}
-
-DM_INLINE void soft_write_result(int b, int status, const double h[6], double S, int it, double* __restrict__ out_poses, double* __restrict__ soft_out,
-                                 int32_t* __restrict__ iters_out, int32_t* __restrict__ status_out) {
-#pragma unroll
-    for (int i = 0; i < 6; i++) out_poses[(size_t)b * 6 + i] = h[i];
-    if (soft_out) soft_out[b] = S;
-    if (iters_out) iters_out[b] = it;
-    if (status_out) status_out[b] = status;
-}
+    const int32_t* frame_of;
+    int per_frame;
+    double tau, beta, cut;
+    const FrameDev& F;
+    Src src;
+    void pass(hipStream_t st, unsigned grid, const SoftGeom& geom, int B, const double* poses, int pose_stride, const int32_t* done, double* part) const;
+};
 
 // split form, the pass: workgroup (one wave) = one chunk of one problem's cells at poses[b * pose_stride .. + 6]; its 28 sums go to part[b][chunk][28]
 template <bool BWD>
@@ -1829,7 +1799,7 @@ __global__ __launch_bounds__(64) void k_soft_pass(int B, const double* __restric
     if (b >= B) return;
     if (done && done[b]) return;  // a finished problem: one flag load
     const int lane = threadIdx.x & 63;
-    soft_problem_frame(F, frame_of, per_frame, b);
+    soft_select_frame(F, frame_of, per_frame, b);
     __shared__ double s_red[32];
     const dm::Cam K = make_cam_r(F);
     double pose[6], R[9], dRdr[27];
@@ -1847,50 +1817,8 @@ __global__ __launch_bounds__(64) void k_soft_pass(int B, const double* __restric
     if (lane < SOFT_NACC) part[((size_t)b * nchunks + ck) * SOFT_NACC + lane] = s_red[lane];
 }
 
-// the chunk sums of problem b added in index order: lane l < 28 adds value l; the totals in s_tot for every lane
-DM_INLINE void soft_ordered_sum(const double* __restrict__ part, int b, int nchunks, double* s_tot) {
-    const int lane = threadIdx.x & 63;
-    if (lane < SOFT_NACC) {
-        const double* p = part + (size_t)b * nchunks * SOFT_NACC + lane;
-        double v = 0.0;
-        for (int ck = 0; ck < nchunks; ck++) v += p[(size_t)ck * SOFT_NACC];
-        s_tot[lane] = v;
-    }
-    wave_sync_lds();
-}
-
-// split form, the step: one wave per problem
-__global__ __launch_bounds__(64) void k_soft_step(int B, int first, const double* __restrict__ init_poses, const double* __restrict__ part, int nchunks,
-                                                  double* __restrict__ state, int32_t* __restrict__ done, int32_t* __restrict__ iters, double min_soft, int max_iters,
-                                                  double step_tol, double* __restrict__ out_poses, double* __restrict__ soft_out, int32_t* __restrict__ iters_out,
-                                                  int32_t* __restrict__ status_out) {
-    const int b = blockIdx.x;
-    if (b >= B) return;
-    if (!first && done[b]) return;
-    const int lane = threadIdx.x & 63;
-    __shared__ double s_tot[32];
-    soft_ordered_sum(part, b, nchunks, s_tot);
-    double* st = state + (size_t)b * SOFT_STATE;
-    double h[6], trial[6], S = 0.0;
-    int it = 0;
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        trial[i] = first ? init_poses[(size_t)b * 6 + i] : st[6 + i];
-        h[i] = first ? trial[i] : st[i];
-    }
-    if (!first) { S = st[12]; it = iters[b]; }
-    const int status = soft_decide(first != 0, s_tot, h, trial, S, it, min_soft, max_iters, step_tol);
-    if (lane != 0) return;
-    if (status >= 0) {
-        soft_write_result(b, status, h, S, it, out_poses, soft_out, iters_out, status_out);
-        done[b] = 1;
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) { st[i] = h[i]; st[6 + i] = trial[i]; }
-    st[12] = S;
-    iters[b] = it;
-    if (first) done[b] = 0;
+void Soft2D::pass(hipStream_t st, unsigned grid, const SoftGeom& geom, int B, const double* poses, int pose_stride, const int32_t* done, double* part) const {
+    hipLaunchKernelGGL(k_soft_pass<false>, dim3(grid), dim3(64), 0, st, B, poses, pose_stride, done, frame_of, per_frame, geom.chunk, geom.nchunks, tau, beta, cut, 0, part, F);
 }
 
 // fused form: one workgroup per problem runs the whole loop; wave w takes the cells w * 64 + lane, + 256, ...; the waves' sums are added in wave order
@@ -1901,7 +1829,7 @@ __global__ __launch_bounds__(64 * SOFT_FUSED_WAVES) void k_soft_fused(int B, con
     const int b = blockIdx.x;
     if (b >= B) return;
     const int wave = threadIdx.x >> 6;
-    soft_problem_frame(F, frame_of, per_frame, b);
+    soft_select_frame(F, frame_of, per_frame, b);
     __shared__ double s_part[SOFT_FUSED_WAVES][32];
     __shared__ double s_tot[32];
     const dm::Cam K = make_cam_r(F);
@@ -1928,7 +1856,7 @@ __global__ __launch_bounds__(64 * SOFT_FUSED_WAVES) void k_soft_fused(int B, con
             s_tot[threadIdx.x] = v;
         }
         __syncthreads();
-        status = soft_decide(k == 0, s_tot, h, trial, S, it, min_soft, max_iters, step_tol);
+        status = soft_decide<Soft2D>(k == 0, s_tot, Soft2D::Src{}, h, trial, S, it, min_soft, max_iters, step_tol);
     }
     if (threadIdx.x == 0) soft_write_result(b, status, h, S, it, out_poses, soft_out, iters_out, status_out);
 }
@@ -1941,9 +1869,9 @@ __global__ __launch_bounds__(64) void k_soft_bwd_solve(int B, const double* __re
     const int b = blockIdx.x;
     if (b >= B) return;
     const int lane = threadIdx.x & 63;
-    const int f = soft_problem_frame(F, frame_of, per_frame, b);
+    const int f = soft_select_frame(F, frame_of, per_frame, b);
     __shared__ double s_tot[32];
-    soft_ordered_sum(part, b, nchunks, s_tot);
+    soft_ordered_sum<SOFT_NACC>(part, b, nchunks, s_tot);
     double pose[6];
     bool ok = true;
 #pragma unroll
@@ -2055,20 +1983,8 @@ hipError_t refine_soft(hipStream_t st, int B, const double* init_poses, const in
                            step_tol, out_poses, soft_out, iters_out, status_out, F);
         return hipGetLastError();
     }
-    char* s = static_cast<char*>(scratch);
-    double* part = reinterpret_cast<double*>(s);
-    double* state = reinterpret_cast<double*>(s + soft_off_state(B, geom));
-    int32_t* done = reinterpret_cast<int32_t*>(s + soft_off_done(B, geom));
-    int32_t* iters = reinterpret_cast<int32_t*>(s + soft_off_iters(B, geom));
-    const unsigned grid = (unsigned)B * (unsigned)geom.nchunks;
-    for (int k = 0; k <= max_iters; k++) {
-        // pass k is taken at the start pose (k = 0) or at the trial pose the step before it wrote; finished problems return after one flag load
-        hipLaunchKernelGGL(k_soft_pass<false>, dim3(grid), dim3(64), 0, st, B, k == 0 ? init_poses : state + 6, k == 0 ? 6 : SOFT_STATE,
-                           k == 0 ? (const int32_t*)nullptr : done, frame_of, per_frame, geom.chunk, geom.nchunks, tau, beta, cut, 0, part, F);
-        hipLaunchKernelGGL(k_soft_step, dim3((unsigned)B), dim3(64), 0, st, B, k == 0 ? 1 : 0, init_poses, part, geom.nchunks, state, done, iters, min_soft, max_iters,
-                           step_tol, out_poses, soft_out, iters_out, status_out);
-    }
-    return hipGetLastError();
+    return soft_loop(st, Soft2D{frame_of, per_frame, tau, beta, cut, F, {}}, B, init_poses, min_soft, max_iters, step_tol, geom, scratch, out_poses, soft_out, iters_out,
+                     status_out);
 }
 
 hipError_t refine_soft_backward(hipStream_t st, int B, const double* ref_poses, const int32_t* frame_of, int per_frame, double tau, double beta, double cut,

@@ -9,6 +9,7 @@
 // the same instructions -- one kernel, one evaluation site.  Fused multiply-adds that are wanted are spelled out.
 #include "kernels.h"
 #include "dmath.h"
+#include "soft_loop.h"
 
 namespace dk {
 
@@ -20,13 +21,6 @@ typedef unsigned u4v __attribute__((ext_vector_type(4)));
 
 DM_INLINE f2 splat2(float a) { return f2{a, a}; }
 DM_INLINE f2 pk_fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-DM_INLINE bool finite_d(double v) { return v - v == 0.0; }
-
-DM_INLINE void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // sum over the wave, the same bits in every lane (each stage adds the same two partial sums in both partners)
 DM_INLINE double wave_sum_d(double v) {
@@ -437,22 +431,19 @@ __global__ __launch_bounds__(256) void k_rgbd_mask_weights(long long cells, cons
 }
 
 // ---- refinement: Horn's alignment over the whole map, re-weighted by the score's sigmoid ---------------------------------------------------------
-// The loop of dsac_refine_soft (k_refine.hip) with another pass and another step: split form, a pass kernel on cell chunks x problems whose 16 sums go to
-// scratch and a one-wave step kernel that adds them in chunk order, decides and moves the pose; max_iters + 1 of each, no host round trip, no
+// The loop of dsac_refine_soft (soft_loop.h) with another pass and another step: split form, a pass kernel on cell chunks x problems whose 16 sums go to
+// scratch and the one-wave step kernel that adds them in chunk order, decides and moves the pose; max_iters + 1 of each, no host round trip, no
 // floating-point atomics.  The sums are taken about the frame's first VALID cell (X0, C0): x = X - X0, c = C - C0.
-constexpr int RG_NACC = 16;   // S, sum w x (3), sum w c (3), sum w x c^T (9, row = x)
-constexpr int RG_STATE = 16;  // doubles per problem between the launches: pose (6), trial pose (6), S, 3 unused
-enum { RG_CONVERGED = 0, RG_MAXIT = 1, RG_SCORE = 2, RG_FEW = 3, RG_SINGULAR = 4, RG_NONFINITE = 5 };  // enum dsac_soft_status
+constexpr int RG_NACC = 16;  // S, sum w x (3), sum w c (3), sum w x c^T (9, row = x)
 
-size_t rg_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-size_t rg_off_state(int B, const SoftGeom& g) { return rg_align256((size_t)B * g.nchunks * RG_NACC * 8); }
-size_t rg_off_done(int B, const SoftGeom& g) { return rg_off_state(B, g) + rg_align256((size_t)B * RG_STATE * 8); }
-size_t rg_off_iters(int B, const SoftGeom& g) { return rg_off_done(B, g) + rg_align256((size_t)B * 4); }
-
-DM_INLINE int rg_problem_frame(int frames, const int32_t* frame_of, int per_frame, int b) {
-    if (frames <= 1) return 0;
-    const int f = frame_of ? frame_of[b] : (per_frame > 0 ? b / per_frame : 0);
-    return __builtin_amdgcn_readfirstlane(min(max(f, 0), frames - 1));
+// (X0, C0) of a frame whose first VALID cell is `first` (xyz, cam: the frame's); zeros where the frame has none
+DM_INLINE void rg_origin(const float* __restrict__ xyz, const float* __restrict__ cam, int first, int P, double X0[3], double C0[3]) {
+#pragma unroll
+    for (int j = 0; j < 3; j++) X0[j] = C0[j] = 0.0;
+    if (first < P) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) { X0[j] = (double)xyz[(size_t)first * 3 + j]; C0[j] = (double)cam[(size_t)first * 3 + j]; }
+    }
 }
 
 __global__ __launch_bounds__(64) void k_rgbd_pass(int B, const double* __restrict__ poses, int pose_stride, const int32_t* __restrict__ done,
@@ -463,7 +454,7 @@ __global__ __launch_bounds__(64) void k_rgbd_pass(int B, const double* __restric
     if (b >= B) return;
     if (done && done[b]) return;  // a finished problem: one flag load
     const int lane = threadIdx.x & 63;
-    const int f = rg_problem_frame(frames, frame_of, per_frame, b);
+    const int f = soft_problem_frame(frames, frame_of, per_frame, b);
     xyz += (long long)f * xyz_stride;
     cam += (size_t)f * (size_t)P * 3;
     double pose[6], R[9];
@@ -471,12 +462,8 @@ __global__ __launch_bounds__(64) void k_rgbd_pass(int B, const double* __restric
     for (int i = 0; i < 6; i++) pose[i] = poses[(size_t)b * pose_stride + i];
     dm::RodAux aux;
     dm::rodrigues_R(pose, R, aux);
-    const int first = meta[2 * f + 1];
-    double X0[3] = {0.0, 0.0, 0.0}, C0[3] = {0.0, 0.0, 0.0};
-    if (first < P) {
-#pragma unroll
-        for (int j = 0; j < 3; j++) { X0[j] = (double)xyz[(size_t)first * 3 + j]; C0[j] = (double)cam[(size_t)first * 3 + j]; }
-    }
+    double X0[3], C0[3];
+    rg_origin(xyz, cam, meta[2 * f + 1], P, X0, C0);
     double acc[RG_NACC];
 #pragma unroll
     for (int i = 0; i < RG_NACC; i++) acc[i] = 0.0;
@@ -513,29 +500,37 @@ __global__ __launch_bounds__(64) void k_rgbd_pass(int B, const double* __restric
     }
 }
 
-// One decision of the loop after the pass at `trial` gave tot[]: -1 = go on (h, S, it updated, trial = the next pose to take a pass at), else the status.
-DM_INLINE int rg_decide(bool first, const double* tot, const double X0[3], const double C0[3], double h[6], double trial[6], double& S, int& it, double min_soft,
-                        int max_iters, double step_tol) {
-    const double Sn = tot[0];
-    if (first) {
-        bool finite = true;
-#pragma unroll
-        for (int i = 0; i < 6; i++) {
-            h[i] = trial[i];
-            finite = finite && finite_d(trial[i]);
-        }
-        it = 0;
-        S = finite ? Sn : 0.0;
-        if (!finite) return RG_NONFINITE;
-        if (!(Sn >= min_soft)) return RG_FEW;
-    } else {
-        if (!(Sn >= S)) return RG_SCORE;
-        S = Sn;
-        it++;
-#pragma unroll
-        for (int i = 0; i < 6; i++) h[i] = trial[i];
-        if (it >= max_iters) return RG_MAXIT;
+// The RGB-D path's policy of the loop: 16 sums, Horn's closed form about (X0, C0) -- which the step loads as the pass does --, the length of a move the
+// norm of h' - h.  Host side: what the pass launch takes
+struct SoftRgbd {
+    static constexpr int NACC = RG_NACC, S_AT = 0;
+    struct Src {
+        const int32_t* frame_of;
+        int per_frame, frames;
+        const float* xyz;
+        long long xyz_stride;
+        const float* cam;
+        const int32_t* meta;
+        int P;
+    };
+    struct RgOrigin { double X0[3], C0[3]; };
+    static DM_INLINE RgOrigin load(const Src& s, int b) {
+        const int f = soft_problem_frame(s.frames, s.frame_of, s.per_frame, b);
+        RgOrigin o;
+        rg_origin(s.xyz + (long long)f * s.xyz_stride, s.cam + (size_t)f * (size_t)s.P * 3, s.meta[2 * f + 1], s.P, o.X0, o.C0);
+        return o;
     }
+    static DM_INLINE bool step(const double* tot, const double h[6], const RgOrigin& o, double hn[6], double& len2);
+    double tau, beta, cut;
+    Src src;
+    void pass(hipStream_t st, unsigned grid, const SoftGeom& geom, int B, const double* poses, int pose_stride, const int32_t* done, double* part) const {
+        hipLaunchKernelGGL(k_rgbd_pass, dim3(grid), dim3(64), 0, st, B, poses, pose_stride, done, src.frame_of, src.per_frame, src.frames, geom.chunk, geom.nchunks, tau,
+                           beta, cut, src.xyz, src.xyz_stride, src.cam, src.meta, src.P, part);
+    }
+};
+
+DM_INLINE bool SoftRgbd::step(const double* tot, const double h[6], const RgOrigin& o, double hn[6], double& len2) {
+    const double Sn = tot[0];
     // the step: weighted means, cross-covariance K (row = scene axis, column = camera axis), Horn's 4 x 4 matrix as dm::align3_horn builds it
     const double inv = 1.0 / Sn;
     double xm[3], cm[3], s[9];
@@ -571,82 +566,24 @@ DM_INLINE int rg_decide(bool first, const double* tot, const double X0[3], const
     q0 *= qn; q1 *= qn; q2 *= qn; q3 *= qn;
     const double q02 = q0 * q0, q12 = q1 * q1, q22 = q2 * q2, q32 = q3 * q3;
     const double q0_1 = q0 * q1, q0_2 = q0 * q2, q0_3 = q0 * q3, q1_2 = q1 * q2, q1_3 = q1 * q3, q2_3 = q2 * q3;
-    double Rn[9], hn[6];
+    double Rn[9];
     Rn[0] = q02 + q12 - q22 - q32; Rn[1] = 2. * (q1_2 - q0_3); Rn[2] = 2. * (q1_3 + q0_2);
     Rn[3] = 2. * (q1_2 + q0_3); Rn[4] = q02 + q22 - q12 - q32; Rn[5] = 2. * (q2_3 - q0_1);
     Rn[6] = 2. * (q1_3 - q0_2); Rn[7] = 2. * (q2_3 + q0_1); Rn[8] = q02 + q32 - q12 - q22;
     dm::rodrigues_m2v(Rn, hn);
-    const double Xb[3] = {X0[0] + xm[0], X0[1] + xm[1], X0[2] + xm[2]};
+    const double Xb[3] = {o.X0[0] + xm[0], o.X0[1] + xm[1], o.X0[2] + xm[2]};
 #pragma unroll
-    for (int i = 0; i < 3; i++) hn[3 + i] = (C0[i] + cm[i]) - (Rn[i * 3] * Xb[0] + Rn[i * 3 + 1] * Xb[1] + Rn[i * 3 + 2] * Xb[2]);
+    for (int i = 0; i < 3; i++) hn[3 + i] = (o.C0[i] + cm[i]) - (Rn[i * 3] * Xb[0] + Rn[i * 3 + 1] * Xb[1] + Rn[i * 3 + 2] * Xb[2]);
     bool fin = true;
 #pragma unroll
     for (int i = 0; i < 9; i++) fin = fin && finite_d(Rn[i]);
 #pragma unroll
     for (int i = 0; i < 6; i++) fin = fin && finite_d(hn[i]);
-    if (!fin || !(l1 - l2 > 1e-9 * l1)) return RG_SINGULAR;
-    double num = 0.0, den = 0.0;
+    if (!fin || !(l1 - l2 > 1e-9 * l1)) return false;
+    len2 = 0.0;
 #pragma unroll
-    for (int i = 0; i < 6; i++) { const double d = hn[i] - h[i]; num += d * d; den += h[i] * h[i]; }
-    if (sqrt(num) <= step_tol * (sqrt(den) + 2.220446049250313e-16)) return RG_CONVERGED;
-#pragma unroll
-    for (int i = 0; i < 6; i++) trial[i] = hn[i];
-    return -1;
-}
-
-// split form, the step: one wave per problem; lane l < 16 adds sum l over the chunks in index order
-__global__ __launch_bounds__(64) void k_rgbd_step(int B, int first, const double* __restrict__ init_poses, const double* __restrict__ part, int nchunks,
-                                                  const int32_t* __restrict__ frame_of, int per_frame, int frames, const float* __restrict__ xyz, long long xyz_stride,
-                                                  const float* __restrict__ cam, const int32_t* __restrict__ meta, int P, double* __restrict__ state,
-                                                  int32_t* __restrict__ done, int32_t* __restrict__ iters, double min_soft, int max_iters, double step_tol,
-                                                  double* __restrict__ out_poses, double* __restrict__ soft_out, int32_t* __restrict__ iters_out,
-                                                  int32_t* __restrict__ status_out) {
-    const int b = blockIdx.x;
-    if (b >= B) return;
-    if (!first && done[b]) return;
-    const int lane = threadIdx.x & 63;
-    __shared__ double s_tot[RG_NACC];
-    if (lane < RG_NACC) {
-        const double* p = part + (size_t)b * nchunks * RG_NACC + lane;
-        double v = 0.0;
-        for (int ck = 0; ck < nchunks; ck++) v += p[(size_t)ck * RG_NACC];
-        s_tot[lane] = v;
-    }
-    wave_lds_sync();
-    const int f = rg_problem_frame(frames, frame_of, per_frame, b);
-    xyz += (long long)f * xyz_stride;
-    cam += (size_t)f * (size_t)P * 3;
-    const int fc = meta[2 * f + 1];
-    double X0[3] = {0.0, 0.0, 0.0}, C0[3] = {0.0, 0.0, 0.0};
-    if (fc < P) {
-#pragma unroll
-        for (int j = 0; j < 3; j++) { X0[j] = (double)xyz[(size_t)fc * 3 + j]; C0[j] = (double)cam[(size_t)fc * 3 + j]; }
-    }
-    double* st = state + (size_t)b * RG_STATE;
-    double h[6], trial[6], S = 0.0;
-    int it = 0;
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        trial[i] = first ? init_poses[(size_t)b * 6 + i] : st[6 + i];
-        h[i] = first ? trial[i] : st[i];
-    }
-    if (!first) { S = st[12]; it = iters[b]; }
-    const int status = rg_decide(first != 0, s_tot, X0, C0, h, trial, S, it, min_soft, max_iters, step_tol);
-    if (lane != 0) return;
-    if (status >= 0) {
-#pragma unroll
-        for (int i = 0; i < 6; i++) out_poses[(size_t)b * 6 + i] = h[i];
-        if (soft_out) soft_out[b] = S;
-        if (iters_out) iters_out[b] = it;
-        if (status_out) status_out[b] = status;
-        done[b] = 1;
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) { st[i] = h[i]; st[6 + i] = trial[i]; }
-    st[12] = S;
-    iters[b] = it;
-    if (first) done[b] = 0;
+    for (int i = 0; i < 6; i++) { const double d = hn[i] - h[i]; len2 += d * d; }
+    return true;
 }
 
 }  // namespace
@@ -661,7 +598,7 @@ hipError_t rgbd_set_points(hipStream_t st, const float* src, const FrameDev& F, 
 }
 
 hipError_t rgbd_sample(hipStream_t st, int N, uint64_t seed, const int32_t* sets_in, const FrameDev& F, const float* cam, const int32_t* meta, double thr,
-                       int max_tries, double* poses, int32_t* sets_out, uint8_t* ok, int Nf, const RgbdGuide* guide) {
+                       int max_tries, double* poses, int32_t* sets_out, uint8_t* ok, int Nf, const GuideView* guide) {
     if (N <= 0) return hipSuccess;
     const unsigned grid = sets_in ? (unsigned)((N + 63) / 64) : (unsigned)N;
     if (guide && !sets_in) {  // given sets are evaluated by the uniform build: the weights do not touch them
@@ -711,28 +648,14 @@ hipError_t rgbd_score(hipStream_t st, int N, const double* poses, float* rec, co
     return reduce_soft(st, N, PT, soft_part, soft);
 }
 
-size_t rgbd_refine_scratch_bytes(int B, const SoftGeom& g) { return rg_off_iters(B, g) + rg_align256((size_t)B * 4); }
+size_t rgbd_refine_scratch_bytes(int B, const SoftGeom& g) { return soft_loop_bytes(RG_NACC, B, g); }
 
 hipError_t rgbd_refine(hipStream_t st, int B, const double* init_poses, const int32_t* frame_of, int per_frame, double tau, double beta, double cut, double min_soft,
                        int max_iters, double step_tol, const SoftGeom& geom, void* scratch, double* out_poses, double* soft_out, int32_t* iters_out,
                        int32_t* status_out, const FrameDev& F, const float* cam, const int32_t* meta) {
     if (B < 1 || F.P < 1 || max_iters < 1 || (long long)B * geom.nchunks > 0x7fffffffll) return hipErrorInvalidValue;
-    const int frames = F.frames > 1 ? F.frames : 1;
-    char* s = static_cast<char*>(scratch);
-    double* part = reinterpret_cast<double*>(s);
-    double* state = reinterpret_cast<double*>(s + rg_off_state(B, geom));
-    int32_t* done = reinterpret_cast<int32_t*>(s + rg_off_done(B, geom));
-    int32_t* iters = reinterpret_cast<int32_t*>(s + rg_off_iters(B, geom));
-    const unsigned grid = (unsigned)B * (unsigned)geom.nchunks;
-    for (int k = 0; k <= max_iters; k++) {
-        // pass k is taken at the start pose (k = 0) or at the trial pose the step before it wrote; finished problems return after one flag load
-        hipLaunchKernelGGL(k_rgbd_pass, dim3(grid), dim3(64), 0, st, B, k == 0 ? init_poses : state + 6, k == 0 ? 6 : RG_STATE,
-                           k == 0 ? (const int32_t*)nullptr : done, frame_of, per_frame, frames, geom.chunk, geom.nchunks, tau, beta, cut, F.xyz, F.xyz_stride, cam, meta,
-                           F.P, part);
-        hipLaunchKernelGGL(k_rgbd_step, dim3((unsigned)B), dim3(64), 0, st, B, k == 0 ? 1 : 0, init_poses, part, geom.nchunks, frame_of, per_frame, frames, F.xyz,
-                           F.xyz_stride, cam, meta, F.P, state, done, iters, min_soft, max_iters, step_tol, out_poses, soft_out, iters_out, status_out);
-    }
-    return hipGetLastError();
+    const SoftRgbd pol{tau, beta, cut, {frame_of, per_frame, F.frames > 1 ? F.frames : 1, F.xyz, F.xyz_stride, cam, meta, F.P}};
+    return soft_loop(st, pol, B, init_poses, min_soft, max_iters, step_tol, geom, scratch, out_poses, soft_out, iters_out, status_out);
 }
 
 }  // namespace dk

@@ -805,19 +805,19 @@ hipError_t guide_backward(hipStream_t st, int frames, int P, int Nf, const float
 }
 
 hipError_t sample(hipStream_t st, int N, uint64_t seed, const int32_t* sets_in, const FrameDev& F, int thr_int, int max_tries, double* poses,
-                  int32_t* sets_out, uint8_t* ok, float* staged, int Nf, const K1Opts& o) {
+                  int32_t* sets_out, uint8_t* ok, float* staged, int Nf, const K1Opts& o, const GuideView* guide) {
     if (N <= 0) return hipSuccess;
     if (sets_in && Nf > 0 && F.frames > 1) return hipErrorInvalidValue;  // given sets are evaluated on one frame only
     if (sets_in) {
         if (o.horn) hipLaunchKernelGGL(k_eval_sets<true>, dim3((N + 63) / 64), dim3(64), 0, st, N, sets_in, F, thr_int, poses, sets_out, ok, staged);
         else hipLaunchKernelGGL(k_eval_sets<false>, dim3((N + 63) / 64), dim3(64), 0, st, N, sets_in, F, thr_int, poses, sets_out, ok, staged);
-    } else if (o.guide_cdf) {
+    } else if (guide) {
         // guided: the one-lane-per-attempt, one-hypothesis-per-wave build serves every N, frame batches and camera tables; "k1_horn" has no guided build
         // (the API refuses it by name).  At a register budget for two waves per SIMD (MINW = 2): 256 registers and no scratch, where the budget for one
         // lets the allocator take 258 and halves the occupancy of the uniform build it stands in for (252)
-        if (o.horn || !o.guide_meta || !o.guide_coarse) return hipErrorInvalidValue;
+        if (o.horn || !guide->cdf || !guide->meta || !guide->coarse) return hipErrorInvalidValue;
         hipLaunchKernelGGL((k_sample<1, 1, false, 2, 1, DrawGuided, const uint64_t*, const GuideMeta*, const uint64_t*, int>), dim3(N), dim3(64), 0, st, N, seed, F, thr_int, max_tries, poses, sets_out, ok, staged, o.prio,
-                           Nf > 0 ? Nf : N, o.guide_cdf, o.guide_meta, o.guide_coarse, guide_coarse_shift(F.P));
+                           Nf > 0 ? Nf : N, guide->cdf, guide->meta, guide->coarse, guide_coarse_shift(F.P));
     } else {
         const int wpb = o.wpb, prio = o.prio;
         int H2 = o.hpw > 0 ? o.hpw : 1;  // see the measurement in the kernel's comment

@@ -120,6 +120,9 @@ struct GuideMeta {
     uint32_t wmax;   // bits of the largest valid weight (positive floats order like their bits), 0 = no valid cell
     int32_t n;       // cells with mass > 0
 };
+// what a guided draw reads of a built table (2D or RGB-D; the context owns the buffers): frames x P inclusive sums of the quantised masses, the per-frame
+// records, and the coarse level, frames x guide_coarse_entries(P)
+struct GuideView { const uint64_t* cdf; const GuideMeta* meta; const uint64_t* coarse; };
 // the coarse level of a frame's table: the last entry of every block of 2^shift cells, the smallest shift >= 8 that leaves at most GUIDE_COARSE_MAX blocks
 // (K1 keeps them in LDS: 16 KB; 640x480 is 1 200 blocks of 256)
 constexpr int GUIDE_COARSE_MAX = 2048;
@@ -148,15 +151,12 @@ struct K1Opts {
     bool horn = false;
     int wide = -1;  // waves per hypothesis of the one-lane-per-attempt form for few hypotheses: -1 auto (2 up to 512 hypotheses), 0 off, 2, 4 (4: up to 256) (DSAC_K1_WIDE)
     int rl = 1;  // lanes per attempt: 4 = one per quartic root, 1 = one lane per attempt with its roots in sequence (DSAC_K1_RL)
-    // guided sampling (dsac_set_sampling_weights): the context's table while weights are active, else nullptr.  sample() then launches the guided build
-    // (one lane per attempt, one hypothesis per wave) whatever the form knobs above say -- they never change a result -- and given sets ignore it
-    const uint64_t* guide_cdf = nullptr;   // frames x P inclusive sums of the quantised masses
-    const GuideMeta* guide_meta = nullptr; // frames
-    const uint64_t* guide_coarse = nullptr; // frames x guide_coarse_entries(P): the table's coarse level
 };
+// guide: the context's table while sampling weights are active (dsac_set_sampling_weights), else nullptr.  sample() then launches the guided build (one lane
+// per attempt, one hypothesis per wave) whatever the form knobs say -- they never change a result -- and given sets ignore it
 hipError_t sample(hipStream_t st, int N, uint64_t seed, const int32_t* sets_in, const FrameDev& F, int thr_int, int max_tries,
                   double* poses, int32_t* sets_out, uint8_t* ok, float* staged_or_null = nullptr, int Nf = 0,
-                  const K1Opts& opts = K1Opts());  // staged: K2 records (N x 12)
+                  const K1Opts& opts = K1Opts(), const GuideView* guide = nullptr);  // staged: K2 records (N x 12)
 // K1 in the reference's own random stream (round 6; core/thread_rand.cpp:40-69, core/cnn_softam.h:1010-1060; refstream.h): T generators std::mt19937(seed + t)
 // on the device; a window = A attempts per stream parsed, evaluated and handed to the stream's next hypotheses in order.
 struct RefStreamState { uint32_t mt[624]; uint32_t idx; uint32_t pad[3]; };
@@ -329,16 +329,15 @@ hipError_t gather_patches(hipStream_t st, const uint8_t* bgr, int H, int W, cons
 hipError_t rgbd_set_points(hipStream_t st, const float* src, const FrameDev& F, float* cam_copy, int32_t* meta);
 // sets N x 3.  sets_in: evaluated once each (one frame); else drawn from K1's counter stream, Nf > 0: hypothesis h belongs to frame h / Nf
 // guide: the table of dsac_set_sampling_weights_rgbd while those weights are active (drawn sets then come from it: the guided build), else nullptr
-struct RgbdGuide { const uint64_t* cdf; const GuideMeta* meta; const uint64_t* coarse; };
 hipError_t rgbd_sample(hipStream_t st, int N, uint64_t seed, const int32_t* sets_in, const FrameDev& F, const float* cam, const int32_t* meta, double thr,
-                       int max_tries, double* poses, int32_t* sets_out, uint8_t* ok, int Nf = 0, const RgbdGuide* guide = nullptr);
+                       int max_tries, double* poses, int32_t* sets_out, uint8_t* ok, int Nf = 0, const GuideView* guide = nullptr);
 // the masked weights of guided RGB-D sampling, one launch: out[f * P + p] = w[f * P + p] where the cell is VALID in the canonical copy, 0 elsewhere
 hipError_t rgbd_mask_weights(hipStream_t st, int frames, int P, const float* w, const float* cam, float* out);
 // rec: N x POSE_STRIDE floats (written here); err (N x P) and / or soft (N doubles; soft_part then holds rgbd_score_tiles(P) x N floats), either may be nullptr
 int rgbd_score_tiles(int P);
 hipError_t rgbd_score(hipStream_t st, int N, const double* poses, float* rec, const FrameDev& F, const float* cam, float clampv, float* err, float tau, float beta,
                       float* soft_part, double* soft, int Nf = 0);
-// the split loop of refine_soft with the RGB-D pass and step (chunks: refine_soft_geom)
+// the split loop of refine_soft (soft_loop.h) with the RGB-D pass and step (chunks: refine_soft_geom)
 size_t rgbd_refine_scratch_bytes(int B, const SoftGeom& g);
 hipError_t rgbd_refine(hipStream_t st, int B, const double* init_poses, const int32_t* frame_of, int per_frame, double tau, double beta, double cut, double min_soft,
                        int max_iters, double step_tol, const SoftGeom& geom, void* scratch, double* out_poses, double* soft_out, int32_t* iters_out,
