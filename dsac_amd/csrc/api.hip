@@ -303,42 +303,61 @@ struct ProfScope {
         if (rc__ != DSAC_OK) return rc__; \
     } while (0)
 
-// The K2 stage: the one place a K2 launch is assembled.  Everything the launch is handed follows from one decision taken here -- from the context's options,
-// the cv poses (NULL only in dsac_score_sampled: nothing to split, the fp32 form on K1's records) and F, the frame the launch READS (the slot's own frame in
-// dsac_score_sampled, the current one everywhere else): the records fold its fx, fy and split exponent.  Records that are wanted are built on `st` right in
-// front of the launch and handed to it; records that are not wanted are neither.
+// The K2 stage: the one place a K2 launch is assembled, and it plans first.  dk::k2_plan (k2_plan.h) decides from the context's options, the cv poses (NULL
+// only in dsac_score_sampled: nothing to split, the fp32 form on K1's records) and F, the frame the launch READS (the slot's own frame in dsac_score_sampled, the
+// current one everywhere else): which form and kernel, which records, how many partial-sum rows -- or that the launch is refused.  A refusal returns here, before
+// the gate's wait, any record kernel and any profiling pair: a refused call enqueues nothing and "k2_form_last" keeps its value.  Otherwise exactly the records
+// the plan names are built on `st` right in front of the launch (they fold F's fx, fy and split exponent), dk::reproject launches the plan, and the plan's form
+// and row count are what the context and the caller are told.
 //   err, elem: the error images and their element type -- dk::K2_ELEM_F32 (float), dk::K2_ELEM_F16 (IEEE binary16: dsac_reproject_f16 /
 //   dsac_process_images_begin_f16) or dk::K2_ELEM_BF16 (bfloat16: the _bf16 twins); the 16-bit calls have checked k2_f16_check before anything was enqueued;
 //   only the auto policy's exact vector build stores 16-bit elements)
+//   part, want_soft: the buffer of the per-tile sums and whether the caller wants them; an error-images-only call hands the buffer over all the same where
+//   the plan fuses the sums (k2_soft_part asks the same dk::k2_fuse_sums)
 //   gated: the launch sits between the context's k2_wait / k2_record events (dsac_set_k2_events)
 //   fallback_stop: the stop event of the launch when profiling attaches no pair to it (the deferred score tails start behind it); *done receives the event
 //   that completes with K2 -- the pair's stop event, else fallback_stop
-// A launch that reproject() refuses (unknown variant, hipErrorNotSupported) records no k2_record, and its event pair goes back to the free list.
+// A launch that fails all the same records no k2_record, and its event pair goes back to the free list.
 int k2_stage(dsac_ctx* c, hipStream_t st, int N, int Nf, const float* staged, const dk::FrameDev& F, const double* poses, float clampv, float tau, float beta,
-             void* err, int elem, float* part, bool gated, hipEvent_t fallback_stop, int* tiles_used, hipEvent_t* done = nullptr) {
+             void* err, int elem, float* part, bool want_soft, bool gated, hipEvent_t fallback_stop, int* tiles_used, hipEvent_t* done = nullptr) {
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    dk::K2PlanIn in;
+    in.o = c->k2;
+    in.N = N; in.Nf = Nf; in.frames = F.frames;
+    in.P = F.P; in.W = F.W; in.uv = F.uv != nullptr;
+    in.xyz_al16 = al16(F.xyz); in.uv_al16 = al16(F.uv); in.err_al16 = al16(err);
+    in.focal_ok = dk::pose_split_available(F);
+    in.poses = poses != nullptr;
+    in.want_err = err != nullptr; in.want_soft = want_soft;
+    in.err_elem = elem;
+    const dk::K2Plan plan = dk::k2_plan(in);
+    *tiles_used = plan.tiles;
+    if (plan.status != dk::K2_STATUS_OK) return fail(c, DSAC_ERR_HIP, "dk::k2_plan(in) failed: %s", hipGetErrorString((hipError_t)plan.status));
+    if (plan.form == dk::K2_FORM_NONE) return DSAC_OK;  // an empty call
+    const bool sums = want_soft || plan.fuse_sums;
+    if (sums && !part) return fail(c, DSAC_ERR_INVALID, "k2_stage: the plan writes partial sums and no buffer was given");
     if (gated && c->k2_wait) HIP_TRY(c, hipStreamWaitEvent(st, c->k2_wait, 0));
-    const bool split = poses && dk::k2_wants_exact(c->k2) && dk::pose_split_available(F);  // the exact-transform form (the default; "k2_flags" bit 28)
-    const bool lo = poses && (c->k2.flags & dk::K2_FLAG_RECLO);                            // "k2_flags" bit 27: the low parts of the staged records
-    if (split) {
+    dk::K2Call call;
+    if (plan.need_split) {  // the exact-transform form (the default; "k2_flags" bit 28 / 29)
         HIP_TRY(c, c->staged_split.reserve(dk::pose_split_bytes(N)));
         HIP_TRY(c, dk::pose_prep_split(st, N, poses, F, c->staged_split.as<char>(), Nf));
+        call.split = c->staged_split.as<char>();
     }
-    if (lo) {
+    if (plan.need_lo) {  // "k2_flags" bit 27: the low parts of the staged records
         HIP_TRY(c, c->staged_lo.reserve((size_t)N * dk::POSE_STRIDE * sizeof(float)));
         HIP_TRY(c, dk::pose_prep_lo(st, N, poses, F, c->staged_lo.as<float>(), Nf));
+        call.staged_lo = c->staged_lo.as<float>();
     }
     ProfScope ps(c, 0, true);
-    dk::K2Opts o = c->k2;
-    o.split = split ? c->staged_split.as<char>() : nullptr;
-    o.staged_lo = lo ? c->staged_lo.as<float>() : nullptr;
-    o.poses64 = poses;  // what the precise form ("k2_flags" bit 25) projects with
-    o.report = c->k2_last;
-    o.err_elem = elem;
-    if (ps.on) { o.ev_start = ps.p.a; o.ev_stop = ps.p.b; }
-    else o.ev_stop = fallback_stop;
-    if (done) *done = o.ev_stop;
-    HIP_TRY(c, dk::reproject(st, N, staged, F, clampv, static_cast<float*>(err), tau, beta, part, o, tiles_used, Nf));
+    call.poses64 = poses;  // what the precise form ("k2_flags" bit 25) projects with
+    call.diag = c->k2.diag;
+    if (ps.on) { call.ev_start = ps.p.a; call.ev_stop = ps.p.b; }
+    else call.ev_stop = fallback_stop;
+    if (done) *done = call.ev_stop;
+    HIP_TRY(c, dk::reproject(st, plan, N, staged, F, clampv, static_cast<float*>(err), tau, beta, sums ? part : nullptr, call));
     ps.commit();
+    c->k2_last[0] = plan.form;
+    c->k2_last[1] = plan.why;
     if (gated && c->k2_record) HIP_TRY(c, hipEventRecord(c->k2_record, st));
     return DSAC_OK;
 }
@@ -419,14 +438,11 @@ int loss_common(dsac_ctx* c, size_t B, size_t gt_count, int gt_stride, int gt_gr
     return end_call(c);
 }
 
-// Error images only on a big launch: the streaming form WITH the sigmoid arithmetic is the faster kernel -- the arithmetic spaces a wave's stores
-// (N = 4096: 860 us against 890-900 for any form without it; idling the wave instead, k2_flags bits 16-23, does not reproduce the effect:
-// profiles/r04_k2_err_ab.txt).  So the auto policy runs that kernel and drops its partial sums (1200 x N floats of scratch, 0.4 % of the
-// stores; no reduction launch).  k2_flags bit 24 switches the policy off (A/B).
-// *part: the context's buffer for the per-tile sums when the caller wants them (want_soft) or the policy applies, else NULL; tau / beta: any finite
-// sigmoid when the policy applies and the caller gave none (the sums are not used).
+// The buffer of K2's per-tile sums for a call that may want error images only: the context's, when the caller wants the sums (want_soft) or the plan will fuse
+// them in all the same (dk::k2_fuse_sums, the helper dk::k2_plan asks: the faster kernel on a big launch, its sums are dropped), else NULL.
+// tau / beta: any finite sigmoid when the sums are fused and the caller gave none (they are not used).
 int k2_soft_part(dsac_ctx* c, int N, bool want_err, bool want_soft, float* tau, float* beta, float** part) {
-    const bool fused_for_err = !want_soft && want_err && c->k2.variant < 0 && !(c->k2.flags & (1 << 24)) && (double)N * (double)c->F.P * 4.0 > 1.0e9;
+    const bool fused_for_err = dk::k2_fuse_sums(c->k2, N, c->F.P, want_err, want_soft);
     *part = nullptr;
     if (want_soft || fused_for_err) {
         HIP_TRY(c, c->soft_part.reserve((size_t)dk::reproject_num_pixel_tiles(c->F.P) * N * sizeof(float)));
@@ -460,12 +476,14 @@ int k2_cams_check(dsac_ctx* c, const char* who) {
         if (std::max(F.cams_h[4 * f], F.cams_h[4 * f + 1]) > 1024.f)
             return fail(c, DSAC_ERR_INVALID, "%s: per-frame cameras need every focal length <= 1024 px (the exact-transform form), frame %d has fx = %g, fy = %g", who, f,
                         (double)F.cams_h[4 * f], (double)F.cams_h[4 * f + 1]);
-    if (c->k2.variant != -1) return fail(c, DSAC_ERR_INVALID, "%s: per-frame cameras need k2_variant -1 (the auto policy's exact-transform form), it is %d", who, c->k2.variant);
-    const int ex_bits = dk::K2_FLAG_EXACT | dk::K2_FLAG_EXACT_ANY;
-    if (c->k2.flags & ~ex_bits)
-        return fail(c, DSAC_ERR_INVALID, "%s: per-frame cameras exist for the exact-transform form only: k2_flags 0x%x sets bits other than 28 / 29", who, c->k2.flags);
-    if (!c->k2.exact_auto && !(c->k2.flags & ex_bits))
-        return fail(c, DSAC_ERR_INVALID, "%s: per-frame cameras need the exact-transform form: k2_exact_auto is 0 and neither k2_flags bit 28 nor 29 is set", who);
+    switch (dk::k2_exact_only(c->k2.variant, c->k2.flags, c->k2.exact_auto)) {
+        case dk::K2_EXONLY_VARIANT:
+            return fail(c, DSAC_ERR_INVALID, "%s: per-frame cameras need k2_variant -1 (the auto policy's exact-transform form), it is %d", who, c->k2.variant);
+        case dk::K2_EXONLY_FLAGS:
+            return fail(c, DSAC_ERR_INVALID, "%s: per-frame cameras exist for the exact-transform form only: k2_flags 0x%x sets bits other than 28 / 29", who, c->k2.flags);
+        case dk::K2_EXONLY_AUTO_OFF:
+            return fail(c, DSAC_ERR_INVALID, "%s: per-frame cameras need the exact-transform form: k2_exact_auto is 0 and neither k2_flags bit 28 nor 29 is set", who);
+    }
     return DSAC_OK;
 }
 // The backward calls use one focal length for both axes (dProjectdObj / dProjectdHyp, core/cnn_softam.h:406,466): with per-frame cameras that holds row by row
@@ -502,12 +520,14 @@ int k2_f16_check(dsac_ctx* c, const char* who, int elem, const void* err16) {
         return fail(c, DSAC_ERR_INVALID, "%s: %s error images need the frame's xyz (%p) and uv (%p) on 16-byte addresses", who, what, (const void*)F.xyz, (const void*)F.uv);
     if (!dk::pose_split_available(F))
         return fail(c, DSAC_ERR_INVALID, "%s: %s error images need a focal length <= 1024 px (the exact-transform form), got fx = %g, fy = %g", who, what, F.fx, F.fy);
-    if (c->k2.variant != -1) return fail(c, DSAC_ERR_INVALID, "%s: %s error images need k2_variant -1 (the auto policy's tiles), it is %d", who, what, c->k2.variant);
-    const int ex_bits = dk::K2_FLAG_EXACT | dk::K2_FLAG_EXACT_ANY;
-    if (c->k2.flags & ~ex_bits)
-        return fail(c, DSAC_ERR_INVALID, "%s: %s error images exist for the exact-transform form only: k2_flags 0x%x sets bits other than 28 / 29", who, what, c->k2.flags);
-    if (!c->k2.exact_auto && !(c->k2.flags & ex_bits))
-        return fail(c, DSAC_ERR_INVALID, "%s: %s error images need the exact-transform form: k2_exact_auto is 0 and neither k2_flags bit 28 nor 29 is set", who, what);
+    switch (dk::k2_exact_only(c->k2.variant, c->k2.flags, c->k2.exact_auto)) {
+        case dk::K2_EXONLY_VARIANT:
+            return fail(c, DSAC_ERR_INVALID, "%s: %s error images need k2_variant -1 (the auto policy's tiles), it is %d", who, what, c->k2.variant);
+        case dk::K2_EXONLY_FLAGS:
+            return fail(c, DSAC_ERR_INVALID, "%s: %s error images exist for the exact-transform form only: k2_flags 0x%x sets bits other than 28 / 29", who, what, c->k2.flags);
+        case dk::K2_EXONLY_AUTO_OFF:
+            return fail(c, DSAC_ERR_INVALID, "%s: %s error images need the exact-transform form: k2_exact_auto is 0 and neither k2_flags bit 28 nor 29 is set", who, what);
+    }
     return DSAC_OK;
 }
 
@@ -1184,7 +1204,7 @@ static int reproject_call(dsac_ctx* c, const char* who, int N, const double* pos
     float* d_part = nullptr;
     ARG_TRY(k2_soft_part(c, N, d_err != nullptr, d_soft != nullptr, &tau, &beta, &d_part));
     int used = 0;
-    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, elem, d_part, /*gated=*/true, nullptr, &used));
+    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, elem, d_part, d_soft != nullptr, /*gated=*/true, nullptr, &used));
     if (d_soft) HIP_TRY(c, dk::reduce_soft(c->stream, N, used, d_part, d_soft));
     return end_call(c);
 }
@@ -1284,7 +1304,7 @@ static int score_hypotheses_common(dsac_ctx* c, int N, int Nf, uint64_t seed, co
         int used_d = 0;
         hipEvent_t k2_done = nullptr;
         // the tail's start rides on K2's own dispatch packet (pi_k2done as its stop event): no record between K2 and the next K1
-        ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, dk::K2_ELEM_F32, part.as<float>(), /*gated=*/true, c->pi_k2done,
+        ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, dk::K2_ELEM_F32, part.as<float>(), /*want_soft=*/true, /*gated=*/true, c->pi_k2done,
                          &used_d, &k2_done));
         ARG_TRY(pi_score_tail(c, b, tk, k2_done, Nf > 0 ? Nf : N, frames, used_d, part.as<float>(), d_scores, scale, d_w, d_ent, avg6_or_null ? d_poses : nullptr,
                               d_avg));
@@ -1296,7 +1316,7 @@ static int score_hypotheses_common(dsac_ctx* c, int N, int Nf, uint64_t seed, co
     // K1 writes the poses AND their staged K2 records (no separate pose_prep launch)
     HIP_TRY(c, dk::sample(c->stream, N, seed, d_sets_in, c->F, (int)thr, max_tries, d_poses, d_sets_out, d_ok, c->staged.as<float>(), Nf, c->k1, c->guide.view()));
     int used = 0;
-    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, dk::K2_ELEM_F32, c->soft_part.as<float>(), /*gated=*/true, nullptr, &used));
+    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, dk::K2_ELEM_F32, c->soft_part.as<float>(), /*want_soft=*/true, /*gated=*/true, nullptr, &used));
     HIP_TRY(c, score_tail(c->stream, Nf > 0 ? Nf : N, frames, used, c->soft_part.as<float>(), d_scores, scale, d_w, d_ent, avg6_or_null ? d_poses : nullptr,
                           d_avg));
     return end_call(c);
@@ -1407,7 +1427,7 @@ int dsac_score_sampled(dsac_ctx* c, int slot, float clampv, float tau, float bet
     if (c->slot_reduced_recorded[slot]) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->slot_reduced[slot], 0));  // partials of frame i-2 consumed
     int used = 0;
     // the slot's own frame and records; no k2_wait / k2_record gate around this launch (dsac_set_k2_events)
-    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->slot_staged[slot].as<float>(), SF, poses, clampv, tau, beta, err_or_null, dk::K2_ELEM_F32, part, /*gated=*/false, nullptr, &used));
+    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->slot_staged[slot].as<float>(), SF, poses, clampv, tau, beta, err_or_null, dk::K2_ELEM_F32, part, /*want_soft=*/true, /*gated=*/false, nullptr, &used));
     HIP_TRY(c, hipEventRecord(c->slot_free[slot], c->stream));
     c->slot_free_recorded[slot] = true;
     c->slot_pending[slot] = false;
@@ -1442,7 +1462,7 @@ int dsac_set_option(dsac_ctx* c, const char* key, int value) {
     if (!c || !key) return fail(c, DSAC_ERR_INVALID, "dsac_set_option: NULL argument");
     const std::string k = key;
     if (k == "k2_variant") {
-        if (!dk::reproject_variant_known(value)) return fail(c, DSAC_ERR_INVALID, "dsac_set_option: unknown K2 kernel form %d", value);
+        if (!dk::k2_variant_known(value)) return fail(c, DSAC_ERR_INVALID, "dsac_set_option: unknown K2 kernel form %d", value);
         c->k2.variant = value;
     }
     else if (k == "k2_order") c->k2.pixel_minor = value != 0;
@@ -2495,7 +2515,7 @@ int dsac_process_images(dsac_ctx* c, int hyps_per_frame, uint64_t seed, float th
     // RECORD between K2 and the next call's K1 is a packet of its own and a ~7 us bubble on the stream that bounds the loop (rank step of configs[3]:
     // 18.6 us from the end of K2 to the start of the next K1 with the record and the wait below, profiles/r04_rank_timeline_mode2.txt)
     hipEvent_t k2_done = nullptr;
-    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, dk::K2_ELEM_F32, part.as<float>(), /*gated=*/true,
+    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, dk::K2_ELEM_F32, part.as<float>(), /*want_soft=*/true, /*gated=*/true,
                      mode == 2 ? c->pi_k2done : nullptr, &used, &k2_done));
     hipStream_t ts = c->stream;
     if (mode == 2) {
@@ -2563,7 +2583,7 @@ static int pi_begin_call(dsac_ctx* c, const char* who, int hyps_per_frame, uint6
     if (c->pi_refstream) ARG_TRY(pi_refstream_k1(c, who, hyps_per_frame, thr, d_poses, d_sets, d_ok));
     else HIP_TRY(c, dk::sample(c->stream, N, seed, nullptr, c->F, (int)thr, max_tries, d_poses, d_sets, d_ok, c->staged.as<float>(), Nf, c->k1, c->guide.view()));
     int used = 0;
-    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, elem, d_part, /*gated=*/true, nullptr, &used));
+    ARG_TRY(k2_stage(c, c->stream, N, Nf, c->staged.as<float>(), c->F, d_poses, clampv, tau, beta, d_err, elem, d_part, d_soft != nullptr, /*gated=*/true, nullptr, &used));
     if (d_soft) HIP_TRY(c, dk::reduce_soft(c->stream, N, used, d_part, d_soft));
     return end_call(c);
 }

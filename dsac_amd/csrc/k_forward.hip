@@ -744,13 +744,12 @@ __global__ __launch_bounds__(K2_THREADS) void k_reproject_hp(const float* __rest
 
 template <int HT, int KM_CH>
 static hipError_t launch_reproject_hp(hipStream_t st, int N, const float* staged, const FrameDev& F, float clampv, float* err, float kA,
-                                      float kB, float* soft_part, int* tiles_used, int Nf, bool pixel_minor, int kflags, hipEvent_t evA, hipEvent_t evB) {
+                                      float kB, float* soft_part, int Nf, bool pixel_minor, int kflags, hipEvent_t evA, hipEvent_t evB) {
     const int tile = K2_THREADS * KM_CH;  // 64 pixels per wave-chunk
     const int PT = (F.P + tile - 1) / tile;
     const int NTa = (N + HT - 1) / HT;
     const int grid = ((PT + 7) / 8) * 8 * NTa;
     const int NT = pixel_minor ? -NTa : NTa;
-    if (tiles_used) *tiles_used = PT;
     const bool ERR = err != nullptr, SOFT = soft_part != nullptr, UV = F.uv != nullptr;
     // experiment knob (k2_flags bits 8..15): that many 8-KiB units of unused dynamic LDS per workgroup cap the workgroups per CU
     const size_t lds_pad = (size_t)((kflags >> 8) & 0xff) * 8192;
@@ -1297,15 +1296,14 @@ __global__ __launch_bounds__(WAVES * 64) void k_reproject_ps(const float* __rest
 
 template <int NG, int WAVES>
 static hipError_t launch_reproject_ps(hipStream_t st, int N, const float* staged, const FrameDev& F, float clampv, float* err, float kA, float kB,
-                                      float* soft_part, int* tiles_used, int Nf, int kflags, hipEvent_t evA, hipEvent_t evB) {
-    if (N % 4 != 0 && soft_part) return hipErrorInvalidValue;  // the partial sums leave as 16-byte stores
+                                      float* soft_part, int Nf, int kflags, hipEvent_t evA, hipEvent_t evB) {
+    // (the partial sums leave as 16-byte stores: the plan has refused N % 4 != 0 with them)
     int dev = 0, cus = 256;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     int per_cu = (kflags >> 8) & 0xff;  // k2_flags bits 8..15: persistent workgroups per CU (0 = default)
     if (per_cu <= 0) per_cu = 3;
     const int grid = ((cus * per_cu + 7) / 8) * 8;
-    if (tiles_used) *tiles_used = (F.P + 63) / 64;
     const bool ERR = err != nullptr, SOFT = soft_part != nullptr, UV = F.uv != nullptr;
 #define DSAC_K2P(E, S, U)                                                                                                               \
     hipExtLaunchKernelGGL((k_reproject_ps<NG, WAVES, E, S, U>), dim3(grid), dim3(WAVES * 64), 0, st, evA, evB, 0, staged, F.xyz, F.uv, err,   \
@@ -1328,7 +1326,7 @@ constexpr int k2_bf16_exf(bool soft, bool uv, bool g64) {
 }
 template <int NG, int CHW, int WAVES, bool PW, int MINW = 1, bool LO = false, int EX = 0, int ANY = 0>
 static hipError_t launch_reproject_st(hipStream_t st, int N, const float* staged, const FrameDev& F, float clampv, float* err, float kA, float kB,
-                                      float* soft_part, int* tiles_used, int Nf, int kflags, hipEvent_t evA, hipEvent_t evB, const float* staged_lo = nullptr,
+                                      float* soft_part, int Nf, int kflags, hipEvent_t evA, hipEvent_t evB, const float* staged_lo = nullptr,
                                       const void* split = nullptr) {
     constexpr int HT = 16 * NG;
     const int tile = WAVES * CHW * 64;
@@ -1336,7 +1334,6 @@ static hipError_t launch_reproject_st(hipStream_t st, int N, const float* staged
     const int PT = (F.P + tile - 1) / tile;
     const int NTa = (N + HT - 1) / HT;
     const int grid = (kflags & 32) ? PT * NTa : WAVES == 1 ? ((PT + 31) / 32) * 32 * NTa : ((PT + 7) / 8) * 8 * NTa;
-    if (tiles_used) *tiles_used = PW ? PT * WAVES : PT;
     const bool ERR = err != nullptr, SOFT = soft_part != nullptr, UV = F.uv != nullptr;
     const bool G64 = !UV && (F.W & 63) == 0;
 #define DSAC_K2S(E, S, U, G)                                                                                                               \
@@ -1356,11 +1353,10 @@ static hipError_t launch_reproject_st(hipStream_t st, int N, const float* staged
 // of 4 -- the tail launch (ANY = 2) for the lane of the last 1-3 cells, whose sums go to one more partial row.  A timing pair spans both launches.
 template <int NG, int CHW, int MINW>
 static hipError_t launch_reproject_any(hipStream_t st, int N, const float* staged, const FrameDev& F, float clampv, float* err, float kA, float kB, float* soft_part,
-                                       int* tiles_used, int Nf, int kflags, hipEvent_t evA, hipEvent_t evB, const void* split) {
+                                       int Nf, int kflags, hipEvent_t evA, hipEvent_t evB, const void* split) {
     const bool tail = (F.P & 3) != 0;
-    int rows = 0;
-    hipError_t e = launch_reproject_st<NG, CHW, 1, true, MINW, false, 2, 1>(st, N, staged, F, clampv, err, kA, kB, soft_part, &rows, Nf, kflags, evA, tail ? nullptr : evB, nullptr, split);
-    if (tiles_used) *tiles_used = rows;
+    const int rows = (F.P + CHW * 64 - 1) / (CHW * 64);  // the main launch's partial rows; the tail's is the plan's one more
+    hipError_t e = launch_reproject_st<NG, CHW, 1, true, MINW, false, 2, 1>(st, N, staged, F, clampv, err, kA, kB, soft_part, Nf, kflags, evA, tail ? nullptr : evB, nullptr, split);
     if (e != hipSuccess || !tail) return e;
     const int NTa = (N + 63) / 64;
     float* part = soft_part ? soft_part + (size_t)rows * N : nullptr;  // row `rows` <= ceil(P / 64) < reproject_num_pixel_tiles(P)
@@ -1372,7 +1368,6 @@ static hipError_t launch_reproject_any(hipStream_t st, int N, const float* stage
     else if (ERR) { if (UV) DSAC_K2T(true, false, true); else DSAC_K2T(true, false, false); }
     else if (SOFT) { if (UV) DSAC_K2T(false, true, true); else DSAC_K2T(false, true, false); }
 #undef DSAC_K2T
-    if (tiles_used && SOFT) *tiles_used = rows + 1;
     return hipGetLastError();
 }
 
@@ -1536,12 +1531,11 @@ __global__ __launch_bounds__(K2_THREADS) void k_reproject_prec(const double* __r
 
 template <int HT>
 static hipError_t launch_reproject_prec(hipStream_t st, int N, const double* poses, const FrameDev& F, float clampv, float* err, double kAd, double kBd,
-                                        float* soft_part, int* tiles_used, int Nf, hipEvent_t evA, hipEvent_t evB, int rec32, int diag) {
+                                        float* soft_part, int Nf, hipEvent_t evA, hipEvent_t evB, int rec32, int diag) {
     const float kA = (float)kAd, kB = (float)kBd, kAl = (float)(kAd - (double)kA), kBl = (float)(kBd - (double)kB);
     const int PT = (F.P + K2_THREADS * 4 - 1) / (K2_THREADS * 4);
     const int NTa = (N + HT - 1) / HT;
     const int grid = ((PT + 7) / 8) * 8 * NTa;
-    if (tiles_used) *tiles_used = 2 * PT;  // a (high, low) pair of partial rows per pixel tile; 2 ceil(P / 1024) <= reproject_num_pixel_tiles(P)
     const bool ERR = err != nullptr, SOFT = soft_part != nullptr, UV = F.uv != nullptr;
 #define DSAC_K2P(E, S, U)                                                                                                                       \
     do { if (diag) hipExtLaunchKernelGGL((k_reproject_prec<HT, E, S, U, true>), dim3(grid), dim3(K2_THREADS), 0, st, evA, evB, 0, poses, F.xyz, F.uv, err, soft_part, N, F.P, \
@@ -1601,14 +1595,6 @@ hipError_t k2_range_census(hipStream_t st, int N, const double* poses, const Fra
     return hipGetLastError();
 }
 
-bool reproject_variant_known(int v) {
-    return v == -1 || (v >= 0 && v <= 3) || (v >= 10 && v <= 13) || (v >= 20 && v <= 27) || (v >= 40 && v <= 62) || (v >= 65 && v <= 77) || (v >= 80 && v <= 85) || v == 89 || (v >= 93 && v <= 95);
-}
-
-// the largest count of partial-sum rows over all forms: one row per 64-pixel wave chunk, and the per-wave-sum forms with several waves per workgroup write
-// PT * WAVES rows (their idle waves of the last workgroup write zero rows): up to WAVES - 1 <= 15 rows beyond ceil(P / 64)
-int reproject_num_pixel_tiles(int P) { return (P + 63) / 64 + 15; }
-
 template <int PX, int HT, bool SPOSE>
 static hipError_t launch_reproject(hipStream_t st, int N, const float* staged, const FrameDev& F, float clampv, float* err, float kA, float kB,
                                    float* soft_part, int Nf, bool pixel_minor, int kflags, hipEvent_t evA, hipEvent_t evB) {
@@ -1628,212 +1614,88 @@ static hipError_t launch_reproject(hipStream_t st, int N, const float* staged, c
     return hipGetLastError();
 }
 
-// variant: -1 = auto (default) ; VALU forms: 0 = LDS-staged poses, HT = 32 ; 1 = scalar-load poses (SGPR operands), HT = 32 ; 2 = HT 16 ;
-//          3 = HT 64 ; 10..13 = 1, 2, 4, 8 hypothesis rows per workgroup ; matrix-core forms <HT, 64-pixel chunks per wave>: 20 = <64,2>,
-//          21 = <64,4>, 22 = <128,2>, 23 = <32,2>, 24 = <64,1>, 25 = <128,4>, 26 = <32,4>, 27 = <128,1> ; streaming small-tile forms
-//          <16-hypothesis groups, chunks per wave, waves per workgroup>: 40 = <1,1,4>, 41 = <2,1,4>, 42 = <4,1,4>, 43 = <2,2,4> (partial sums
-//          through LDS, one row per workgroup) ; per-wave partial sums, no barrier: 44-46 = <1|2|4,4,1>, 47-49 = <1|2|4,2,1>, 50-52 = <1|2|4,1,1>,
-//          53 = <2,1,4>, 54 = <2,2,4>, 55 = <4,1,4>, 56 = <2,4,4>, 57 = <4,2,4>.  Unknown values are an error.
-hipError_t reproject(hipStream_t st, int N, const float* staged, const FrameDev& F, float clampv, float* err, float tau, float beta,
-                     float* soft_part, const K2Opts& opts, int* tiles_used, int Nf) {
-    if (tiles_used) *tiles_used = 0;
-    if (N <= 0 || F.P <= 0 || (!err && !soft_part)) return hipSuccess;
-    if (Nf <= 0 || F.frames <= 1) Nf = N > 0 ? ((N + 127) / 128) * 128 : 128;  // one frame: every tile maps to frame 0
-    else if (Nf % K2_NF_MULTIPLE != 0) return hipErrorInvalidValue;           // tiles (<= 128 hypotheses) must not straddle frames
+// K2: enqueue the kernel of a plan (k2_plan.h).  Every decision -- form, kernel, block order, flags -- is the plan's; the switches below only turn its tile
+// numbers into template arguments, through the id lists the plan resolved them from.
+static_assert(K2_WG == K2_THREADS, "k2_plan.h counts partial-sum rows with the workgroup size of the kernels");
+static_assert(K2_STATUS_OK == (int)hipSuccess && K2_STATUS_INVALID == (int)hipErrorInvalidValue && K2_STATUS_NOT_SUPPORTED == (int)hipErrorNotSupported,
+              "k2_plan.h spells the HIP status values out");
+hipError_t reproject(hipStream_t st, const K2Plan& plan, int N, const float* staged, const FrameDev& F, float clampv, float* err, float tau, float beta,
+                     float* soft_part, const K2Call& call) {
+    if (plan.status != K2_STATUS_OK) return (hipError_t)plan.status;
+    const K2Kernel& k = plan.k;
     const float LOG2E = 1.4426950408889634f;
     const float kA = beta * LOG2E, kB = -beta * tau * LOG2E;
-    const bool vec = (F.P % 4 == 0) && ((reinterpret_cast<uintptr_t>(err) & 15) == 0) && ((reinterpret_cast<uintptr_t>(F.xyz) & 15) == 0) &&
-                     ((reinterpret_cast<uintptr_t>(F.uv) & 15) == 0);
-    if (tiles_used) *tiles_used = vec ? (F.P + K2_THREADS * 4 - 1) / (K2_THREADS * 4) : (F.P + K2_THREADS - 1) / K2_THREADS;
-    // the streaming / persistent forms (variant >= 40) know two block orders: XCD-aware pixel-minor (k2_order 1) and plain pixel-minor (k2_order 0
-    // or k2_flags bit 5)
-    int kf = opts.flags | ((opts.variant >= 40 && !opts.pixel_minor) ? 32 : 0);
+    const int Nf = plan.Nf, kf = plan.kflags;
+    const bool pm = plan.pixel_minor;
     // timing events (dsac_profile_enable): attached to the kernel's own dispatch (hipExtLaunchKernelGGL) instead of two event records on the
     // stream, which cost ~7 us of bubble each (one 640x480 frame: 100 us per step with them, 86 without)
-    hipEvent_t evA = opts.ev_start, evB = opts.ev_stop;
-    // the form decision is taken from THIS frame (the one the launch reads), and reported: form + the reasons the exact form did not run
-    const bool split_ok = opts.split && pose_split_available(F);
-    const bool ex_variant = opts.variant == 84 || opts.variant == 85 || opts.variant == 89 || (opts.variant >= 93 && opts.variant <= 95);
-    int why = 0;
-    if (!(opts.flags & (K2_FLAG_EXACT | K2_FLAG_EXACT_ANY))) {
-        if (opts.variant >= 0 || (opts.flags & (K2_FLAG_PRECISE | K2_FLAG_RECLO | K2_FLAG_STORE_ONLY | (1 << 26)))) why |= K2_WHY_FORCED;
-        else if (!opts.exact_auto) why |= K2_WHY_AUTO_OFF;
-    } else if (opts.variant >= 0 && !ex_variant) why |= K2_WHY_FORCED;
-    if (!pose_split_available(F)) why |= K2_WHY_FOCAL;
-    if (!opts.poses64) why |= K2_WHY_NO_POSES;  // dsac_score_sampled without the cv poses: nothing to split
-    // 16-bit error images (dsac_reproject_f16 / _bf16, dsac_process_images_begin_f16 / _bf16): the auto policy's exact vector build and nothing else -- the entry points have refused
-    // every other request by name; a launch that gets here all the same is an error, never another form and never a float store into a half buffer
-    if (opts.err_elem != K2_ELEM_F32 && !(err && vec && F.P % 8 == 0 && split_ok && opts.variant < 0 && k2_wants_exact(opts) &&
-                                          !(opts.flags & ~(K2_FLAG_EXACT | K2_FLAG_EXACT_ANY))))
-        return hipErrorNotSupported;
-    auto report = [&](int form) { if (opts.report) { opts.report[0] = form; opts.report[1] = (form == K2_FORM_EXACT_VEC || form == K2_FORM_EXACT_ANY) ? 0 : why; } };
-    // An arithmetic form that was ASKED for (k2_flags bits 25 / 27 / 28) and cannot run on this map -- its kernels read 16-byte vectors: H*W % 4, aligned buffers
-    // and, on the implicit grid, four cells of a lane in one row; the exact form also needs a focal length <= 2^10 -- is an error, not a silent fp32 launch
-    // (a parity run must not measure the fast form unknowingly).  The auto policy's exact form simply falls back.
-    if (opts.poses64 && (((opts.flags & K2_FLAG_PRECISE) && !(vec && (F.uv || F.W % 4 == 0))) || ((opts.flags & K2_FLAG_RECLO) && !vec) ||
-                         ((opts.flags & K2_FLAG_EXACT) && !(vec && split_ok)) ||
-                         ((opts.flags & K2_FLAG_EXACT_ANY) && !(split_ok && (opts.variant < 0 || (ex_variant && vec))))))
-        return hipErrorNotSupported;
-    // bit 29 (EXACT, any map) is what a parity run sets: besides the focal length only what would make it another form rules it out -- a k2_variant that names
-    // another form (the tile / tail trades 84 .. 95 exist in the vector build only), or a call without the cv poses the records are split from
-    if ((opts.flags & K2_FLAG_EXACT_ANY) && !opts.poses64) return hipErrorNotSupported;
-    // the precise form (k2_flags bit 25): needs the cv poses themselves, 16-byte vectors and -- on the implicit grid -- four cells of a lane in one row
-    if ((opts.flags & K2_FLAG_PRECISE) && opts.poses64 && vec && (F.uv || F.W % 4 == 0)) {
-        const double nhp = (double)N * (double)F.P;
-        const double kAd = (double)beta * 1.4426950408889634, kBd = -(double)beta * (double)tau * 1.4426950408889634;
-        // hypothesis tile by size as the VALU forms: 32 for big launches, 16 for a single small frame (more workgroups)
-        const int rec32 = (opts.flags >> 26) & 1;
-        report(K2_FORM_PRECISE);
-        return nhp > 2.0e8 ? launch_reproject_prec<32>(st, N, opts.poses64, F, clampv, err, kAd, kBd, soft_part, tiles_used, Nf, evA, evB, rec32, opts.diag)
-                           : launch_reproject_prec<16>(st, N, opts.poses64, F, clampv, err, kAd, kBd, soft_part, tiles_used, Nf, evA, evB, rec32, opts.diag);
-    }
-    // records in two pieces (k2_flags bit 27): the one-wave streaming form <64 hypotheses, 256 pixels> with the fp16 correction instructions, whatever the size
-    if ((opts.flags & K2_FLAG_RECLO) && opts.staged_lo && vec && (opts.variant < 0 || (opts.variant >= 80 && opts.variant <= 83))) {
-        report(K2_FORM_RECLO);
-#define DSAC_LO(NG_, CH_, MW_) launch_reproject_st<NG_, CH_, 1, true, MW_, true>(st, N, staged, F, clampv, err, kA, kB, soft_part, tiles_used, Nf, kf | 32, evA, evB, opts.staged_lo)
-        switch (opts.variant) {  // k2_variant 80..83 with the flag: the register / occupancy trades of this form (A/B); -1: the measured one
-            case 80: return DSAC_LO(4, 4, 3);   // <64 hypotheses, 256 pixels>, 3 waves per SIMD (92 B of scratch)
-            case 82: return DSAC_LO(4, 2, 4);   // <64, 128>, 4 waves per SIMD
-            case 83: return DSAC_LO(2, 4, 3);   // <32, 256>, 3 waves per SIMD
-            case 81: default: return DSAC_LO(4, 4, 2);  // <64, 256>, 2 waves per SIMD, no scratch: the fastest of the four (profiles/r05_k2_reclo_ab.txt)
-        }
-#undef DSAC_LO
-    }
-    // the exact-transform form (k2_flags bit 28, round 6): the one-wave streaming forms with the split records; k2_variant 84 / 89 / 93 = its tile / occupancy trades
-    // Maps the vector build cannot read (H*W % 4, a buffer off the 16-byte grid) take the ANY build of the same kernel on the auto policy's tile for their
-    // size: the same arithmetic per cell, the same tile for the same P, so the two builds agree bit for bit on the same cells (but for groups that hold a hypothesis
-    // with clamped records, which only the ANY build sends through the fp32 transform: grp_far)
-    if (k2_wants_exact(opts) && split_ok && opts.variant < 0 && !vec) {
-        report(K2_FORM_EXACT_ANY);
-#define DSAC_EXA(NG_, CH_, MW_) launch_reproject_any<NG_, CH_, MW_>(st, N, staged, F, clampv, err, kA, kB, soft_part, tiles_used, Nf, kf | 32, evA, evB, opts.split)
-        if (F.P <= 16384) return DSAC_EXA(4, 1, 3);
-        return DSAC_EXA(4, 4, 2);
-#undef DSAC_EXA
-    }
-    if (k2_wants_exact(opts) && split_ok && vec && (opts.variant < 0 || ex_variant)) {
-        report(K2_FORM_EXACT_VEC);
-#define DSAC_EX(NG_, CH_, MW_, F_) launch_reproject_st<NG_, CH_, 1, true, MW_, false, F_>(st, N, staged, F, clampv, err, kA, kB, soft_part, tiles_used, Nf, kf | 32, evA, evB, nullptr, opts.split)
-        switch (opts.variant) {
-            // (85 .. 88: <64, 128 / 256> with a scheduling fence per m at three waves per SIMD, one / two / four waves per workgroup -- 44-480 B of scratch, 1.08-1.7 ms:
-            //  measured and removed, profiles/r06_k2_exact_ab.txt)
-            case 85: return DSAC_EX(4, 4, 2, 2);      // 84 with the one-transcendental tail (A/B)
-            case 94: return DSAC_EX(4, 1, 3, 2);      // 93 with the one-transcendental tail (A/B)
-            case 89: return DSAC_EX(2, 4, 2, 1);      // <32 hypotheses, 256 pixels>, 2 waves per SIMD
-            case 93: return DSAC_EX(4, 1, 3, 1);      // <64, 64>, one-wave workgroups, 168 registers: 3 waves per SIMD
-            // (90 .. 92: <64, 4 waves x 64>, <64, 2 x 128> at two / three waves per SIMD: 1 098-1 206 us at the bench shape, 67.5-77 us for one frame -- measured
-            //  and removed, profiles/r06_k2_exact_tiles.txt)
-            case 95: return DSAC_EX(4, 1, 4, 2);      // 94 at four waves per SIMD (the one-transcendental tail needs 128 registers there)
-            case -1:  // auto: the one-transcendental tail (968-987 against 1 002-1 020 us at the bench shape, the same or smaller errors: profiles/r06_k2_rsq_ab.txt,
-                      // r06_k2_rsq_parity.txt) on the <64, 256> tile at every size.  For one frame of 256 hypotheses the <64, 64> tile is 0.8 us faster by itself
-                      // (62.6 against 63.4) but leaves four times the partial-sum rows: k_reduce_soft 27.6 against 8.9 us (profiles/r06_one_image_trace.txt)
-                // small maps keep the small tile: a 40 x 40 map is 7 tiles of 256 pixels (one image per call 116 -> 127 us with them), and its partial sums are 25 rows
-                // half error images: the same two tiles, EXF = 3 (8-byte stores) or 4 (rows traded between neighbouring lanes, 16-byte stores; "k2_f16_store")
-                if (opts.err_elem == K2_ELEM_F16) {
-                    if (opts.f16_store == 0) return F.P <= 16384 ? DSAC_EX(4, 1, 3, 3) : DSAC_EX(4, 4, 2, 3);
-                    return F.P <= 16384 ? DSAC_EX(4, 1, 3, 4) : DSAC_EX(4, 4, 2, 4);
-                }
-                // bfloat16 error images: EXF = 5 / 6, the same tiles and the same two layouts
-                if (opts.err_elem == K2_ELEM_BF16) {
-                    if (opts.f16_store == 0) return F.P <= 16384 ? DSAC_EX(4, 1, 3, 5) : DSAC_EX(4, 4, 2, 5);
-                    return F.P <= 16384 ? DSAC_EX(4, 1, 3, 6) : DSAC_EX(4, 4, 2, 6);
-                }
-                if (F.P <= 16384) return DSAC_EX(4, 1, 3, 2);
-                return DSAC_EX(4, 4, 2, 2);
-            case 84: default: return DSAC_EX(4, 4, 2, 1);  // <64, 256>, 2 waves per SIMD, reciprocal + Newton + square root (<64, 256> at three waves per SIMD spills: 1.7 ms, profiles/r06_k2_exact_ab.txt)
-        }
-#undef DSAC_EX
-    }
-    report((!vec || opts.variant < 0 ? !vec || !soft_part : opts.variant <= 13) ? K2_FORM_FP32_VALU : K2_FORM_FP32_MFMA);
-    if (!vec) return launch_reproject<1, 32, false>(st, N, staged, F, clampv, err, kA, kB, soft_part, Nf, opts.pixel_minor, kf, evA, evB);
-    const bool pm = opts.variant < 0 ? true : opts.pixel_minor;  // the auto policy's forms were all measured with pixel tiles innermost
+    hipEvent_t evA = call.ev_start, evB = call.ev_stop;
 #define DSAC_VA(PX_, HT_, SP_) launch_reproject<PX_, HT_, SP_>(st, N, staged, F, clampv, err, kA, kB, soft_part, Nf, pm, kf, evA, evB)
-#define DSAC_HP(HT_, CH_) launch_reproject_hp<HT_, CH_>(st, N, staged, F, clampv, err, kA, kB, soft_part, tiles_used, Nf, pm, kf, evA, evB)
-#define DSAC_ST(NG_, CH_, WV_, PW_) launch_reproject_st<NG_, CH_, WV_, PW_>(st, N, staged, F, clampv, err, kA, kB, soft_part, tiles_used, Nf, kf, evA, evB)
-    int variant = opts.variant;
-    if (variant < 0) {
-        // auto (measured on MI355X, profiles/r02_k2_variants.txt).  With the fused soft-inlier sums the kernel is VALU-limited: matrix-core
-        // form; 1024 pixels per workgroup for big launches (> 1.5 GB of error images: N = 4096 or a batch of frames: 443 vs 460-508 us for
-        // the 8-frame batch), 256 for a single frame of 256 hypotheses.  Error images only: store-limited, the VALU kernel with pixel
-        // tiles innermost has the best store stream (N = 256: 56.6 vs 58.9 us; N = 4096: equal).
-        // Round 3 (A/B inside bench.py on five boxes, profiles/r03_k2_ab_bench*.txt -- a plain-HIP harness, scripts/micro/k2_lab, ranks the forms
-        // differently from the bench's process and is NOT what this policy follows): big launches take the streaming form <32 hypotheses, 256
-        // pixels> per one-wave workgroup (no LDS, no barrier, operands straight from the staged records, per-wave partial sums) in PLAIN
-        // pixel-minor block order: 842-870 us against 904-950 for round 2's <64,4> (0.73-0.75 of the HBM spec instead of 0.67-0.70); one frame
-        // of 256 hypotheses takes <64 hypotheses, 4 waves x 64 pixels>: 56.7-58.0 against 60.2-60.8 us.
-        // Late round 3: <64 hypotheses, 256 pixels> per one-wave workgroup at >= 4 waves per SIMD (form 58) instead of <32, 256> (form 45): 1 % ahead in
-        // every A/B on six boxes (profiles/r03_k2_ab_58_45.txt: 861-867 against 872-875 us alternating on one box) and half the partial-sum rows
-        // (with sampled pixel positions, or a map width that is not a multiple of 64, the kernel keeps the positions of every chunk in vector
-        // registers: form 58's 128-register build would spill 108-116 bytes per lane there, form 45 needs no scratch)
-        // By size (A/B inside bench.py at 2 ... 16 frames of 256 hypotheses per launch, profiles/r03_k2_ab_mid.txt): up to 1 GB of error images form 42
-        // (2 frames: 111.7 us against 115.1 for form 45 and 121.6 for 58), up to 4.4 GB form 45 (4 frames 220.5 against 224 / 232; 8 frames
-        // 424-427 us = 0.75 of the HBM spec against 443 / 460-465; 12 frames 644 = 638-644), above it form 58 (16 frames: 861-867 against 872-875)
-        const double bytes = (double)N * (double)F.P * 4.0;
-        const bool big = bytes > 1.0e9;
-        const bool grid64 = F.uv == nullptr && (F.W & 63) == 0;
-        variant = soft_part ? (big ? ((grid64 && bytes > 4.4e9) ? 58 : 45) : 42) : 0;
-        if (soft_part && big) kf |= 32;
+#define DSAC_HP(HT_, CH_) launch_reproject_hp<HT_, CH_>(st, N, staged, F, clampv, err, kA, kB, soft_part, Nf, pm, kf, evA, evB)
+#define DSAC_ST(NG_, CH_, WV_, PW_, MW_) launch_reproject_st<NG_, CH_, WV_, PW_, MW_>(st, N, staged, F, clampv, err, kA, kB, soft_part, Nf, kf, evA, evB)
+#define DSAC_PS(NG_) launch_reproject_ps<NG_, 4>(st, N, staged, F, clampv, err, kA, kB, soft_part, Nf, kf, evA, evB)
+#define DSAC_LO(NG_, CH_, MW_) launch_reproject_st<NG_, CH_, 1, true, MW_, true>(st, N, staged, F, clampv, err, kA, kB, soft_part, Nf, kf, evA, evB, call.staged_lo)
+#define DSAC_EX(NG_, CH_, MW_, F_) launch_reproject_st<NG_, CH_, 1, true, MW_, false, F_>(st, N, staged, F, clampv, err, kA, kB, soft_part, Nf, kf, evA, evB, nullptr, call.split)
+#define DSAC_EXA(NG_, CH_, MW_) launch_reproject_any<NG_, CH_, MW_>(st, N, staged, F, clampv, err, kA, kB, soft_part, Nf, kf, evA, evB, call.split)
+    switch (k.family) {
+        case K2_FAM_NONE: return hipSuccess;  // an empty call
+        case K2_FAM_VALU_SCALAR: return DSAC_VA(1, 32, false);
+        case K2_FAM_VALU: case K2_FAM_HP: case K2_FAM_ST: case K2_FAM_PS:
+            switch (k.id) {
+#define K2_VA_(ID, PX, HT, SP) case ID: return DSAC_VA(PX, HT, SP);
+#define K2_HP_(ID, HT, CH) case ID: return DSAC_HP(HT, CH);
+#define K2_ST_(ID, NG, CH, WV, PW, MW) case ID: return DSAC_ST(NG, CH, WV, PW, MW);
+#define K2_PS_(ID, NG) case ID: return DSAC_PS(NG);
+                K2_FP32_IDS(K2_VA_, K2_HP_, K2_ST_, K2_PS_)
+#undef K2_VA_
+#undef K2_HP_
+#undef K2_ST_
+#undef K2_PS_
+            }
+            break;
+        case K2_FAM_RECLO:
+            switch (k.id) {
+#define K2_LO_(ID, NG, CH, MW) case ID: return DSAC_LO(NG, CH, MW);
+                K2_RECLO_IDS(K2_LO_)
+#undef K2_LO_
+            }
+            break;
+        case K2_FAM_EXACT_VEC:
+#define K2_EX_(ID, NG, CH, MW, F_) if (k.ng == NG && k.ch == CH && k.minw == MW && k.exf == F_) return DSAC_EX(NG, CH, MW, F_);
+            K2_EXACT_IDS(K2_EX_)
+#undef K2_EX_
+            // the 16-bit stores of the auto policy's two tiles: binary16 (EXF 3 / 4) and bfloat16 (5 / 6)
+#define K2_AX_(NG, CH, MW)                                  \
+            if (k.ng == NG && k.ch == CH && k.minw == MW)   \
+                switch (k.exf) {                            \
+                    case 3: return DSAC_EX(NG, CH, MW, 3);  \
+                    case 4: return DSAC_EX(NG, CH, MW, 4);  \
+                    case 5: return DSAC_EX(NG, CH, MW, 5);  \
+                    case 6: return DSAC_EX(NG, CH, MW, 6);  \
+                }
+            K2_EXACT_AUTO_TILES(K2_AX_)
+#undef K2_AX_
+            break;
+        case K2_FAM_EXACT_ANY:
+#define K2_AX_(NG, CH, MW) if (k.ng == NG && k.ch == CH && k.minw == MW) return DSAC_EXA(NG, CH, MW);
+            K2_EXACT_AUTO_TILES(K2_AX_)
+#undef K2_AX_
+            break;
+        case K2_FAM_PRECISE: {
+            const double kAd = (double)beta * 1.4426950408889634, kBd = -(double)beta * (double)tau * 1.4426950408889634;
+            const int rec32 = (kf & K2_FLAG_REC32) ? 1 : 0;
+            return k.ht == 32 ? launch_reproject_prec<32>(st, N, call.poses64, F, clampv, err, kAd, kBd, soft_part, Nf, evA, evB, rec32, call.diag)
+                              : launch_reproject_prec<16>(st, N, call.poses64, F, clampv, err, kAd, kBd, soft_part, Nf, evA, evB, rec32, call.diag);
+        }
     }
-    switch (variant) {
-        case 0: return DSAC_VA(4, 32, false);
-        case 1: return DSAC_VA(4, 32, true);
-        case 2: return DSAC_VA(4, 16, false);
-        case 3: return DSAC_VA(4, 64, false);
-        case 10: return DSAC_VA(4, 1, false);
-        case 11: return DSAC_VA(4, 2, false);
-        case 12: return DSAC_VA(4, 4, false);
-        case 13: return DSAC_VA(4, 8, false);
-        case 20: return DSAC_HP(64, 2);
-        case 21: return DSAC_HP(64, 4);
-        case 22: return DSAC_HP(128, 2);
-        case 23: return DSAC_HP(32, 2);
-        case 24: return DSAC_HP(64, 1);
-        case 25: return DSAC_HP(128, 4);
-        case 26: return DSAC_HP(32, 4);
-        case 27: return DSAC_HP(128, 1);
-        // streaming small-tile forms <16-hypothesis groups, 64-pixel chunks per wave, waves per workgroup>
-        case 40: return DSAC_ST(1, 1, 4, false);
-        case 41: return DSAC_ST(2, 1, 4, false);
-        case 42: return DSAC_ST(4, 1, 4, false);
-        case 43: return DSAC_ST(2, 2, 4, false);
-        case 44: return DSAC_ST(1, 4, 1, true);
-        case 45: return DSAC_ST(2, 4, 1, true);
-        case 46: return DSAC_ST(4, 4, 1, true);
-        case 47: return DSAC_ST(1, 2, 1, true);
-        case 48: return DSAC_ST(2, 2, 1, true);
-        case 49: return DSAC_ST(4, 2, 1, true);
-        case 50: return DSAC_ST(1, 1, 1, true);
-        case 51: return DSAC_ST(2, 1, 1, true);
-        case 52: return DSAC_ST(4, 1, 1, true);
-        case 53: return DSAC_ST(2, 1, 4, true);
-        case 54: return DSAC_ST(2, 2, 4, true);
-        case 55: return DSAC_ST(4, 1, 4, true);
-        case 56: return DSAC_ST(2, 4, 4, true);
-        case 57: return DSAC_ST(4, 2, 4, true);
-        case 58: case 80: case 81: case 82: case 83: case 84: case 85: case 89: case 93: case 94: case 95:  // 84 / 89 / 93: the exact-transform forms when k2_flags bit 28 is set (above); 80..83: the two-piece-record forms when k2_flags bit 27 is set (above); without the flag the plain form
-            return launch_reproject_st<4, 4, 1, true, 4>(st, N, staged, F, clampv, err, kA, kB, soft_part, tiles_used, Nf, kf, evA, evB);  // <4,4,1>, >= 4 waves per SIMD
-        case 59: return launch_reproject_st<2, 4, 1, true, 5>(st, N, staged, F, clampv, err, kA, kB, soft_part, tiles_used, Nf, kf, evA, evB);  // <2,4,1>, >= 5 waves per SIMD
-        case 65: return launch_reproject_st<4, 4, 4, true, 4>(st, N, staged, F, clampv, err, kA, kB, soft_part, tiles_used, Nf, kf, evA, evB);  // <4,4,4> per-wave sums
-        case 66: return launch_reproject_st<4, 4, 2, true, 4>(st, N, staged, F, clampv, err, kA, kB, soft_part, tiles_used, Nf, kf, evA, evB);  // <4,4,2>
-        case 67: return DSAC_ST(1, 4, 4, true);
-        case 68: return DSAC_ST(2, 4, 4, false);
-        case 69: return DSAC_ST(2, 4, 8, true);
-        case 70: return launch_reproject_st<2, 4, 4, true, 4>(st, N, staged, F, clampv, err, kA, kB, soft_part, tiles_used, Nf, kf, evA, evB);
-        case 71: return DSAC_ST(1, 4, 8, true);
-        case 72: return DSAC_ST(2, 4, 16, true);
-        case 73: return DSAC_ST(2, 8, 1, true);
-        case 74: return DSAC_ST(1, 8, 1, true);
-        case 75: return DSAC_ST(2, 6, 1, true);
-        case 76: return DSAC_ST(2, 3, 1, true);
-        case 77: return DSAC_ST(1, 6, 1, true);
-        // persistent pipelined forms <16-hypothesis groups, waves per workgroup>; k2_flags bits 8..15 = workgroups per CU
-        case 60: return launch_reproject_ps<1, 4>(st, N, staged, F, clampv, err, kA, kB, soft_part, tiles_used, Nf, kf, evA, evB);
-        case 61: return launch_reproject_ps<2, 4>(st, N, staged, F, clampv, err, kA, kB, soft_part, tiles_used, Nf, kf, evA, evB);
-        case 62: return launch_reproject_ps<4, 4>(st, N, staged, F, clampv, err, kA, kB, soft_part, tiles_used, Nf, kf, evA, evB);
-        default: return hipErrorInvalidValue;
-    }
+    return hipErrorInvalidValue;  // a kernel the plan never names
 #undef DSAC_VA
 #undef DSAC_HP
 #undef DSAC_ST
+#undef DSAC_PS
+#undef DSAC_LO
+#undef DSAC_EX
+#undef DSAC_EXA
 }
 
 // --------------------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "k2_plan.h"
 
 namespace dk {
 
@@ -59,45 +60,18 @@ bool pose_split_available(const FrameDev& F);
 hipError_t pose_prep_split(hipStream_t st, int N, const double* poses, const FrameDev& F, void* split, int Nf = 0);
 
 // K2.  err (N x P) and/or soft partials.  soft_part must hold reproject_num_pixel_tiles(P) * N floats.
-// Launch knobs of K2; they live in the context (read once from the environment in dsac_create), never in process-wide state.
-struct K2Opts {
-    bool pixel_minor = true;  // block order: pixel tiles innermost (DSAC_K2_ORDER)
-    int flags = 0;            // bit0: plain (cached) stores instead of non-temporal (DSAC_K2_FLAGS)
-    int variant = -1;         // -1 = auto policy, otherwise a fixed kernel form (DSAC_K2_VARIANT), see reproject()
-    bool exact_auto = true;   // "k2_exact_auto" (DSAC_K2_EXACT_AUTO): the auto policy (variant -1, no other arithmetic flag) takes the exact-transform form wherever it
-                              // applies -- round 6: the default K2 is the form that holds every stated tolerance; 0 = the fp32 matrix-core forms
-    int diag = 0;             // "k2_diag": diagnostic switches of the precise form (which fp32 step costs what; k_reproject_prec), 0 = none
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // per call: timing events attached to the K2 dispatch itself (profiling), else null
-    const float* staged_lo = nullptr;  // per call: the low parts of the staged records (pose_prep_lo), for flags bit 27
-    const void* split = nullptr;      // per call: the split fp16 records (pose_prep_split), for flags bit 28
-    const double* poses64 = nullptr;  // per call: the cv poses (N x 6 doubles) the staged records were made from -- the precise form (flags bit 25) works from these
-    int* report = nullptr;            // per call: int[2] that receives the arithmetic form of the launch (K2_FORM_*) and why it is not the exact one (K2_WHY_*)
-    int err_elem = 0;                 // per call: element type of `err` (K2_ELEM_*); K2_ELEM_F16 / K2_ELEM_BF16: `err` points to N x P IEEE binary16 / bfloat16 (the exact vector build only, P % 8 == 0)
-    int f16_store = 1;                // "k2_f16_store": store layout of both 16-bit builds (binary16 and bfloat16): 0 = four 8-byte stores per lane and chunk, 1 (default: 882 against 892 us at the
-                                      // bench shape, profiles/k2_f16_ab.txt) = two 16-byte stores after a lane exchange
+// The knobs (K2Opts), the flags and the decision which kernel runs (k2_plan) are in k2_plan.h; reproject() enqueues the kernel of a plan whose status is
+// K2_STATUS_OK and decides nothing.  N, F, err and soft_part are the ones the plan was made for (soft_part non-NULL exactly when the plan writes sums).
+// What a launch is handed per call: the records the plan names, the cv poses, the timing events, "k2_diag"
+struct K2Call {
+    const float* staged_lo = nullptr;  // the low parts of the staged records (pose_prep_lo), where the plan says need_lo
+    const void* split = nullptr;       // the split fp16 records (pose_prep_split), where the plan says need_split
+    const double* poses64 = nullptr;   // the cv poses (N x 6 doubles) the staged records were made from -- the precise form works from these
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // timing events attached to the K2 dispatch itself (profiling), else null
+    int diag = 0;
 };
-enum { K2_ELEM_F32 = 0, K2_ELEM_F16 = 1, K2_ELEM_BF16 = 2 };
-constexpr int K2_FLAG_RECLO = 1 << 27;    // k2_flags: pose records in two pieces -- the low parts through fp16 matrix-core instructions chained onto the fp32 ones
-constexpr int K2_FLAG_STORE_ONLY = 1 << 1;  // k2_flags: store schedule only (measurement)
-constexpr int K2_FLAG_EXACT = 1 << 28;    // k2_flags: exact transform -- split fp16 records through the fp16 matrix core, the camera-frame point rounded to float once (round 6)
-constexpr int K2_FLAG_PRECISE = 1 << 25;  // k2_flags: the fp64 projection of the reference (k_reproject_prec) instead of the fp32 matrix-core transform
-constexpr int K2_FLAG_EXACT_ANY = 1 << 29;  // k2_flags: the exact transform on whatever build fits the map (vector or any-map); an error only where the focal length rules the split records out
-// what a launch computed with (dsac_get_option "k2_form_last"; the values of enum dsac_k2_form) and why it was not the exact form ("k2_form_why_last")
-enum { K2_FORM_NONE = 0, K2_FORM_FP32_VALU = 1, K2_FORM_FP32_MFMA = 2, K2_FORM_RECLO = 3, K2_FORM_EXACT_VEC = 4, K2_FORM_EXACT_ANY = 5, K2_FORM_PRECISE = 6 };
-enum { K2_WHY_AUTO_OFF = 1, K2_WHY_FORCED = 2, K2_WHY_FOCAL = 4, K2_WHY_NO_POSES = 8 };
-// does a K2 launch with these options want the split records?  (bits 28 / 29 ask for them; the auto policy wants them unless another arithmetic form or a measurement flag is set)
-inline bool k2_wants_exact(const K2Opts& o) {
-    if (o.flags & (K2_FLAG_EXACT | K2_FLAG_EXACT_ANY)) return true;
-    return o.exact_auto && o.variant < 0 && !(o.flags & (K2_FLAG_PRECISE | K2_FLAG_RECLO | K2_FLAG_STORE_ONLY | (1 << 26)));
-}
-int reproject_num_pixel_tiles(int P);  // upper bound over both code paths
-// *tiles_used receives the number of pixel tiles actually written to soft_part (<= reproject_num_pixel_tiles).
-// Nf: hypotheses per frame of a frame batch (hypothesis h scores frame h / Nf; Nf must be a multiple of K2_NF_MULTIPLE = 128 then: no
-// hypothesis tile of any kernel form may straddle two frames); 0 = one frame.
-constexpr int K2_NF_MULTIPLE = 128;
-bool reproject_variant_known(int variant);  // -1 (auto) or a value reproject() has a kernel form for
-hipError_t reproject(hipStream_t st, int N, const float* staged, const FrameDev& F, float clampv, float* err, float tau, float beta,
-                     float* soft_part, const K2Opts& opts, int* tiles_used, int Nf = 0);
+hipError_t reproject(hipStream_t st, const K2Plan& plan, int N, const float* staged, const FrameDev& F, float clampv, float* err, float tau, float beta,
+                     float* soft_part, const K2Call& call);
 // soft[h] = sum over pixel tiles of soft_part[tile][h]   (double, deterministic)
 hipError_t reduce_soft(hipStream_t st, int N, int tiles, const float* soft_part, double* soft);
 // what the exact form degrades on (dsac_k2_range_census): out[0] += 64-cell chunks of the frame(s) with a coordinate outside the split's range (split_B's

@@ -75,11 +75,16 @@ int main(int argc, char** argv) {
     hipEvent_t ea, eb; CK(hipEventCreate(&ea)); CK(hipEventCreate(&eb));
     hipEvent_t da = nullptr, db = nullptr;  // when set: timing events attached to the K2 dispatch itself, as dsac_profile_enable does
     auto run = [&](int variant, int flags, float* err, double* soft) {
-        dk::K2Opts o; o.variant = variant; o.flags = flags; o.pixel_minor = true;
-        o.ev_start = da; o.ev_stop = db;
-        int used = 0;
-        if (flags & 64) { err = nullptr; o.flags &= ~64; }  // arithmetic only: soft sums without the error-image output
-        hipError_t e = dk::reproject(st, N, d_staged, F, 100.f, err, 10.f, 0.5f, d_part, o, &used, frames > 1 ? Nf : 0);
+        dk::K2PlanIn in;  // staged records only, no cv poses: the fp32 forms
+        in.o.variant = variant; in.o.flags = flags; in.o.pixel_minor = true;
+        if (flags & 64) { err = nullptr; in.o.flags &= ~64; }  // arithmetic only: soft sums without the error-image output
+        in.N = N; in.Nf = frames > 1 ? Nf : 0; in.frames = frames; in.P = P; in.W = W; in.poses = false;
+        in.want_err = err != nullptr; in.want_soft = true;
+        const dk::K2Plan plan = dk::k2_plan(in);
+        dk::K2Call call;
+        call.ev_start = da; call.ev_stop = db;
+        const int used = plan.tiles;
+        hipError_t e = dk::reproject(st, plan, N, d_staged, F, 100.f, err, 10.f, 0.5f, d_part, call);
         if (e != hipSuccess) { printf("variant %d: %s\n", variant, hipGetErrorString(e)); exit(1); }
         if (soft) CK(dk::reduce_soft(st, N, used, d_part, soft));
     };
