@@ -26,6 +26,8 @@ constexpr int K2_FLAG_REC32 = 1 << 26;    // k2_flags: the precise form on fp32 
 constexpr int K2_FLAG_RECLO = 1 << 27;    // k2_flags: pose records in two pieces -- the low parts through fp16 matrix-core instructions chained onto the fp32 ones
 constexpr int K2_FLAG_EXACT = 1 << 28;    // k2_flags: exact transform -- split fp16 records through the fp16 matrix core, the camera-frame point rounded to float once (round 6)
 constexpr int K2_FLAG_EXACT_ANY = 1 << 29;  // k2_flags: the exact transform on whatever build fits the map (vector or any-map); an error only where the focal length rules the split records out
+constexpr int K2_FLAG_GENERAL_PATH = 1 << 30;  // k2_flags: the exact vector builds take their general path on every tile, never the full-tile path (measurement: the A/B of the
+                                                // two paths in one process); no part of the decision -- the form, the kernel and every result are the same with and without it
 // what a launch computed with (dsac_get_option "k2_form_last"; the values of enum dsac_k2_form) and why it was not the exact form ("k2_form_why_last")
 enum { K2_FORM_NONE = 0, K2_FORM_FP32_VALU = 1, K2_FORM_FP32_MFMA = 2, K2_FORM_RECLO = 3, K2_FORM_EXACT_VEC = 4, K2_FORM_EXACT_ANY = 5, K2_FORM_PRECISE = 6 };
 enum { K2_WHY_AUTO_OFF = 1, K2_WHY_FORCED = 2, K2_WHY_FOCAL = 4, K2_WHY_NO_POSES = 8 };
@@ -45,7 +47,7 @@ enum { K2_EXONLY_OK = 0, K2_EXONLY_VARIANT = 1, K2_EXONLY_FLAGS = 2, K2_EXONLY_A
 inline int k2_exact_only(int variant, int flags, bool exact_auto) {
     const int ex_bits = K2_FLAG_EXACT | K2_FLAG_EXACT_ANY;
     if (variant != -1) return K2_EXONLY_VARIANT;
-    if (flags & ~ex_bits) return K2_EXONLY_FLAGS;
+    if (flags & ~(ex_bits | K2_FLAG_GENERAL_PATH)) return K2_EXONLY_FLAGS;  // the path knob selects no other form
     if (!exact_auto && !(flags & ex_bits)) return K2_EXONLY_AUTO_OFF;
     return K2_EXONLY_OK;
 }

@@ -793,7 +793,19 @@ typedef f4 f4_a4 __attribute__((aligned(4)));
 // BF: the values are rounded to bfloat16 instead (k_reproject_st<.., EXF = 5 / 6>, dsac_reproject_bf16) -- only the packing of two floats into a dword differs; the
 // lane exchange and the stores move packed dwords and are the same code
 typedef unsigned u2v __attribute__((ext_vector_type(2)));
-template <int LAYOUT, bool BF = false>
+// The stores of a chunk in the full-tile path stand between two scheduling fences, with four idle cycles behind the last one, so that no vector instruction
+// WRITES a store's data register right behind the store.  Observed on MI355X (the <64, 64> tile, 64 x 640x480): with `buffer_store_dwordx4 v[32:35], .., s41 offen`
+// followed at once by `v_mov_b32 v32, ..` (the partial sums taking over the row's registers) the stored row held the NEW v32 in lanes 12-15 of every row of 16,
+// in a few chunks per launch and other ones every run; with the fence, never.  Supposed, not proven: the store reads its data over several cycles.  The
+// compiler's hazard table (one idle cycle behind a store of more than 8 bytes) exempts the buffer form with a scalar row offset as free of the hazard, and the
+// general path runs with such writes one and two cycles behind 16-bit stores without a failing test ("Wrong rows in the first build").
+DM_INLINE void k2_stores_begin() { __builtin_amdgcn_sched_barrier(0); }
+DM_INLINE void k2_stores_end() {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_nop 3");
+    __builtin_amdgcn_sched_barrier(0);
+}
+template <int LAYOUT, bool BF = false, bool FENCE = false>
 DM_INLINE void store_rows_h16(_Float16* base, const f4 (&ev)[4], int P, int p0, int g, int c, bool full, int rows) {
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0xffffffffu, 0x00020000);
     unsigned pk[4][2];
@@ -802,8 +814,10 @@ DM_INLINE void store_rows_h16(_Float16* base, const f4 (&ev)[4], int P, int p0, 
     if constexpr (LAYOUT == 1) {
         const unsigned loff = ((unsigned)(4 * g) * (unsigned)P + (unsigned)p0) * 2u;
         if (full) {
+            if (FENCE) k2_stores_begin();
 #pragma unroll
             for (int r = 0; r < 4; r++) __builtin_amdgcn_raw_buffer_store_b64(u2v{pk[r][0], pk[r][1]}, rsrc, loff, (unsigned)r * (unsigned)P * 2u, 2);
+            if (FENCE) k2_stores_end();
         } else {
 #pragma unroll
             for (int r = 0; r < 4; r++)
@@ -822,14 +836,19 @@ DM_INLINE void store_rows_h16(_Float16* base, const f4 (&ev)[4], int P, int p0, 
         const int r0 = odd ? 2 : 0;  // this lane's rows: r0, r0 + 1
         const unsigned loff = ((unsigned)(4 * g + r0) * (unsigned)P + (unsigned)(p0 & ~7)) * 2u;
         if (full) {
+            if (FENCE) k2_stores_begin();
             __builtin_amdgcn_raw_buffer_store_b128(ra, rsrc, loff, 0u, 2);
             __builtin_amdgcn_raw_buffer_store_b128(rb, rsrc, loff, (unsigned)P * 2u, 2);
+            if (FENCE) k2_stores_end();
         } else {
             if (r0 < rows) __builtin_amdgcn_raw_buffer_store_b128(ra, rsrc, loff, 0u, 2);
             if (r0 + 1 < rows) __builtin_amdgcn_raw_buffer_store_b128(rb, rsrc, loff, (unsigned)P * 2u, 2);
         }
     }
 }
+// The immediate of s_waitcnt on gfx9 for "at most n vector memory operations (loads AND stores: one counter) in flight", the other counters not waited for:
+// vmcnt[3:0] in bits 3:0, vmcnt[5:4] in bits 15:14; expcnt (bits 6:4) and lgkmcnt (bits 11:8) at their maxima
+constexpr int k2_vmcnt_imm(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0f70; }
 template <int NG, int CHW, int WAVES, bool PW, bool ERR, bool SOFT, bool UV, bool G64, int MINW, bool LO = false, int EXF = 0, int ANY = 0>
 __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* __restrict__ staged, const float* __restrict__ xyz,
                                                              const float* __restrict__ uv, float* __restrict__ err,
@@ -1011,6 +1030,86 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* 
                 ppix[ch * pc][m] = f2{(float)x - cx, (float)y - cy};
                 if (++x == W) { x = 0; y++; }
             }
+        }
+    }
+
+    // The full-tile path: the one-transcendental exact vector builds on the implicit grid (the auto policy's kernels for W % 64 == 0, the bench shape among
+    // them).  One wave-uniform test picks it: a whole hypothesis tile, every chunk inside the map, no chunk with a coordinate beyond the split's range;
+    // k2_flags bit 30 sends every tile down the general path below (the A/B knob).  The calls, their order and operands, the loop nest and the stores are the
+    // general path's.  What is left out is every branch the compiler's wait-count analysis cannot follow: the exec-masked skips around a chunk body and its
+    // stores (valid[ch], the row guards) and the far-coordinate cold path, which issues loads of its own and comes back by a backward branch.  Over those
+    // joins the analysis keeps, for every operand register, the fewest younger memory operations of any path, and loads and stores share one counter: in
+    // the general path every chunk top waits until at most 6 (in the last group: none) of the wave's own stores are in flight, for operands that landed
+    // long before.  Here the only waits on that counter are the counted ones, which the analysis takes over.
+    // (The other exact builds keep the general path alone: with a second path the sampled-position builds, the reciprocal tail and the four-waves-per-SIMD
+    // tile spill 50-330 bytes per lane.)
+    if constexpr (EXF >= 2 && ANY == 0 && !LO && G64 && !UV && PW && MINW <= 3) {
+        bool far = false;
+#pragma unroll
+        for (int ch = 0; ch < CHW; ch++) far = far || oor[ch];
+        if (nh == HT && (chunk0 + CHW) * 64 <= P && !far && !(kflags & K2_FLAG_GENERAL_PATH)) {
+            // error-image stores of one group: what is certainly issued between the fetch of a group's operands and their first use (the four partial-sum
+            // stores of the lanes c == 0 sit under a branch and do not count)
+            constexpr int GRP_STORES = ERR ? CHW * (H16 == 2 ? 2 : 4) : 0;
+            // end of the prologue: every load so far (coordinates, the first group's operands), before the first store -- the first MFMA waits for them anyway
+            __builtin_amdgcn_s_waitcnt(k2_vmcnt_imm(0));  // 0x0f70: vmcnt(0)
+#pragma unroll
+            for (int gi = 0; gi < NG; gi++) {
+                // group top: the operands fetched one group ahead
+                if (A_AHEAD && gi > 0) {
+                    __builtin_amdgcn_s_waitcnt(k2_vmcnt_imm(GRP_STORES));  // 16 stores: 0x4f70 = vmcnt(16); 8: 0x0f78; 4: 0x0f74; 2: 0x0f72; none: 0x0f70
+                    // the operands pass through here: no MFMA of the group is scheduled in front of the wait (it would get a wait of its own)
+                    asm volatile("" : "+v"(aex[gi].cx), "+v"(aex[gi].cy), "+v"(aex[gi].cz), "+v"(aex[gi].hx), "+v"(aex[gi].hy), "+v"(aex[gi].hz));
+                }
+                if (A_AHEAD && gi + 1 < NG) {
+                    asm volatile("" ::: "memory");
+                    load_A(gi + 1);
+                }
+                const int hyp0 = 16 * gi + 4 * g;
+                f2 ssum[4] = {splat(0.f), splat(0.f), splat(0.f), splat(0.f)};
+#pragma unroll
+                for (int ch = 0; ch < CHW; ch++) {
+                    f4 ev[4];
+                    f2 sloc[4];
+                    f2 pb = f2{(float)(sx0[ch] + 4 * c) - cx, sby[ch]};
+                    asm volatile("" : "+v"(pb));
+#pragma unroll
+                    for (int m = 0; m < 4; m++) ppix[0][m] = f2{pb.x + (float)m, pb.y};
+                    // the exact-z redo: arithmetic only
+                    if (__builtin_expect(__any(hp_chunk_ex<false, SOFT, RSQ>(aex[gi], B8[ch], ppix[0], clampv, kA, kB, ev, sloc)), 0)) {
+                        (void)hp_chunk_ex<true, SOFT>(aex[gi], B8[ch], ppix[0], clampv, kA, kB, ev, sloc);
+                    }
+                    if (SOFT) {
+                        const f2 vf = splat(1.0f);
+#pragma unroll
+                        for (int r = 0; r < 4; r++) ssum[r] = pk_fma(sloc[r], vf, ssum[r]);
+                    }
+                    if constexpr (H16 != 0) {
+                        store_rows_h16<H16, BF16, true>(reinterpret_cast<_Float16*>(err) + (size_t)(h0 + 16 * gi) * P, ev, P, p0[ch], g, c, true, 4);
+                    } else if (ERR) {
+                        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(err + (size_t)(h0 + 16 * gi) * P, 0, 0xffffffffu, 0x00020000);
+                        const unsigned loff = ((unsigned)(4 * g) * (unsigned)P + (unsigned)p0[ch]) * 4u;
+                        k2_stores_begin();
+#pragma unroll
+                        for (int r = 0; r < 4; r++) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, ev[r]), rsrc, loff, (unsigned)r * (unsigned)P * 4u, 2);
+                        k2_stores_end();
+                    }
+                    if (ERR && !SOFT) {  // the pacing knobs of the error-images-only builds (k2_flags bits 16-23)
+                        const int ps = (kflags >> 16) & 15, pn = (kflags >> 20) & 15;
+                        for (int i = 0; i < ps; i++) __builtin_amdgcn_s_sleep(1);
+                        for (int i = 0; i < pn; i++) asm volatile("s_nop 15");
+                    }
+                }
+                if (SOFT) {
+                    const float s0 = row16_sum(ssum[0].x + ssum[0].y), s1 = row16_sum(ssum[1].x + ssum[1].y);
+                    const float s2 = row16_sum(ssum[2].x + ssum[2].y), s3 = row16_sum(ssum[3].x + ssum[3].y);
+                    if (c == 0) {
+                        float* dst = soft_part + (size_t)(pt * WAVES + wave) * N + h0 + hyp0;
+                        dst[0] = s0; dst[1] = s1; dst[2] = s2; dst[3] = s3;
+                    }
+                }
+            }
+            return;
         }
     }
 

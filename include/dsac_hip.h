@@ -122,6 +122,11 @@ DSAC_API int dsac_device_info(dsac_ctx* ctx, int* cus, int* clock_khz, uint64_t*
  *                 dsac_k2_range_census counts them): the any-map build sends the group of 16 hypotheses that holds one through the fp32 transform, as
  *                 chunks of far coordinates go in both builds; the vector build does NOT (its results are unchanged), so on a vector-readable map such a
  *                 hypothesis still misses 1e-3 px, and those 16 rows differ between an aligned buffer and a slice of it
+ *                 bit 30 (0x40000000): GENERAL PATH FOR EVERY TILE (measurement) -- the exact vector builds choose per tile between a full-tile path (a whole
+ *                 hypothesis tile, every chunk inside the map, no coordinate beyond +-65.5 m: no guard around a chunk or its stores, counted waits on the
+ *                 memory counter) and the general path that ragged tiles, the map's last tile and tiles with a far chunk take; with this bit every tile takes
+ *                 the general path.  Same kernel, same form, the same bits in every output: the A/B of the two paths in one process.  Selects no form, and is
+ *                 the one bit beside 28 / 29 that the 16-bit error images and per-frame cameras accept
  *   "k2_exact_auto"  1 (default since round 6): the auto policy (k2_variant -1, none of the bits 1 / 25 / 26 / 27 set) launches the exact-transform form on every
  *                 frame with a focal length <= 1 024 px, whatever the shape of the map or the alignment of its buffers (the vector build or the any-map build,
  *                 see bit 29) -- the library's default K2 holds every stated tolerance for poses inside the split records' range (see bit 29: on vector-readable maps a
