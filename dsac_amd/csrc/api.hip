@@ -113,6 +113,7 @@ struct dsac_ctx {
     struct Pending { void* host; const void* dev; size_t bytes; };
     std::vector<Pending> pending;
     dk::K2Opts k2;  // launch knobs, read once in dsac_create (DSAC_K2_*) or set with dsac_set_option; no process-wide state
+    int k2_walk_last = 0;     // the hypothesis walk of that launch (dsac_get_option "k2_hyp_walk_last"; 0 before the first launch)
     int k2_last[2] = {0, 0};  // the arithmetic form of the last K2 launch this context enqueued and why it was not the exact one (dsac_get_option "k2_form_last" / "k2_form_why_last")
     dk::K1Opts k1;
     int k1_cus = 0;       // > 0: the auxiliary stream of the pipelined pair (K1 of the next step) is confined to that many CUs (DSAC_K1_CUS / "k1_cus")
@@ -358,6 +359,7 @@ int k2_stage(dsac_ctx* c, hipStream_t st, int N, int Nf, const float* staged, co
     ps.commit();
     c->k2_last[0] = plan.form;
     c->k2_last[1] = plan.why;
+    c->k2_walk_last = plan.hyp_walk;
     if (gated && c->k2_record) HIP_TRY(c, hipEventRecord(c->k2_record, st));
     return DSAC_OK;
 }
@@ -651,6 +653,7 @@ int dsac_create(dsac_ctx** out, int device) {
     if (const char* v = getenv("DSAC_K2_ORDER")) c->k2.pixel_minor = atoi(v) != 0;
     if (const char* v = getenv("DSAC_K2_FLAGS")) c->k2.flags = atoi(v);
     if (const char* v = getenv("DSAC_K2_EXACT_AUTO")) c->k2.exact_auto = atoi(v) != 0;
+    if (const char* v = getenv("DSAC_K2_HYP_WALK")) { const int w = atoi(v); if (w == 1 || w == 2 || w == 4) c->k2.hyp_walk = w; }
     if (const char* v = getenv("DSAC_K1_WPB")) c->k1.wpb = atoi(v);
     if (const char* v = getenv("DSAC_K1_PRIO")) c->k1.prio = atoi(v);
     if (const char* v = getenv("DSAC_K1_HPW")) c->k1.hpw = atoi(v);
@@ -1473,6 +1476,10 @@ int dsac_set_option(dsac_ctx* c, const char* key, int value) {
         if (value != 0 && value != 1) return fail(c, DSAC_ERR_INVALID, "dsac_set_option: k2_f16_store (both 16-bit builds, binary16 and bfloat16) is 0 (8-byte stores) or 1 (16-byte stores after a lane exchange)");
         c->k2.f16_store = value;
     }
+    else if (k == "k2_hyp_walk") {
+        if (value != 0 && value != 1 && value != 2 && value != 4) return fail(c, DSAC_ERR_INVALID, "dsac_set_option: k2_hyp_walk is 0 (auto), 1, 2 or 4 hypothesis tiles per workgroup");
+        c->k2.hyp_walk = value;
+    }
     else if (k == "k6_walk_exact") c->k6_walk_exact = value != 0;
     else if (k == "k6_scan_tune") {  // A/B of the scan (process-wide): problems per wave | chunk cells << 8 | no skip check << 24
         const int g = value & 255, chunk = (value >> 8) & 0xffff;
@@ -1551,6 +1558,8 @@ int dsac_get_option(dsac_ctx* c, const char* key, int* value) {
     else if (k == "k2_diag") *value = c->k2.diag;
     else if (k == "k2_exact_auto") *value = c->k2.exact_auto ? 1 : 0;
     else if (k == "k2_f16_store") *value = c->k2.f16_store;
+    else if (k == "k2_hyp_walk") *value = c->k2.hyp_walk;
+    else if (k == "k2_hyp_walk_last") *value = c->k2_walk_last;
     else if (k == "k6_walk_exact") *value = c->k6_walk_exact;
     else if (k == "k6_scan_tune") *value = dk::refine_scan_tune_get();
     else if (k == "k6_waves") *value = c->k6_waves;

@@ -17,6 +17,8 @@ struct K2Opts {
     int diag = 0;             // "k2_diag": diagnostic switches of the precise form (which fp32 step costs what; k_reproject_prec), 0 = none; no part of the decision
     int f16_store = 1;        // "k2_f16_store": store layout of both 16-bit builds (binary16 and bfloat16): 0 = four 8-byte stores per lane and chunk, 1 (default: 882 against 892 us at the
                               // bench shape, profiles/k2_f16_ab.txt) = two 16-byte stores after a lane exchange
+    int hyp_walk = 0;         // "k2_hyp_walk": hypothesis tiles a workgroup of the full-tile builds scores on its pixel tile: 0 = auto (k2_hyp_walk), 1 / 2 / 4 = that many
+                              // wherever the kernel has the walk and no walk would straddle a frame or the end of N
 };
 enum { K2_ELEM_F32 = 0, K2_ELEM_F16 = 1, K2_ELEM_BF16 = 2 };
 constexpr int K2_FLAG_STORE_ONLY = 1 << 1;  // k2_flags: store schedule only (measurement)
@@ -33,6 +35,7 @@ enum { K2_FORM_NONE = 0, K2_FORM_FP32_VALU = 1, K2_FORM_FP32_MFMA = 2, K2_FORM_R
 enum { K2_WHY_AUTO_OFF = 1, K2_WHY_FORCED = 2, K2_WHY_FOCAL = 4, K2_WHY_NO_POSES = 8 };
 // Nf of a frame batch must be a multiple of this: no hypothesis tile of any kernel form (<= 128 hypotheses) may straddle two frames
 constexpr int K2_NF_MULTIPLE = 128;
+constexpr int K2_KFLAG_WALK_SHIFT = 6;  // the kernels' flag bits 6-7: log2 of the plan's hyp_walk, put there by dk::reproject (never taken from "k2_flags")
 constexpr int K2_WG = 256;  // threads per workgroup of the VALU, matrix-core and precise kernels (K2_THREADS)
 
 // does a K2 launch with these options want the split records?  (bits 28 / 29 ask for them; the auto policy wants them unless another arithmetic form or a measurement flag is set)
@@ -217,7 +220,44 @@ struct K2Plan {
     bool pixel_minor = true;    // block order of the VALU / matrix-core forms
     int Nf = 0;                 // as the kernels take it: one frame = N rounded up to 128 (every tile maps to frame 0)
     int tiles = 0;              // rows of soft_part the launch writes
+    int hyp_walk = 1;           // consecutive hypothesis tiles of one frame a workgroup scores on its pixel tile (1, 2 or 4): the grid has that many times fewer workgroups
 };
+
+// ---- the hypothesis walk ---------------------------------------------------------------------------------------------------------------------------------
+// The exact vector builds with a full-tile path (k_reproject_st: tail 2 or a 16-bit store, per-wave sums, at most 3 waves per SIMD, the implicit grid with
+// W % 64 == 0) can score 2 or 4 consecutive hypothesis tiles of one frame per workgroup: the pixel tile's coordinates are loaded and split once per walk.
+// Every (hypothesis, cell) is computed and stored exactly as with a walk of 1.
+//   legal: no walk straddles the end of N or a frame -- N, and Nf of a frame batch, are multiples of the walk's hypotheses; else the next smaller length
+//   "k2_hyp_walk" 1 / 2 / 4: that length where the kernel has the walk and it is legal
+//   auto (0): only the regime of the <64, 256> tile at two waves per SIMD on more than K2_BIG_BYTES of error images (float-sized, whichever outputs are asked
+//   for), and only while the launch is still K2_WALK_MIN_GENERATIONS fills of the chip's K2_WAVE_SLOTS wave slots: a walk of 4 on one frame of 256
+//   hypotheses would be 0.6 fills of four-times-longer waves instead of 2.3 (measured: 88 against 61 us).  There the length is K2_WALK_AUTO, the fastest measured
+//   at the bench shape, 16 x 256 x 640x480: K2 896 us at 4 and 900 at 2 against 920 at 1 (medians, profiles/k2_walk_path_ab.txt); bench.py's step 990.5-994.2 us
+//   against the parent's 1 019.9-1 022.5, nine alternating runs each (profiles/k2_walk_bench_ab.txt)
+constexpr int K2_WALK_AUTO = 4;
+constexpr int K2_WAVE_SLOTS = 256 * 4 * 2;  // MI355X: 256 CUs x 4 SIMDs x the two waves per SIMD of the <64, 256> build
+constexpr int K2_WALK_MIN_GENERATIONS = 8;  // the last, partly filled generation is then at most an eighth of the launch
+inline bool k2_has_walk(const K2PlanIn& in, const K2Kernel& k) {
+    return k.family == K2_FAM_EXACT_VEC && k.exf >= 2 && k.pw && k.wv == 1 && k.minw <= 3 && !in.uv && (in.W & 63) == 0;
+}
+inline bool k2_walk_legal(const K2PlanIn& in, const K2Kernel& k, int walk) {
+    const int hyps = 16 * k.ng * walk;
+    return in.N % hyps == 0 && (in.frames <= 1 || in.Nf <= 0 || in.Nf % hyps == 0);
+}
+// the hypothesis dimension of the streaming builds' grid: walks of `walk` tiles of 16 ng hypotheses (launch_reproject_st multiplies by the pixel tiles)
+inline int k2_walks(int N, int ng, int walk) { return k2_ceil_div(k2_ceil_div(N, 16 * ng), walk); }
+inline int k2_hyp_walk(const K2PlanIn& in, const K2Kernel& k) {
+    if (!k2_has_walk(in, k)) return 1;
+    int walk = in.o.hyp_walk;
+    if (walk <= 0) {
+        walk = K2_WALK_AUTO;
+        if (!(k.ch == 4 && k.minw == 2 && k2_err_bytes(in.N, in.P) > K2_BIG_BYTES)) walk = 1;
+        const long long wgs = (long long)k2_ceil_div(in.N, 16 * k.ng) * k2_ceil_div(in.P, 64 * k.ch);
+        while (walk > 1 && wgs / walk < (long long)K2_WALK_MIN_GENERATIONS * K2_WAVE_SLOTS) walk >>= 1;
+    }
+    while (walk > 1 && !k2_walk_legal(in, k, walk)) walk >>= 1;
+    return walk;
+}
 
 inline K2Plan k2_plan(const K2PlanIn& in) {
     K2Plan p;
@@ -308,6 +348,7 @@ inline K2Plan k2_plan(const K2PlanIn& in) {
     }
     p.why = (p.form == K2_FORM_EXACT_VEC || p.form == K2_FORM_EXACT_ANY) ? 0 : why;
     p.tiles = k2_tiles(p.k, in.P, soft);
+    p.hyp_walk = k2_hyp_walk(in, p.k);
     return p;
 }
 

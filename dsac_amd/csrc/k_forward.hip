@@ -881,8 +881,13 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* 
         pt = (q % PTG) * 8 + (b & 7);
         if (pt >= PT) return;
     }
-    const int h0 = ht * HT;
-    const int nh = min(HT, N - h0);
+    // The hypothesis walk (k2_plan.h, K2Plan::hyp_walk; k2_flags bits 6-7 hold its log2, set by dk::reproject alone): the builds with the full-tile path score
+    // HB consecutive hypothesis tiles of one frame on the workgroup's pixel tile -- the coordinate loads, their fp16 split and the prologue's wait happen once
+    // per walk.  `ht` counts walks; the plan allows HB > 1 only where every tile of every walk is whole and no walk straddles a frame.  Every other build: HB = 1
+    constexpr bool FULL_TILE = EXF >= 2 && ANY == 0 && !LO && G64 && !UV && PW && MINW <= 3;
+    const int HB = FULL_TILE ? 1 << ((kflags >> K2_KFLAG_WALK_SHIFT) & 3) : 1;
+    int h0 = ht * HT * HB;
+    int nh = min(HT, N - h0);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 15, g = lane >> 4;
@@ -962,21 +967,24 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* 
     float ax[EX ? 1 : NG], ay[EX ? 1 : NG], az[EX ? 1 : NG];
     LoOps alo[LO ? NG : 1];
     ExOps aex[EX ? NG : 1];
+    // lh, lc: the first hypothesis of the tile load_A fetches for and the lane's column -- h0 and c, but where the walk of the full-tile builds passes copies of
+    // them through an empty asm: no operand address then lives across the tiles as an induction variable (vector registers the <64, 256> builds do not have)
+    int lh = h0, lc = c;
     auto load_A = [&](int gi) {
-        const int hyp = min(16 * gi + c, nh - 1);  // beyond the ragged end: repeat the last valid hypothesis (never stored)
+        const int hyp = min(16 * gi + lc, nh - 1);  // beyond the ragged end: repeat the last valid hypothesis (never stored)
         if (EX) {
             // the split records in the matrix core's lane layout: quarter g of rows x, y, z of hypothesis c -- 16 bytes (K = 32 operand) + 8 bytes (K = 16) each
-            const h8* rc = reinterpret_cast<const h8*>(split) + (size_t)(h0 + hyp) * 12 + g;
-            const h4* rh = reinterpret_cast<const h4*>(reinterpret_cast<const char*>(split) + (size_t)N * SPLIT_CROSS_BYTES) + (size_t)(h0 + hyp) * 12 + g;
+            const h8* rc = reinterpret_cast<const h8*>(split) + (size_t)(lh + hyp) * 12 + g;
+            const h4* rh = reinterpret_cast<const h4*>(reinterpret_cast<const char*>(split) + (size_t)N * SPLIT_CROSS_BYTES) + (size_t)(lh + hyp) * 12 + g;
             aex[gi].cx = rc[0]; aex[gi].cy = rc[4]; aex[gi].cz = rc[8];
             aex[gi].hx = rh[0]; aex[gi].hy = rh[4]; aex[gi].hz = rh[8];
             return;
         }
-        const float* rec = staged + (size_t)(h0 + hyp) * POSE_STRIDE + g;
+        const float* rec = staged + (size_t)(lh + hyp) * POSE_STRIDE + g;
         ax[gi] = rec[0]; ay[gi] = rec[4]; az[gi] = rec[8];
         if (LO) {
             // the records' low parts x 2^16 (x and y rows negated like the high parts), k = 0..3 of hypothesis c in the lanes of row 0
-            const f4* rl = reinterpret_cast<const f4*>(staged_lo + (size_t)(h0 + hyp) * POSE_STRIDE);
+            const f4* rl = reinterpret_cast<const f4*>(staged_lo + (size_t)(lh + hyp) * POSE_STRIDE);
             const float S = (g == 0) ? 65536.f : 0.f, T = (g == 0) ? 256.f : 0.f;  // rotation entries x 2^16 against coordinates x 2^-16, translation x 2^8 against 2^-8
             const f4 lx = rl[0], ly = rl[1], lz = rl[2];
             alo[gi].x = h4{(_Float16)(-lx.x * S), (_Float16)(-lx.y * S), (_Float16)(-lx.z * S), (_Float16)(-lx.w * T)};
@@ -1043,7 +1051,7 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* 
     // long before.  Here the only waits on that counter are the counted ones, which the analysis takes over.
     // (The other exact builds keep the general path alone: with a second path the sampled-position builds, the reciprocal tail and the four-waves-per-SIMD
     // tile spill 50-330 bytes per lane.)
-    if constexpr (EXF >= 2 && ANY == 0 && !LO && G64 && !UV && PW && MINW <= 3) {
+    if constexpr (FULL_TILE) {
         bool far = false;
 #pragma unroll
         for (int ch = 0; ch < CHW; ch++) far = far || oor[ch];
@@ -1053,69 +1061,96 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* 
             constexpr int GRP_STORES = ERR ? CHW * (H16 == 2 ? 2 : 4) : 0;
             // end of the prologue: every load so far (coordinates, the first group's operands), before the first store -- the first MFMA waits for them anyway
             __builtin_amdgcn_s_waitcnt(k2_vmcnt_imm(0));  // 0x0f70: vmcnt(0)
+            // The walk over the HB tiles stays ROLLED (the executed path is about 35 KB of a 64 KB instruction cache).  The fetch one group ahead carries across
+            // the tile boundary: the last group of a tile fetches the first group of the next one, and the wait for it stands at the top of the next trip -- the
+            // same count as at any group top: the fetch was issued at the top of the last group, the group's GRP_STORES error-image stores behind it
+            static_assert(A_AHEAD, "the walk fetches the next tile's first group from the last group of this one");
+#pragma unroll 1
+            for (int k = 0;; k++) {
+                // tile top: the first group's operands, fetched from the last group of the tile before (the first tile's: landed with the prologue's wait)
+                __builtin_amdgcn_s_waitcnt(k2_vmcnt_imm(GRP_STORES));
+                asm volatile("" : "+v"(aex[0].cx), "+v"(aex[0].cy), "+v"(aex[0].cz), "+v"(aex[0].hx), "+v"(aex[0].hy), "+v"(aex[0].hz));
 #pragma unroll
-            for (int gi = 0; gi < NG; gi++) {
-                // group top: the operands fetched one group ahead
-                if (A_AHEAD && gi > 0) {
-                    __builtin_amdgcn_s_waitcnt(k2_vmcnt_imm(GRP_STORES));  // 16 stores: 0x4f70 = vmcnt(16); 8: 0x0f78; 4: 0x0f74; 2: 0x0f72; none: 0x0f70
-                    // the operands pass through here: no MFMA of the group is scheduled in front of the wait (it would get a wait of its own)
-                    asm volatile("" : "+v"(aex[gi].cx), "+v"(aex[gi].cy), "+v"(aex[gi].cz), "+v"(aex[gi].hx), "+v"(aex[gi].hy), "+v"(aex[gi].hz));
-                }
-                if (A_AHEAD && gi + 1 < NG) {
-                    asm volatile("" ::: "memory");
-                    load_A(gi + 1);
-                }
-                const int hyp0 = 16 * gi + 4 * g;
-                f2 ssum[4] = {splat(0.f), splat(0.f), splat(0.f), splat(0.f)};
+                for (int gi = 0; gi < NG; gi++) {
+                    // group top: the operands fetched one group ahead
+                    if (A_AHEAD && gi > 0) {
+                        __builtin_amdgcn_s_waitcnt(k2_vmcnt_imm(GRP_STORES));  // 16 stores: 0x4f70 = vmcnt(16); 8: 0x0f78; 4: 0x0f74; 2: 0x0f72; none: 0x0f70
+                        // the operands pass through here: no MFMA of the group is scheduled in front of the wait (it would get a wait of its own)
+                        asm volatile("" : "+v"(aex[gi].cx), "+v"(aex[gi].cy), "+v"(aex[gi].cz), "+v"(aex[gi].hx), "+v"(aex[gi].hy), "+v"(aex[gi].hz));
+                    }
+                    lh = h0; lc = c;
+                    asm volatile("" : "+s"(lh), "+v"(lc));
+                    const int hk = lh;
+                    if (A_AHEAD && gi + 1 < NG) {
+                        asm volatile("" ::: "memory");
+                        load_A(gi + 1);
+                    } else if (k + 1 < HB) {  // wave-uniform: the first group of the next tile
+                        asm volatile("" ::: "memory");
+                        lh += HT;
+                        load_A(0);
+                    }
+                    const int hyp0 = 16 * gi + 4 * g;
+                    f2 ssum[4] = {splat(0.f), splat(0.f), splat(0.f), splat(0.f)};
 #pragma unroll
-                for (int ch = 0; ch < CHW; ch++) {
-                    f4 ev[4];
-                    f2 sloc[4];
-                    f2 pb = f2{(float)(sx0[ch] + 4 * c) - cx, sby[ch]};
-                    asm volatile("" : "+v"(pb));
+                    for (int ch = 0; ch < CHW; ch++) {
+                        f4 ev[4];
+                        f2 sloc[4];
+                        f2 pb = f2{(float)(sx0[ch] + 4 * c) - cx, sby[ch]};
+                        asm volatile("" : "+v"(pb));
 #pragma unroll
-                    for (int m = 0; m < 4; m++) ppix[0][m] = f2{pb.x + (float)m, pb.y};
-                    // the exact-z redo: arithmetic only
-                    if (__builtin_expect(__any(hp_chunk_ex<false, SOFT, RSQ>(aex[gi], B8[ch], ppix[0], clampv, kA, kB, ev, sloc)), 0)) {
-                        (void)hp_chunk_ex<true, SOFT>(aex[gi], B8[ch], ppix[0], clampv, kA, kB, ev, sloc);
+                        for (int m = 0; m < 4; m++) ppix[0][m] = f2{pb.x + (float)m, pb.y};
+                        // the exact-z redo: arithmetic only
+                        if (__builtin_expect(__any(hp_chunk_ex<false, SOFT, RSQ>(aex[gi], B8[ch], ppix[0], clampv, kA, kB, ev, sloc)), 0)) {
+                            (void)hp_chunk_ex<true, SOFT>(aex[gi], B8[ch], ppix[0], clampv, kA, kB, ev, sloc);
+                        }
+                        if (SOFT) {
+                            const f2 vf = splat(1.0f);
+#pragma unroll
+                            for (int r = 0; r < 4; r++) ssum[r] = pk_fma(sloc[r], vf, ssum[r]);
+                        }
+                        if constexpr (H16 != 0) {
+                            store_rows_h16<H16, BF16, true>(reinterpret_cast<_Float16*>(err) + (size_t)(h0 + 16 * gi) * P, ev, P, p0[ch], g, c, true, 4);
+                        } else if (ERR) {
+                            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(err + (size_t)(h0 + 16 * gi) * P, 0, 0xffffffffu, 0x00020000);
+                            const unsigned loff = ((unsigned)(4 * g) * (unsigned)P + (unsigned)p0[ch]) * 4u;
+                            k2_stores_begin();
+#pragma unroll
+                            for (int r = 0; r < 4; r++) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, ev[r]), rsrc, loff, (unsigned)r * (unsigned)P * 4u, 2);
+                            k2_stores_end();
+                        }
+                        if (ERR && !SOFT) {  // the pacing knobs of the error-images-only builds (k2_flags bits 16-23)
+                            const int ps = (kflags >> 16) & 15, pn = (kflags >> 20) & 15;
+                            for (int i = 0; i < ps; i++) __builtin_amdgcn_s_sleep(1);
+                            for (int i = 0; i < pn; i++) asm volatile("s_nop 15");
+                        }
                     }
                     if (SOFT) {
-                        const f2 vf = splat(1.0f);
-#pragma unroll
-                        for (int r = 0; r < 4; r++) ssum[r] = pk_fma(sloc[r], vf, ssum[r]);
-                    }
-                    if constexpr (H16 != 0) {
-                        store_rows_h16<H16, BF16, true>(reinterpret_cast<_Float16*>(err) + (size_t)(h0 + 16 * gi) * P, ev, P, p0[ch], g, c, true, 4);
-                    } else if (ERR) {
-                        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(err + (size_t)(h0 + 16 * gi) * P, 0, 0xffffffffu, 0x00020000);
-                        const unsigned loff = ((unsigned)(4 * g) * (unsigned)P + (unsigned)p0[ch]) * 4u;
-                        k2_stores_begin();
-#pragma unroll
-                        for (int r = 0; r < 4; r++) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, ev[r]), rsrc, loff, (unsigned)r * (unsigned)P * 4u, 2);
-                        k2_stores_end();
-                    }
-                    if (ERR && !SOFT) {  // the pacing knobs of the error-images-only builds (k2_flags bits 16-23)
-                        const int ps = (kflags >> 16) & 15, pn = (kflags >> 20) & 15;
-                        for (int i = 0; i < ps; i++) __builtin_amdgcn_s_sleep(1);
-                        for (int i = 0; i < pn; i++) asm volatile("s_nop 15");
+                        const float s0 = row16_sum(ssum[0].x + ssum[0].y), s1 = row16_sum(ssum[1].x + ssum[1].y);
+                        const float s2 = row16_sum(ssum[2].x + ssum[2].y), s3 = row16_sum(ssum[3].x + ssum[3].y);
+                        if (c == 0) {
+                            float* dst = soft_part + (size_t)(pt * WAVES + wave) * N + hk + hyp0;
+                            dst[0] = s0; dst[1] = s1; dst[2] = s2; dst[3] = s3;
+                        }
                     }
                 }
-                if (SOFT) {
-                    const float s0 = row16_sum(ssum[0].x + ssum[0].y), s1 = row16_sum(ssum[1].x + ssum[1].y);
-                    const float s2 = row16_sum(ssum[2].x + ssum[2].y), s3 = row16_sum(ssum[3].x + ssum[3].y);
-                    if (c == 0) {
-                        float* dst = soft_part + (size_t)(pt * WAVES + wave) * N + h0 + hyp0;
-                        dst[0] = s0; dst[1] = s1; dst[2] = s2; dst[3] = s3;
-                    }
-                }
+                if (k + 1 == HB) break;
+                h0 += HT;
             }
             return;
         }
     }
 
+    // The general path.  In the full-tile builds it runs once per tile of the walk (a partial last pixel tile, a far chunk, k2_flags bit 30), each further tile
+    // starting like the first, with the operands of its first group; every other build has one tile and no way back up here
+    [[maybe_unused]] int walked = 1;
+[[maybe_unused]] next_tile:;
 #pragma unroll
     for (int gi = 0; gi < NG; gi++) {
         if (16 * gi >= nh) break;
+        if constexpr (FULL_TILE) {  // the walk: see lh, lc
+            lh = h0; lc = c;
+            asm volatile("" : "+s"(lh), "+v"(lc));
+        }
         if (A_AHEAD && gi + 1 < NG) {
             asm volatile("" ::: "memory");  // keeps the compiler from hoisting the fetch to the top of the kernel (that is the up-front form)
             load_A(gi + 1);
@@ -1221,12 +1256,23 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void k_reproject_st(const float* 
             const float s0 = row16_sum(ssum[0].x + ssum[0].y), s1 = row16_sum(ssum[1].x + ssum[1].y);
             const float s2 = row16_sum(ssum[2].x + ssum[2].y), s3 = row16_sum(ssum[3].x + ssum[3].y);
             if (c == 0) {
-                float* dst = !PW ? s_soft + wave * HT + hyp0 : soft_part + (size_t)(pt * WAVES + wave) * N + h0 + hyp0;
+                float* dst = !PW ? s_soft + wave * HT + hyp0 : soft_part + (size_t)(pt * WAVES + wave) * N + (FULL_TILE ? lh : h0) + hyp0;
                 if (hyp0 + 0 < nh) dst[0] = s0;
                 if (hyp0 + 1 < nh) dst[1] = s1;
                 if (hyp0 + 2 < nh) dst[2] = s2;
                 if (hyp0 + 3 < nh) dst[3] = s3;
             }
+        }
+    }
+    if constexpr (FULL_TILE) {
+        static_assert(A_AHEAD, "a further tile starts with the operands of its first group alone");
+        if (walked < HB) {
+            walked++;
+            h0 += HT;
+            nh = min(HT, N - h0);
+            lh = h0;
+            load_A(0);
+            goto next_tile;
         }
     }
     if (SOFT && !PW) {
@@ -1427,11 +1473,11 @@ template <int NG, int CHW, int WAVES, bool PW, int MINW = 1, bool LO = false, in
 static hipError_t launch_reproject_st(hipStream_t st, int N, const float* staged, const FrameDev& F, float clampv, float* err, float kA, float kB,
                                       float* soft_part, int Nf, int kflags, hipEvent_t evA, hipEvent_t evB, const float* staged_lo = nullptr,
                                       const void* split = nullptr) {
-    constexpr int HT = 16 * NG;
     const int tile = WAVES * CHW * 64;
     static_assert(PW || WAVES > 1, "one-wave workgroups write per-wave partial sums");
     const int PT = (F.P + tile - 1) / tile;
-    const int NTa = (N + HT - 1) / HT;
+    // hypothesis walks (the plan's hyp_walk, in the kernel's flag bits 6-7): a workgroup scores that many tiles; the plan has made sure they divide the tiles
+    const int NTa = k2_walks(N, NG, 1 << ((kflags >> K2_KFLAG_WALK_SHIFT) & 3));
     const int grid = (kflags & 32) ? PT * NTa : WAVES == 1 ? ((PT + 31) / 32) * 32 * NTa : ((PT + 7) / 8) * 8 * NTa;
     const bool ERR = err != nullptr, SOFT = soft_part != nullptr, UV = F.uv != nullptr;
     const bool G64 = !UV && (F.W & 63) == 0;
@@ -1724,7 +1770,8 @@ hipError_t reproject(hipStream_t st, const K2Plan& plan, int N, const float* sta
     const K2Kernel& k = plan.k;
     const float LOG2E = 1.4426950408889634f;
     const float kA = beta * LOG2E, kB = -beta * tau * LOG2E;
-    const int Nf = plan.Nf, kf = plan.kflags;
+    // the kernels take the plan's hypothesis walk in flag bits 6-7 (log2); whatever "k2_flags" held there is dropped
+    const int Nf = plan.Nf, kf = (plan.kflags & ~(3 << K2_KFLAG_WALK_SHIFT)) | ((plan.hyp_walk == 4 ? 2 : plan.hyp_walk == 2 ? 1 : 0) << K2_KFLAG_WALK_SHIFT);
     const bool pm = plan.pixel_minor;
     // timing events (dsac_profile_enable): attached to the kernel's own dispatch (hipExtLaunchKernelGGL) instead of two event records on the
     // stream, which cost ~7 us of bubble each (one 640x480 frame: 100 us per step with them, 86 without)

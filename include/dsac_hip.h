@@ -132,6 +132,11 @@ DSAC_API int dsac_device_info(dsac_ctx* ctx, int* cus, int* clock_khz, uint64_t*
  *                 see bit 29) -- the library's default K2 holds every stated tolerance for poses inside the split records' range (see bit 29: on vector-readable maps a
  *                 hypothesis with a translation beyond 131 m is outside it and the census is how to find one); the fp32 forms remain for focal lengths above 1 024 px (dsac_get_option
  *                 "k2_form_last" tells); 0: the fp32 forms of rounds 2-5 (DSAC_K2_EXACT_AUTO in the environment of dsac_create)
+ *   "k2_hyp_walk" the hypothesis walk of the exact vector builds with a full-tile path (implicit grid, W % 64 == 0): how many consecutive 64-hypothesis tiles of
+ *                 one frame a workgroup scores on its pixel tile, loading and splitting the tile's coordinates once.  0 (default): the library decides by the
+ *                 size of the launch; 1, 2 or 4: that many wherever the kernel has the walk -- shortened to the longest walk that straddles neither a frame nor
+ *                 the end of N (N, and the hypotheses per frame of a batch, must be multiples of 64 x the walk).  Any other value is DSAC_ERR_INVALID.  Every
+ *                 output holds the same bits at every walk (DSAC_K2_HYP_WALK in the environment of dsac_create)
  *   "k2_diag"     diagnostic switches of the precise form (bit 25): degrade ONE step at a time towards the fast forms' arithmetic (scripts/r06_k2_diag.py)
  *   "k6_walk_exact" 1: the scan of the two-launch refinement step (k_refine_walk, >= 32 problems on >= 16 384 cells) decides every cell by the reference's fp64
  *                 residual; 0 (default): an fp32 test with a proven error bound discards the cells that are certainly no inliers, the fp64 residual decides the
@@ -172,10 +177,11 @@ DSAC_API int dsac_device_info(dsac_ctx* ctx, int* cus, int* clock_khz, uint64_t*
  * The environment variables DSAC_K2_VARIANT, DSAC_K2_ORDER, DSAC_K2_FLAGS, DSAC_K1_WPB, DSAC_K1_PRIO, DSAC_K1_HPW, DSAC_K1_MINW, DSAC_K1_RL, DSAC_K1_WIDE, DSAC_K1_SHARE,
  * DSAC_K1_HORN, DSAC_K1_CUS, DSAC_K4_VARIANT, DSAC_TAIL_PRIO give the initial values at dsac_create. */
 DSAC_API int dsac_set_option(dsac_ctx* ctx, const char* key, int value);
-/* The current value of every key dsac_set_option accepts, and two read-only keys that describe the last K2 launch this context ENQUEUED (host state: no
+/* The current value of every key dsac_set_option accepts, and three read-only keys that describe the last K2 launch this context ENQUEUED (host state: no
  * device access, no synchronisation):
  *   "k2_form_last"      the arithmetic form of that launch, an enum dsac_k2_form (DSAC_K2_FORM_NONE before the first launch)
  *   "k2_form_why_last"  0 when the exact form ran, else the DSAC_K2_WHY_* bits that kept it from running
+ *   "k2_hyp_walk_last"  the hypothesis walk of that launch: 1, 2 or 4 (see "k2_hyp_walk"; 0 before the first launch)
  * Unknown key, NULL context or NULL value: DSAC_ERR_INVALID. */
 typedef enum dsac_k2_form {
     DSAC_K2_FORM_NONE = 0,      /* no K2 launch yet */

@@ -85,6 +85,13 @@ def walk(code, take=()):
                 m1, m2 = re.match(r"(s\[\d+:\d+\]), 0$", a1), re.match(r"vcc, exec, (s\[\d+:\d+\])$", a2)
                 if o1 == "s_mov_b64" and o2 == "s_and_b64" and m1 and m2 and m1.group(1) == m2.group(1):
                     taken = op == "s_cbranch_vccz"
+                # ... or the same with the mask inverted, `s_andn2_b64 vcc, exec, s[a:b]; s_cbranch_vccnz` (the exit of the full-tile path's tile loop)
+                if o1 == "s_mov_b64" and o2 == "s_andn2_b64" and m1 and m2 and m1.group(1) == m2.group(1):
+                    taken = op == "s_cbranch_vccnz"
+            # ... or `s_branch L; L: s_cbranch_execnz <end>` with nothing in between that could have cleared exec: the way out of the rolled tile loop of the
+            # full-tile path (a wave that gets there runs with the lanes it had)
+            if op == "s_cbranch_execnz" and len(order) >= 2 and code[order[-2]][1] == "s_branch":
+                taken = True
             branches.append((len(order) - 1, i, taken))
             if taken:
                 i = at[tgt]
